@@ -8,10 +8,15 @@ N > 1 = one process per GPU (torch.distributed / RCCL only for the barrier + max
         timing); frames are independent, every rank processes its own batch: replicas, weak scaling,
         no data-path collective.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0: metric / value / unit / higher_is_better / dtype / ms_per_step of the --steps timed steps.
+A plain run does only that (set up, warm up, time, optionally --dump-outputs, print).  --full adds, after the timed steps:
   roofline     — the voxeliser (the north-star HBM kernel sequence), timed with HIP events on the
                  launch stream inside the timed region; algorithmic bytes per launch from SURVEY §8d.
+  extra        — side measurements (tools/bench_extra.py: H2D-inclusive rate, SECOND / sparse GEMM / NMS / PFN, ...).
   cpu_baseline — the oracle (CPU restatement of the reference path) timed on a bounded sample.
+
+--dump-outputs DIR writes what the last timed step returned (rank 0): boxes, scores (float32), labels, counts (float64, exact)
+as DIR/<name>.npy.  Inputs and weights are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -217,6 +222,16 @@ def h2d_inclusive(model, frames, steps, device, resident_fps):
             "h2d_note": "raw (N, 4) clouds from host numpy arrays every step: pinned double-buffered staging + copy stream (feeder.py)"}
 
 
+def dump_outputs(out_dir, out):
+    """what a caller of the timed path receives from its last step: boxes (B, post, 7), scores (B, post), labels (B, post),
+    counts (B) -> out_dir/<name>.npy; float32 as computed, the integer arrays as float64 (exact)"""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in zip(("boxes", "scores", "labels", "counts"), out):
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float32) if a.dtype == np.float32 else a.astype(np.float64)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def launch_ranks(n, argv):
     """`python bench.py --gpus N` without a torch.distributed launcher: start N fresh rank processes, one per GPU, with
     RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set (what tools/scripts/dist_train.sh:7 + pcdet/utils/common_utils.py:170-184
@@ -273,8 +288,12 @@ def main():
     ap.add_argument("--mode", choices=["infer", "train-ddp"], default="infer", help="train-ddp: BASELINE configs[4]'s DDP leg — "
                     "SECOND-MultiHead NuScenes bs 4 / GPU, forward + backward + DistributedDataParallel step (tools/ddp_train_bench.py)")
     ap.add_argument("--dry-run", action="store_true", help="N-rank plumbing only, CPU / gloo, no kernels (tests)")
-    ap.add_argument("--stages", action="store_true", help="also print per-stage GPU times (stderr)")
+    ap.add_argument("--stages", action="store_true", help="also print per-stage GPU times (stderr); implies --full")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure the roofline, the `extra` side "
+                    "measurements and the CPU baseline (the --no-* / --roofline-launches / --cpu-frames options apply here)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs (rank 0) as DIR/<name>.npy")
     args = ap.parse_args()
+    args.full = args.full or args.stages
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))       # before anything touches the GPU
@@ -349,6 +368,27 @@ def main():
         barrier()
         dt = time.perf_counter() - t0
     dt = dist_utils.max_over_ranks(dt, dist, device)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
+    frames_total = args.batch * args.steps * world
+    res = {
+        "metric": "frames/sec (fwd+NMS) PointPillar-KITTI", "value": frames_total / dt, "unit": "frames/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "PointPillar-KITTI bs=16 per GPU, fp32, eval BN folded: HIP voxelize + PFN; dense 2D backbone = first layer from the "
+                               "pillars (sparse implicit GEMM), stride-1 3x3 layers as Winograd F(4x4,3x3) on the fp32 MFMA, strided deblocks as one "
+                               "fused MFMA GEMM (all this repo's HIP), the two stride-2 3x3 layers MIOpen, stride-1 deblock + 1x1 heads hipBLASLt; exact "
+                               "HIP top-k + decode + batched rotated NMS; cloud_uniform 20k pts/frame, 16k pillars/frame (max_voxels cap), NMS pre 4096 "
+                               "/ post 500 / thr 0.01",
+                   "frames_per_step": args.batch, "replicas": world},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(res))
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # Voxeliser durations for the roofline: the kernels' own start / stop events (lidar_timer_*: hipExtLaunchKernel carries them, the
     # timestamps a kernel trace reports) on extra full detector steps AFTER the timed region, >= 100 launches per path, split into
@@ -440,7 +480,6 @@ def main():
             traffic_src = (f"{os.path.relpath(pmc, ROOT)} (voxelize.hip sha256 {sha}; FETCH_SIZE upper bracket + WRITE_SIZE, "
                            "separate --pmc passes)")
             break
-    frames_total = args.batch * args.steps * world
     gbs = lambda nbytes, ms: nbytes / (ms * 1e-3) / 1e9
     ratio = lambda tr, nbytes: None if tr is None else tr / nbytes
     # roofline.frac describes the path that MOVES the priced bytes: the drop-in contract (fresh output buffers, the whole padded
@@ -461,16 +500,7 @@ def main():
     else:   # --no-full-rewrite: only the timed path was measured; price it with its own bytes
         roof = roof_of(resident, own_bytes, "resident (algo 4), in-step, extra steps after the timed region, priced with its own algorithmic bytes")
     vox_ms = (resident or contract)["kernel_sum_us"] * 1e-3
-    res = {
-        "metric": "frames/sec (fwd+NMS) PointPillar-KITTI", "value": frames_total / dt, "unit": "frames/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": "PointPillar-KITTI bs=16 per GPU, fp32, eval BN folded: HIP voxelize + PFN; dense 2D backbone = first layer from the "
-                               "pillars (sparse implicit GEMM), stride-1 3x3 layers as Winograd F(4x4,3x3) on the fp32 MFMA, strided deblocks as one "
-                               "fused MFMA GEMM (all this repo's HIP), the two stride-2 3x3 layers MIOpen, stride-1 deblock + 1x1 heads hipBLASLt; exact "
-                               "HIP top-k + decode + batched rotated NMS; cloud_uniform 20k pts/frame, 16k pillars/frame (max_voxels cap), NMS pre 4096 "
-                               "/ post 500 / thr 0.01",
-                   "frames_per_step": args.batch, "replicas": world},
+    res.update({
         "roofline": {"bound": "hbm", "kernel": "lidar_voxelize = vxl_keybin_kernel (bin + zero-fill roles in one launch) + vxl_emit_kernel",
                      "achieved": roof["achieved"], "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": roof["frac"], "path": roof["path"],
                      "ms_per_launch": roof["ms_per_launch"], "alg_bytes_per_launch": alg_bytes if contract_ms is not None else own_bytes,
@@ -503,7 +533,7 @@ def main():
                                     "equivalent_contract_frac": gbs(alg_bytes, vox_ms) / HBM_PEAK_GBS,
                                     "traffic": traffic["resident"], "traffic_ratio_vs_own": ratio(traffic["resident"], own_bytes),
                                     "traffic_ratio_vs_contract": ratio(traffic["resident"], alg_bytes)}},
-    }
+    })
     if args.stages and rank == 0:
         def gpu_time(fn, n=20):
             """median GPU time of one call (per-call event pairs: a host-side pause between launches is not GPU time)"""

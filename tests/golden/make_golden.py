@@ -12,9 +12,17 @@ outputs) and are what travels to the GPU box.
                       configuration with random eval-mode BatchNorm statistics, and its own ResidualCoder.decode_torch
                       (pcdet/utils/box_coder_utils.py) on random anchors / encodings
 
-Usage:  python tests/golden/make_golden.py
+  iou3d_live.npz   <- boxes_iou_bev_cpu of the compiled reference (oracle/_ref) on synth.boxes_random(101, 150) x (102, 130)
+  ref_checks.json  <- the reference's own spconv_backbone.py, loaded from its file with `spconv` aliased to
+                      lidardetection_amd.spconv: state_dict names + shapes, num_point_features, sparse_shape of
+                      VoxelBackBone8x / VoxelResBackBone8x; and the `<native module>.<function>(` calls its operator
+                      wrappers (pcdet/ops/*/..._utils.py) make
+
+Usage:  python tests/golden/make_golden.py [pp_modules iou3d_ref bev_head iou3d_live ref_checks]   (default: all)
 """
+import json
 import os
+import re
 import sys
 import types
 
@@ -162,7 +170,63 @@ def make_bev_head():
     print("bev_head.npz", tuple(y.shape), tuple(dec.shape), len(sd))
 
 
+def make_iou3d_live():
+    build_ref.build()
+    iou = ref_loader.load("iou3d_nms_cuda")
+    a = synth.boxes_random(101, 150)
+    b = synth.boxes_random(102, 130)
+    out = torch.zeros(len(a), len(b))
+    iou.boxes_iou_bev_cpu(torch.from_numpy(a), torch.from_numpy(b), out)
+    np.savez_compressed(os.path.join(HERE, "iou3d_live.npz"), boxes_a=a, boxes_b=b, iou_bev_cpu=out.numpy())
+    print("iou3d_live.npz", tuple(out.shape))
+
+
+# the reference's pcdet/ tree (the directory build_ref compiles its ops from)
+REF_PCDET = os.path.dirname(build_ref.REF)
+# operator wrapper -> the name it imports its native module under
+NATIVE_WRAPPERS = [("ops/iou3d_nms/iou3d_nms_utils.py", "iou3d_nms_cuda"),
+                   ("ops/roiaware_pool3d/roiaware_pool3d_utils.py", "roiaware_pool3d_cuda"),
+                   ("ops/roipoint_pool3d/roipoint_pool3d_utils.py", "roipoint_pool3d_cuda"),
+                   ("ops/pointnet2/pointnet2_stack/pointnet2_utils.py", "pointnet2"),
+                   ("ops/pointnet2/pointnet2_batch/pointnet2_utils.py", "pointnet2")]
+
+
+def make_ref_checks():
+    import importlib.util
+    import lidardetection_amd.spconv as sp
+    from lidardetection_amd.pcdet.utils.cfg import AttrDict
+    saved = {k: sys.modules.get(k) for k in ("spconv", "spconv.utils")}
+    sys.modules["spconv"], sys.modules["spconv.utils"] = sp, sp.utils
+    try:
+        spec = importlib.util.spec_from_file_location("_ref_spconv_backbone", os.path.join(REF_PCDET, "models", "backbones_3d",
+                                                                                            "spconv_backbone.py"))
+        ref = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(ref)
+        backbones = {}
+        for name in ("VoxelBackBone8x", "VoxelResBackBone8x"):
+            m = getattr(ref, name)(AttrDict(), 4, np.array([1408, 1600, 40]))     # the reference passes a numpy grid size
+            backbones[name] = {"state_dict": [[k, list(v.shape)] for k, v in m.state_dict().items()],
+                               "num_point_features": int(m.num_point_features),
+                               "sparse_shape": [int(v) for v in m.sparse_shape]}
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                sys.modules.pop(k, None)
+            else:
+                sys.modules[k] = v
+    calls = []
+    for rel, alias in NATIVE_WRAPPERS:
+        src = open(os.path.join(REF_PCDET, rel)).read()
+        calls.append({"wrapper": "pcdet/" + rel, "module": alias,
+                      "functions": sorted(set(re.findall(r"\b%s\.([A-Za-z_0-9]+)\(" % re.escape(alias), src)))})
+    with open(os.path.join(HERE, "ref_checks.json"), "w") as fh:
+        json.dump({"spconv_backbones": backbones, "native_calls": calls}, fh, indent=1)
+        fh.write("\n")
+    print("ref_checks.json", {k: len(v["state_dict"]) for k, v in backbones.items()}, sum(len(c["functions"]) for c in calls))
+
+
 if __name__ == "__main__":
-    make_pp_modules()
-    make_iou3d_ref()
-    make_bev_head()
+    makers = {"pp_modules": make_pp_modules, "iou3d_ref": make_iou3d_ref, "bev_head": make_bev_head,
+              "iou3d_live": make_iou3d_live, "ref_checks": make_ref_checks}
+    for name in sys.argv[1:] or makers:
+        makers[name]()

@@ -89,61 +89,50 @@ def test_cpu_entry_points_bit_exact_vs_reference_golden(golden_dir):
     assert np.array_equal(pib, ref)
 
 
+def _ref_checks():
+    import json
+    with open(os.path.join(ROOT, "tests", "golden", "ref_checks.json")) as fh:
+        return json.load(fh)
+
+
 def test_reference_backbone_source_runs_on_this_spconv():
     """Drop-in check of the spconv mirror: the REFERENCE's own pcdet/models/backbones_3d/spconv_backbone.py, loaded from its
-    file with `spconv` aliased to lidardetection_amd.spconv, builds both backbones, and their state_dicts
-    (names + shapes = checkpoint layout) equal this repo's mirror.  Skipped where /root/reference is absent (GPU box)."""
-    import importlib.util
-    import sys
-    path = "/root/reference/pcdet/models/backbones_3d/spconv_backbone.py"
-    if not os.path.exists(path):
-        pytest.skip("reference tree not present")
-    import lidardetection_amd.spconv as sp
+    file with `spconv` aliased to lidardetection_amd.spconv, builds both backbones
+    (tests/golden/make_golden.py ref_checks), and their state_dicts (names + shapes = checkpoint layout), num_point_features
+    and sparse_shape, stored in tests/golden/ref_checks.json, equal this repo's mirror."""
     from lidardetection_amd.pcdet.models.backbones_3d import spconv_backbone as mine
     from lidardetection_amd.pcdet.utils.cfg import AttrDict
-    saved = {k: sys.modules.get(k) for k in ("spconv", "spconv.utils")}
-    sys.modules["spconv"], sys.modules["spconv.utils"] = sp, sp.utils
-    try:
-        spec = importlib.util.spec_from_file_location("_ref_spconv_backbone", path)
-        ref = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(ref)
-        for name in ("VoxelBackBone8x", "VoxelResBackBone8x"):
-            a = getattr(ref, name)(AttrDict(), 4, np.array([1408, 1600, 40]))     # the reference passes a numpy grid size
-            b = getattr(mine, name)(AttrDict(), 4, np.array([1408, 1600, 40]))
-            sa, sb = a.state_dict(), b.state_dict()
-            assert list(sa.keys()) == list(sb.keys()), name
-            assert all(sa[k].shape == sb[k].shape for k in sa), name
-            assert a.num_point_features == b.num_point_features
-            assert [int(v) for v in a.sparse_shape] == [int(v) for v in b.sparse_shape]
-    finally:
-        for k, v in saved.items():
-            if v is None:
-                sys.modules.pop(k, None)
-            else:
-                sys.modules[k] = v
+    ref = _ref_checks()["spconv_backbones"]
+    assert sorted(ref) == ["VoxelBackBone8x", "VoxelResBackBone8x"]
+    for name, a in ref.items():
+        b = getattr(mine, name)(AttrDict(), 4, np.array([1408, 1600, 40]))     # the reference passes a numpy grid size
+        sb = b.state_dict()
+        assert [k for k, _ in a["state_dict"]] == list(sb.keys()), name
+        assert all(list(sb[k].shape) == shape for k, shape in a["state_dict"]), name
+        assert a["num_point_features"] == b.num_point_features
+        assert a["sparse_shape"] == [int(v) for v in b.sparse_shape]
 
 
 def test_every_native_symbol_the_reference_wrappers_call_is_exported():
-    """Static drop-in check: scan the reference's operator wrappers for `<native module>.<function>(` calls and require each
-    function on this repo's same-named ext module.  (The wrappers themselves cannot be imported here: pcdet.utils.common_utils
-    needs the absent `quaternion` package.)  Skipped where /root/reference is absent."""
+    """Static drop-in check: the `<native module>.<function>(` calls in the reference's operator wrappers (scanned from their
+    source by tests/golden/make_golden.py ref_checks into tests/golden/ref_checks.json) must each be a function on this
+    repo's same-named ext module.  (The wrappers themselves cannot be imported: pcdet.utils.common_utils needs the absent
+    `quaternion` package.)"""
     from lidardetection_amd.ext import (iou3d_nms_cuda, pointnet2_batch_cuda, pointnet2_stack_cuda, roiaware_pool3d_cuda,
                                         roipoint_pool3d_cuda)
-    root = "/root/reference/pcdet/ops"
-    if not os.path.isdir(root):
-        pytest.skip("reference tree not present")
-    cases = [("iou3d_nms/iou3d_nms_utils.py", "iou3d_nms_cuda", iou3d_nms_cuda),
-             ("roiaware_pool3d/roiaware_pool3d_utils.py", "roiaware_pool3d_cuda", roiaware_pool3d_cuda),
-             ("roipoint_pool3d/roipoint_pool3d_utils.py", "roipoint_pool3d_cuda", roipoint_pool3d_cuda),
-             ("pointnet2/pointnet2_stack/pointnet2_utils.py", "pointnet2", pointnet2_stack_cuda),
-             ("pointnet2/pointnet2_batch/pointnet2_utils.py", "pointnet2", pointnet2_batch_cuda)]
+    mods = {"pcdet/ops/iou3d_nms/iou3d_nms_utils.py": iou3d_nms_cuda,
+            "pcdet/ops/roiaware_pool3d/roiaware_pool3d_utils.py": roiaware_pool3d_cuda,
+            "pcdet/ops/roipoint_pool3d/roipoint_pool3d_utils.py": roipoint_pool3d_cuda,
+            "pcdet/ops/pointnet2/pointnet2_stack/pointnet2_utils.py": pointnet2_stack_cuda,
+            "pcdet/ops/pointnet2/pointnet2_batch/pointnet2_utils.py": pointnet2_batch_cuda}
+    calls = _ref_checks()["native_calls"]
+    assert sorted(c["wrapper"] for c in calls) == sorted(mods)
     total = 0
-    for rel, alias, mod in cases:
-        src = open(os.path.join(root, rel)).read()
-        names = set(re.findall(r"\b%s\.([A-Za-z_0-9]+)\(" % re.escape(alias), src))
-        assert names, rel
-        missing = sorted(n for n in names if not callable(getattr(mod, n, None)))
-        assert not missing, (rel, missing)
+    for c in calls:
+        names = c["functions"]
+        assert names, c["wrapper"]
+        missing = sorted(n for n in names if not callable(getattr(mods[c["wrapper"]], n, None)))
+        assert not missing, (c["wrapper"], missing)
         total += len(names)
     assert total >= 20
 
