@@ -474,6 +474,32 @@ int lidar_post_nms_gather(const float *boxes, const float *top_scores, const lon
                           const long long *keep, const int *num_keep, int batch, int k, long long n, int keep_stride, int post,
                           float *out_boxes, float *out_scores, long long *out_labels, int *out_num, void *stream);
 
+/* ------------------------------------------------------------------ anchor target assignment (training)
+ * AxisAlignedTargetAssigner.assign_targets (pcdet/models/dense_heads/target_assigner/axis_aligned_target_assigner.py:37-129,
+ * assign_targets_single :131-210; built in anchor_head_template.py:55-72, called from :90-101) on its deterministic path
+ * (POS_FRACTION < 0, MATCH_HEIGHT False) for a whole batch and every anchor class, no host synchronisation (csrc/anchor_assign.hip).
+ * Matching: nearest-BEV IoU (pcdet/utils/box_utils.py:238-287, limit_period pcdet/utils/common_utils.py:52-55); targets:
+ * ResidualCoder.encode_torch (pcdet/utils/box_coder_utils.py:13-42).
+ *   anchors, counts, per_loc, out_off, matched, unmatched, remap   HOST arrays of num_classes (<= 16) entries, passed by value in
+ *       the kernel arguments: DEVICE pointer to the class's contiguous (counts[k], anchor_dim) anchors, anchors per output location,
+ *       output offset, thresholds, and the SEPERATE_MULTIHEAD label id (> 0) or 0 = the gt's own class id.  Anchor i of class k goes
+ *       to output anchor (i / per_loc[k]) * a_total + out_off[k] + i % per_loc[k] (single head: the view(*fmap, -1) + cat(dim=-1)
+ *       of :102-115; multihead: per_loc = counts, out_off = running sum, :92-100).
+ *   class_of_id   HOST (128) int8: entry id + 64, for gt class ids -64..63 -> anchor class index or -1 (class_names[id - 1] ==
+ *                 anchor class name with numpy's wrap, :61-66; ids past the name list, where the reference raises, match none)
+ *   gt (batch, max_gt, gt_cols) f32 [box (gt_cols - 1) | class id]; gt_enlarged: same shape or NULL (its boxes are encoded)
+ *   code_size == 6 + (sincos ? 2 : 1) + min(anchor_dim, gt_cols - 1) - 7
+ *   -> labels (batch, n_total) i32, targets (batch, n_total, code_size) f32, weights (batch, n_total) f32; n_total = sum counts.
+ *   targets are encoded for the reference's fg_inds (forced or >= matched, class > 0, before its background pass, :176), so with
+ *   matched < unmatched a label-0 anchor may carry targets; weights follow the final labels.
+ *   norm_by_num_examples: weights of labels > 0 are 1 / max(#labels >= 0 of the (frame, class), 1) (:201-205); one more launch. */
+size_t lidar_anchor_assign_workspace_bytes(int batch, int max_gt, int num_classes);
+int lidar_anchor_assign(const float *const *anchors, const long long *counts, const long long *per_loc, const long long *out_off,
+                        const float *matched, const float *unmatched, const int *remap, int num_classes, int anchor_dim,
+                        long long a_total, const signed char *class_of_id, const float *gt, const float *gt_enlarged, int batch,
+                        int max_gt, int gt_cols, int code_size, int sincos, int norm_by_num_examples, int *labels, float *targets,
+                        float *weights, void *ws, size_t ws_bytes, void *stream);
+
 /* HeightCompression in one pass (pcdet/models/backbones_2d/map_to_bev/height_compression.py:21-24): the (N, C*D, H, W) BEV
  * map of a sparse tensor written directly channels-last: out[b][h][w][c*D + d]; D <= 4, channels % 4 == 0; same workspace
  * as lidar_sparse_to_dense. */

@@ -121,6 +121,9 @@ SIGNATURES = {
     "lidar_anchor_scores_hist": (i32, [vp, i32, C.c_longlong, i32, i32, i32, i32, f32, vp, vp, vp, sz, vp]),
     "lidar_topk_desc": (i32, [vp, i32, C.c_longlong, i32, f32, f32, i32, vp, vp, vp, vp, sz, vp]),
     "lidar_post_nms_gather": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, C.c_longlong, i32, i32, vp, vp, vp, vp, vp]),
+    "lidar_anchor_assign_workspace_bytes": (sz, [i32, i32, i32]),
+    "lidar_anchor_assign": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, C.c_longlong, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp,
+                                  vp, vp, vp, sz, vp]),
     "lidar_rotate_iou_eval": (i32, [vp, i32, vp, i32, i32, vp, vp]),
     "lidar_boxes_iou_bev_cpu": (i32, [vp, i32, vp, i32, vp]),
     "lidar_points_in_boxes_cpu": (i32, [vp, i32, vp, i32, vp]),
