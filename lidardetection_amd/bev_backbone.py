@@ -124,6 +124,16 @@ def deconv_pack(w_kn):
     return packed
 
 
+# largest map (input or output, bytes) csrc/deconv_gemm.hip addresses: it loads and stores with 32-bit byte offsets
+# (lidar_deconv_gemm_nhwc refuses 2^31 - 1 and more).  A list so that tests can lower it.
+_DECONV_MAX_BYTES = [2 ** 31 - 1]
+
+
+def deconv_fits(B, K, h, w, s, out_c):
+    """the fused deblock kernel can read the (B, K, h, w) map and write the (B, out_c, s*h, s*w) concat map; else the two-step path"""
+    return B * h * w * K * 4 < _DECONV_MAX_BYTES[0] and B * h * w * s * s * out_c * 4 < _DECONV_MAX_BYTES[0]
+
+
 def deconv_gemm_into_(x, packed, bias, s, out, out_offset=0, relu=True):
     """x (B, K, h, w) channels-last -> out[:, out_offset:out_offset + C_up] (B, C_out, s*h, s*w channels-last) = act(ConvTranspose2d
     (kernel == stride == s)(x) + bias): one fp32-MFMA kernel, no temporary, no pixel-shuffle pass (csrc/deconv_gemm.hip)"""
@@ -182,6 +192,17 @@ def _fold(weight, bn, out_dim, conv_bias=None):
     return (weight.detach() * scale.view(shape)), shift.contiguous()
 
 
+class _FoldedConv(tuple):
+    """One folded Conv2d/BN/ReLU layer of a block.  Unpacks as (weight, shift, stride, conv padding (h, w), Winograd filters or None);
+    .dilation, .groups and .zero_pad (an asymmetric ZeroPad2d (left, right, top, bottom), applied with F.pad, or None: a symmetric one
+    is folded into the padding) carry the rest of the layer's settings."""
+
+    def __new__(cls, w, b, stride, pad, packed, dilation, groups, zero_pad):
+        self = super().__new__(cls, (w, b, stride, pad, packed))
+        self.dilation, self.groups, self.zero_pad = dilation, groups, zero_pad
+        return self
+
+
 class FoldedBEVBackbone:
     """Built from the (eval-mode) reference-shaped modules; call with the channels-last canvas."""
 
@@ -192,22 +213,32 @@ class FoldedBEVBackbone:
         for blk, de in zip(blocks, deblocks):
             convs, mods, i = [], list(blk), 0
             while i < len(mods):
-                pad = 0
+                zpad = (0, 0, 0, 0)
                 if isinstance(mods[i], nn.ZeroPad2d):
-                    pad, i = int(mods[i].padding[0]), i + 1
+                    zpad, i = tuple(int(v) for v in mods[i].padding), i + 1         # (left, right, top, bottom)
                 conv, bn = mods[i], mods[i + 1]
                 assert isinstance(conv, nn.Conv2d) and isinstance(bn, nn.BatchNorm2d) and isinstance(mods[i + 2], nn.ReLU)
+                assert conv.padding_mode == "zeros" and not isinstance(conv.padding, str), "FoldedBEVBackbone: explicit zero padding only"
                 w, b = _fold(conv.weight, bn, 0, conv.bias)
+                # a symmetric ZeroPad2d is the conv's own zero padding (no padded copy); anything else stays a separate F.pad
+                pad, zp = tuple(int(v) for v in conv.padding), None
+                if zpad[0] == zpad[1] >= 0 and zpad[2] == zpad[3] >= 0:
+                    pad = (pad[0] + zpad[2], pad[1] + zpad[0])
+                else:
+                    zp = zpad
+                plain = tuple(conv.dilation) == (1, 1) and conv.groups == 1 and zp is None
                 # stride-1 3x3 layers (LAYER_NUMS per block, base_bev_backbone.py:40-45; SECOND's first block opens with one too):
                 # Winograd on the matrix cores with shift + ReLU in the kernel (csrc/wino43_conv.hip F(4x4, 3x3), csrc/wino_conv.hip F(2x2, 3x3))
                 packed = None
-                if (_WINO[0] and w.is_cuda and tuple(conv.kernel_size) == (3, 3) and tuple(conv.stride) == (1, 1)
-                        and tuple(conv.dilation) == (1, 1) and conv.groups == 1 and conv.padding[0] + pad == 1
-                        and conv.padding[1] + pad == 1 and wino.supported(w.shape[1], w.shape[0])):
+                if (_WINO[0] and w.is_cuda and plain and tuple(conv.kernel_size) == (3, 3) and tuple(conv.stride) == (1, 1)
+                        and pad == (1, 1) and wino.supported(w.shape[1], w.shape[0])):
                     packed = wino.pack_auto(w)        # F(4x4, 3x3) where supported (Cout % 64 == 0), else F(2x2, 3x3)
-                convs.append((w.contiguous(memory_format=torch.channels_last), b, conv.stride, conv.padding[0] + pad, packed))
+                convs.append(_FoldedConv(w.contiguous(memory_format=torch.channels_last), b, tuple(conv.stride), pad, packed,
+                                         tuple(conv.dilation), conv.groups, zp))
                 i += 3
             up, bn = de[0], de[1]
+            assert tuple(up.dilation) == (1, 1) and up.groups == 1 and up.padding_mode == "zeros", \
+                "FoldedBEVBackbone: deblocks with dilation, groups or non-zero padding modes are not supported"
             if isinstance(up, nn.ConvTranspose2d):
                 w, b = _fold(up.weight, bn, 1, up.bias)
                 if tuple(up.kernel_size) == tuple(up.stride) and up.stride[0] == up.stride[1] and \
@@ -218,10 +249,10 @@ class FoldedBEVBackbone:
                     if (_DECONV[0] and w.is_cuda and up.stride[0] > 1 and deconv_supported(w_kn.shape[0], up.stride[0], b.numel())):
                         upc = ("deconv_mfma", (deconv_pack(w_kn), w_kn), b, up.stride[0])   # csrc/deconv_gemm.hip (+ the plain weight: maps of 2 GiB and more take the two-step path)
                 else:
-                    upc = ("deconv", w.contiguous(memory_format=torch.channels_last), b, up.stride)
+                    upc = ("deconv", w.contiguous(memory_format=torch.channels_last), b, (up.stride, up.padding, up.output_padding))
             else:   # stride < 1 in the reference config: a strided Conv2d (base_bev_backbone.py:60-69)
                 w, b = _fold(up.weight, bn, 0, up.bias)
-                upc = ("conv", w.contiguous(memory_format=torch.channels_last), b, up.stride)
+                upc = ("conv", w.contiguous(memory_format=torch.channels_last), b, (up.stride, up.padding))
             self.stages.append((convs, upc))
         self.up_channels = [s[1][2].numel() for s in self.stages]
         for h in heads:
@@ -235,12 +266,14 @@ class FoldedBEVBackbone:
         self._streams = None
         # the first layer as a sparse implicit GEMM over the pillars (csrc/pillar.hip lidar_pillar_conv_table): (k*k, Cin, Cout) weights
         self._first_sparse = None
-        w0, b0, st0, pad0, _ = self.stages[0][0][0]
+        c0 = self.stages[0][0][0]
+        w0, b0, st0, pad0, _ = c0
         k0 = w0.shape[2]
-        if (w0.is_cuda and w0.shape[2] == w0.shape[3] and st0[0] == st0[1] and k0 * k0 <= 31):
+        if (w0.is_cuda and w0.shape[2] == w0.shape[3] and st0[0] == st0[1] and pad0[0] == pad0[1] and k0 * k0 <= 31
+                and c0.dilation == (1, 1) and c0.groups == 1 and c0.zero_pad is None):   # (the neighbour table knows one stride and one symmetric pad)
             from .spconv import ops as _sops
             if _sops.sorted_gemm_supported(k0 * k0, w0.shape[1], w0.shape[0]):
-                self._first_sparse = (w0.permute(2, 3, 1, 0).reshape(k0 * k0, w0.shape[1], w0.shape[0]).contiguous(), b0, k0, int(st0[0]), int(pad0))
+                self._first_sparse = (w0.permute(2, 3, 1, 0).reshape(k0 * k0, w0.shape[1], w0.shape[0]).contiguous(), b0, k0, int(st0[0]), int(pad0[0]))
 
     def first_layer_from_pillars(self, pm):
         """pm: pillar_ops.PillarMap -> act(conv0(scatter(pm)) + shift) as a channels-last (B, Cout, OH, OW) map WITHOUT building the
@@ -262,13 +295,16 @@ class FoldedBEVBackbone:
         of the first layer (first_layer_from_pillars)."""
         x, cat, off = canvas, None, 0
         for si, (convs, (kind, uw, ub, ustride)) in enumerate(self.stages):
-            for ci, (w, b, stride, pad, packed) in enumerate(convs):
+            for ci, cv in enumerate(convs):
                 if first_done and si == 0 and ci == 0:
                     continue
+                w, b, stride, pad, packed = cv
                 if packed is not None and _WINO[0] and x.is_contiguous(memory_format=torch.channels_last):
                     x = wino.conv3x3_auto(x, packed, w.shape[0], b, True)
                     continue
-                x = F.conv2d(x, w, None, stride, pad)
+                if cv.zero_pad is not None:
+                    x = F.pad(x, cv.zero_pad)
+                x = F.conv2d(x, w, None, stride, pad, cv.dilation, cv.groups)
                 if not x.is_contiguous(memory_format=torch.channels_last):
                     x = x.contiguous(memory_format=torch.channels_last)
                 bias_act_(x, b)
@@ -276,7 +312,7 @@ class FoldedBEVBackbone:
             y = None
             if kind == "deconv_mfma":
                 oh, ow = h * ustride, w * ustride
-                if B * oh * ow * sum(self.up_channels) * 4 >= 2 ** 31 - 1:       # the fused kernel stores with 32-bit byte offsets
+                if not deconv_fits(B, x.shape[1], h, w, ustride, sum(self.up_channels)):
                     kind, uw = "gemm", uw[1]
                     y = rows_gemm(x.permute(0, 2, 3, 1).reshape(B * h * w, -1), uw)
                 else:
@@ -286,7 +322,7 @@ class FoldedBEVBackbone:
                 if not (ustride == 1 and _LT_GEMM[0]):
                     y = rows_gemm(x.permute(0, 2, 3, 1).reshape(B * h * w, -1), uw)  # the NHWC map IS the row-major A
             else:
-                y = F.conv_transpose2d(x, uw, None, ustride) if kind == "deconv" else F.conv2d(x, uw, None, ustride)
+                y = F.conv_transpose2d(x, uw, None, *ustride) if kind == "deconv" else F.conv2d(x, uw, None, *ustride)
                 if not y.is_contiguous(memory_format=torch.channels_last):
                     y = y.contiguous(memory_format=torch.channels_last)
                 oh, ow = y.shape[2], y.shape[3]

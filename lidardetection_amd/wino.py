@@ -93,23 +93,36 @@ def conv3x3_f43(x, packed, cout, bias=None, relu=True, out=None, out_offset=0, c
 
 
 def pack_auto(w):
-    """-> [kind, packed filters, weight]: F(4x4, 3x3) where csrc/wino43_conv.hip takes the layer (and LIDAR_WINO_F43 != 0), else
-    F(2x2, 3x3).  The weight rides along: a map too large for the F(4x4) kernel's 32-bit byte offsets (>= 2 GiB) is served by F(2x2),
-    packed on first need."""
+    """-> [kind, packed filters, weight, F(2x2) filters]: F(4x4, 3x3) where csrc/wino43_conv.hip takes the layer (and LIDAR_WINO_F43
+    != 0), else F(2x2, 3x3).  An "f43" entry carries the F(2x2, 3x3) filters too (16 Cin Cout more floats), packed here on the
+    caller's stream: a map too large for the F(4x4) kernel's 32-bit byte offsets (f43_fits) is served by F(2x2), and filters packed
+    on first need would be written on whichever stream met that map first while another stream may already read them."""
     if _F43[0] and supported43(w.shape[1], w.shape[0]):
-        return ["f43", pack_weights43(w), w.detach()]
+        return ["f43", pack_weights43(w), w.detach(), pack_weights(w)]
     return ["f23", pack_weights(w), None]
+
+
+# largest map (input or output, bytes) the F(4x4, 3x3) kernel addresses: it stores with 32-bit byte offsets
+# (lidar_wino43_conv3x3_nhwc refuses 2^31 - 1 and more).  A list so that tests can lower it.
+_F43_MAX_BYTES = [2 ** 31 - 1]
+
+
+def f43_fits(x_shape, cout, out=None):
+    """the F(4x4, 3x3) kernel can serve conv3x3_auto(x, ..., cout, out=out) for an x of shape x_shape (B, Cin, H, W): input and
+    output map both under _F43_MAX_BYTES, the output being `out` when given, else the (B, cout, H, W) map conv3x3_auto allocates.
+    Pure host arithmetic (no library call)."""
+    B, cin, H, W = (int(v) for v in x_shape)
+    out_elems = out.numel() if out is not None else B * int(cout) * H * W
+    return B * cin * H * W * 4 < _F43_MAX_BYTES[0] and out_elems * 4 < _F43_MAX_BYTES[0]
 
 
 def conv3x3_auto(x, packed, cout, bias=None, relu=True, out=None, out_offset=0):
     """conv3x3 with the filters of pack_auto"""
     kind, p = packed[0], packed[1]
     if kind == "f43":
-        if x.numel() * 4 < 2 ** 31 - 1 and (out is None or out.numel() * 4 < 2 ** 31 - 1):
+        if f43_fits(x.shape, cout, out):
             return conv3x3_f43(x, p, cout, bias, relu, out, out_offset)
-        if len(packed) < 4:                            # oversize map: F(2x2) filters, packed once
-            packed.append(pack_weights(packed[2]))
-        p = packed[3]
+        p = packed[3]                                  # oversize map: F(2x2)
     return conv3x3(x, p, cout, bias, relu, out, out_offset)
 
 

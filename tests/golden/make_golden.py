@@ -12,13 +12,21 @@ outputs) and are what travels to the GPU box.
                       configuration with random eval-mode BatchNorm statistics, and its own ResidualCoder.decode_torch
                       (pcdet/utils/box_coder_utils.py) on random anchors / encodings
 
+  bev_wide.npz     <- the reference's own BaseBEVBackbone again, in float64, on a configuration wide enough for the production
+                      routes of the folded backbone (NUM_FILTERS [64, 64], NUM_UPSAMPLE_FILTERS [128, 128], input 64 channels):
+                      F(4x4, 3x3) Winograd for both stride-1 layers, the fused deblock GEMM for the stride-2 deblock and the sparse
+                      first layer from the pillars.  Input 2 x 64 x 24 x 20 shaped like a pillar canvas (~12 % of the cells hold a
+                      non-zero vector, the rest exactly 0).  Conv / deconv weights are int8 codes (key suffix kept: `bev.<name>`,
+                      value = code * 2^-9, the scale stored as `weight_scale`), so the float32 weights a test rebuilds are the exact
+                      values the reference ran with; BatchNorm entries are float32; spatial_features_2d is rounded to float32
+
   iou3d_live.npz   <- boxes_iou_bev_cpu of the compiled reference (oracle/_ref) on synth.boxes_random(101, 150) x (102, 130)
   ref_checks.json  <- the reference's own spconv_backbone.py, loaded from its file with `spconv` aliased to
                       lidardetection_amd.spconv: state_dict names + shapes, num_point_features, sparse_shape of
                       VoxelBackBone8x / VoxelResBackBone8x; and the `<native module>.<function>(` calls its operator
                       wrappers (pcdet/ops/*/..._utils.py) make
 
-Usage:  python tests/golden/make_golden.py [pp_modules iou3d_ref bev_head iou3d_live ref_checks]   (default: all)
+Usage:  python tests/golden/make_golden.py [pp_modules iou3d_ref bev_head bev_wide iou3d_live ref_checks]   (default: all)
 """
 import json
 import os
@@ -128,15 +136,28 @@ def make_iou3d_ref():
     print("iou3d_ref.npz", out.shape, out_n.shape, int(pib.sum()))
 
 
-def make_bev_head():
+def _load_file(name, path):
     import importlib.util
+    spec = importlib.util.spec_from_file_location(name, path)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
 
-    def load(name, path):
-        spec = importlib.util.spec_from_file_location(name, path)
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-        return mod
 
+def _savez_reproducible(path, **arrays):
+    """np.savez_compressed with a fixed member timestamp: the same arrays give the same bytes on every run"""
+    import io
+    import zipfile
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_DEFLATED) as zf:
+        for key, val in arrays.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(val), allow_pickle=False)
+            zf.writestr(zipfile.ZipInfo(key + ".npy", date_time=(1980, 1, 1, 0, 0, 0)), buf.getvalue(),
+                        compress_type=zipfile.ZIP_DEFLATED)
+
+
+def make_bev_head():
+    load = _load_file
     bev = load("_ref_base_bev_backbone", "/root/reference/pcdet/models/backbones_2d/base_bev_backbone.py")
     coder = load("_ref_box_coder_utils", "/root/reference/pcdet/utils/box_coder_utils.py")
     cfg = types.SimpleNamespace(LAYER_NUMS=[1, 2], LAYER_STRIDES=[2, 2], NUM_FILTERS=[16, 32], UPSAMPLE_STRIDES=[1, 2],
@@ -168,6 +189,46 @@ def make_bev_head():
     np.savez_compressed(os.path.join(HERE, "bev_head.npz"), bev_input=x.numpy(), bev_output=y.numpy(),
                         decode_anchors=anchors, decode_enc=enc, decode_out=dec.numpy(), **sd)
     print("bev_head.npz", tuple(y.shape), tuple(dec.shape), len(sd))
+
+
+def make_bev_wide():
+    bev = _load_file("_ref_base_bev_backbone", "/root/reference/pcdet/models/backbones_2d/base_bev_backbone.py")
+    cfg = types.SimpleNamespace(LAYER_NUMS=[1, 1], LAYER_STRIDES=[2, 2], NUM_FILTERS=[64, 64], UPSAMPLE_STRIDES=[1, 2],
+                                NUM_UPSAMPLE_FILTERS=[128, 128])
+    cfg.get = lambda k, d=None: getattr(cfg, k, d)
+    torch.manual_seed(21)
+    m = bev.BaseBEVBackbone(cfg, input_channels=64)
+    g = torch.Generator().manual_seed(22)
+    scale = 2.0 ** -9
+    codes = {}
+    with torch.no_grad():
+        for name, mod in m.named_modules():
+            if isinstance(mod, (torch.nn.Conv2d, torch.nn.ConvTranspose2d)):
+                # int8 codes with a spread of about 1/sqrt(fan-in) (in units of the scale): the activations keep their size
+                fan_in = mod.weight.shape[1 if isinstance(mod, torch.nn.Conv2d) else 0] * mod.weight[0, 0].numel()
+                c = torch.round(torch.randn(mod.weight.shape, generator=g) * (1.0 / scale) / fan_in ** 0.5).clamp_(-127, 127)
+                codes[name + ".weight"] = c.to(torch.int8)
+                mod.weight.copy_(c * scale)
+            elif isinstance(mod, torch.nn.BatchNorm2d):
+                mod.running_mean.copy_(torch.empty(mod.num_features).uniform_(-0.3, 0.3, generator=g))
+                mod.running_var.copy_(torch.empty(mod.num_features).uniform_(0.6, 1.4, generator=g))
+                mod.weight.copy_(torch.empty(mod.num_features).uniform_(0.5, 1.5, generator=g))
+                mod.bias.copy_(torch.empty(mod.num_features).uniform_(-0.3, 0.3, generator=g))
+    m.eval()
+    B, C, H, W = 2, 64, 24, 20
+    occ = torch.rand(B, H, W, generator=g) < 0.12                     # pillar-like occupancy; empty cells are exactly 0
+    x = torch.randn(B, C, H, W, generator=g) * occ[:, None].float()
+    assert bool((x.abs().sum(1) > 0).eq(occ).all())
+    sd = {k: v.clone() for k, v in m.state_dict().items()}        # float32, before the module is cast
+    with torch.no_grad():
+        y = m.double()({"spatial_features": x.double()})["spatial_features_2d"].float()
+    arrays = {"bev_input": x.numpy(), "bev_output": y.numpy(), "weight_scale": np.float32(scale)}
+    for k, v in sd.items():
+        arrays["bev." + k] = codes[k].numpy() if k in codes else v.numpy()
+    path = os.path.join(HERE, "bev_wide.npz")
+    _savez_reproducible(path, **arrays)
+    print("bev_wide.npz", tuple(y.shape), "occupied", int(occ.sum()), "of", occ.numel(), "|y|max %.3f" % float(y.abs().max()),
+          os.path.getsize(path), "bytes")
 
 
 def make_iou3d_live():
@@ -227,6 +288,6 @@ def make_ref_checks():
 
 if __name__ == "__main__":
     makers = {"pp_modules": make_pp_modules, "iou3d_ref": make_iou3d_ref, "bev_head": make_bev_head,
-              "iou3d_live": make_iou3d_live, "ref_checks": make_ref_checks}
+              "bev_wide": make_bev_wide, "iou3d_live": make_iou3d_live, "ref_checks": make_ref_checks}
     for name in sys.argv[1:] or makers:
         makers[name]()

@@ -228,3 +228,36 @@ def test_trim_padding_cuts_capacity_sized_tensors_to_their_true_rows():
     assert idict["spconv2"]["in_indices"].shape[0] == 10 and "order" not in idict["spconv2"]
     assert idict["subm2"]["nbr"].shape == (11, 27) and idict["subm2"]["nbr_t"] is idict["subm2"]["nbr"] and "order" not in idict["subm2"]
     assert idict["subm1"]["nbr"].shape == (10, 27) and idict["subm1"]["order"] == "kept"
+
+
+def test_winograd_and_deblock_size_predicates(monkeypatch):
+    """wino.f43_fits / bev_backbone.deconv_fits decide, on the host alone, when a map is too large for the 32-bit byte offsets of
+    the F(4x4, 3x3) kernel and of the fused deblock (lidar_wino43_conv3x3_nhwc / lidar_deconv_gemm_nhwc refuse >= 2^31 - 1 bytes).
+    The output counts whether or not the caller passes it: SECOND-MultiHead's merged first branch layer (64 -> 2304 channels on
+    128 x 128) at bs 16 has a small input and a 2.4 GB output, allocated by conv3x3_auto itself."""
+    import torch
+    from lidardetection_amd import bev_backbone, wino
+
+    def no_library():
+        raise AssertionError("the size predicates must not load the HIP library")
+    monkeypatch.setattr(_lib, "lib", no_library)
+    assert not wino.f43_fits((16, 64, 128, 128), 2304)                     # SECOND-MultiHead bs 16, out=None
+    assert wino.f43_fits((14, 64, 128, 128), 2304)                         # 2.11e9 bytes: still under 2^31 - 1
+    assert not wino.f43_fits((15, 64, 128, 128), 2304)
+    # PointPillar-KITTI bs 16: the stride-1 layers of the three blocks (248 x 216, 124 x 108, 62 x 54) and SECOND's 200 x 176 ones
+    for shape, cout in (((16, 64, 248, 216), 64), ((16, 128, 124, 108), 128), ((16, 256, 62, 54), 256),
+                        ((16, 128, 200, 176), 128), ((16, 256, 100, 88), 256)):
+        assert wino.f43_fits(shape, cout), shape
+    big_out = torch.empty((16, 2304, 128, 128), device="meta")              # shape only, nothing allocated
+    small_out = torch.empty((16, 64, 128, 128), device="meta")
+    assert not wino.f43_fits((16, 64, 128, 128), 64, out=big_out)           # a caller-supplied output that is too large
+    assert wino.f43_fits((16, 64, 128, 128), 64, out=small_out)
+    assert not wino.f43_fits((16, 2304, 128, 128), 64)                      # ... or an input that is
+    # the limit is the module-level one (tests lower it to reach the fallback on small maps)
+    monkeypatch.setattr(wino, "_F43_MAX_BYTES", [2 * 64 * 8 * 8 * 4 + 1])
+    assert wino.f43_fits((2, 64, 8, 8), 64) and not wino.f43_fits((2, 64, 8, 8), 128)
+    # fused deblock: PointPillar bs 16 (128 x 124 x 108 -> 384 x 248 x 216 concat map) fits, 2.4 GB of concat map does not
+    assert bev_backbone.deconv_fits(16, 128, 124, 108, 2, 384)
+    assert not bev_backbone.deconv_fits(16, 256, 100, 88, 2, 1024)
+    monkeypatch.setattr(bev_backbone, "_DECONV_MAX_BYTES", [2 * 64 * 6 * 5 * 4 * 4])
+    assert not bev_backbone.deconv_fits(2, 64, 6, 5, 2, 64) and bev_backbone.deconv_fits(2, 64, 6, 5, 2, 63)

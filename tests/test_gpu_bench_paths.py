@@ -54,6 +54,37 @@ def _to_device(frames, dev):
     return pts, offs
 
 
+def _head_errs(got, want, tag, what):
+    """(cls, box, dir) of the folded forward vs a stock forward of the same frames: max |error| / max(1, |want|max) per output,
+    each <= 1e-4 (README "Parity")"""
+    errs = []
+    for a, b, name in zip(got, want, ("cls", "box", "dir")):
+        assert a.shape == b.shape, (tag, what, name)
+        a, b = a.double().cpu(), b.double().cpu()
+        errs.append(float((a - b).abs().max()) / max(1.0, float(b.abs().max())))
+        assert errs[-1] <= 1e-4, (tag, what, name, errs[-1])
+    return errs
+
+
+# frames of the `short` batch replayed in fp64: both part-batches of the two-stream split (frames 0-7 | 8-15) including the two next
+# to the split, and frame 12, which has no points at all
+FP64_FRAMES = [2, 7, 8, 12]
+
+
+def _stock_fp64(m, canvas, frames):
+    """the model's stock modules (deep copies on the CPU, float64) on `frames` of the canvas -> cls, box, dir as split_heads gives"""
+    import copy
+    mods = [copy.deepcopy(mod).cpu().double() for mod in (m.blocks, m.deblocks, m.conv_cls, m.conv_box, m.conv_dir_cls)]
+    x = canvas[frames].cpu().double().contiguous()
+    ups = []
+    with torch.no_grad():
+        for blk, de in zip(mods[0], mods[1]):
+            x = blk(x)
+            ups.append(de(x))
+        x = torch.cat(ups, 1)
+        n = len(frames)
+        return tuple(hd(x).permute(0, 2, 3, 1).reshape(n, -1, c) for hd, c in zip(mods[2:], (m.num_class, 7, m.num_dir_bins)))
+
 def _check_voxels(vox, frames, vs, rng, P, maxv, tag):
     """the model's (resident) voxel buffers vs the sequential oracle, frame by frame; -> oracle (voxels, coords4, counts)"""
     offsets = vox["voxel_offsets"].cpu().numpy()
@@ -141,6 +172,10 @@ def test_pointpillar_kitti_bs16_timed_path_over_successive_batches(dev):
             e1 = float((x1 - ref1).abs().max())
             assert e1 <= 1e-4 * max(1.0, float(ref1.abs().max())), (tag, e1)
             del ref1, x1
+            # the head output itself: every frame against the stock modules on the canvas (fp32), some against fp64
+            got = m.split_heads(head)
+            e_stock = _head_errs(got, m.backbone_head_stock(canvas), tag, "stock")
+            e64 = _head_errs([t[FP64_FRAMES] for t in got], _stock_fp64(m, canvas, FP64_FRAMES), tag, "fp64") if tag == "short" else None
         ev, ec, en = _check_voxels(vox, frames, synth.PP_VOXEL, synth.PP_RANGE, 32, 16000, tag)
         total = len(ev)
         # PFN rows: the canvas holds them; recompute the kernel's rows with the model's own arguments (same kernel, same bits)
@@ -160,6 +195,8 @@ def test_pointpillar_kitti_bs16_timed_path_over_successive_batches(dev):
         info = _check_post(m, head, out, tag)
         print(f"[pp bs16 {tag}] rows {total} pfn err {err:.1e} kept/frame min {min(info['kept'])} max {max(info['kept'])} "
               f"candidates min {min(info['candidates'])} ties left out at the k-th score {info['excluded_ties_at_kth']}")
+        print(f"[pp bs16 {tag}] head err/scale vs stock cls {e_stock[0]:.1e} box {e_stock[1]:.1e} dir {e_stock[2]:.1e}"
+              + (f"; vs fp64 (frames {FP64_FRAMES}) cls {e64[0]:.1e} box {e64[1]:.1e} dir {e64[2]:.1e}" if e64 else ""))
         assert max(info["kept"]) > 0
     # the whole forward in one call gives the same detections as the staged calls of the last batch
     # the voxeliser's other entry (device offsets only) gives the same bits as the host-offset entry used above.  (The whole forward
@@ -190,6 +227,7 @@ def test_second_kitti_bs16_timed_path_over_successive_batches(dev):
             canvas = m.sparse_backbone(feats, coords)
             (head,) = m.backbone_head(canvas)
             out = m.post_process(head)
+            e_stock = _head_errs(m.split_heads(head), m.backbone_head_stock(canvas), tag, "stock")   # every frame, fp32 stock modules
         ev, ec, en = _check_voxels(m._vox_out, frames, synth.SEC_VOXEL, synth.SEC_RANGE, 5, 16000, tag)
         total = len(ev)
         assert feats.shape[0] == total and torch.equal(coords.cpu(), torch.from_numpy(ec.astype(np.int32)))
@@ -215,6 +253,7 @@ def test_second_kitti_bs16_timed_path_over_successive_batches(dev):
         info = _check_post(m, head, out, tag)
         print(f"[second bs16 {tag}] voxels {total} out sites {len(idx)} dense err/scale {err:.1e} kept/frame min {min(info['kept'])} "
               f"max {max(info['kept'])} ties left out at the k-th score {info['excluded_ties_at_kth']}")
+        print(f"[second bs16 {tag}] head err/scale vs stock cls {e_stock[0]:.1e} box {e_stock[1]:.1e} dir {e_stock[2]:.1e}")
     # the voxeliser's other entry (device offsets only) gives the same bits as the host-offset entry used above.  (The whole forward
     # is NOT compared bit for bit between two calls: MIOpen's global-K-split convolution kernels accumulate with atomics, so the head
     # output moves in its last bit from call to call — 1.2e-7 on PointPillar, tools/split_determinism_probe.py — and every call is

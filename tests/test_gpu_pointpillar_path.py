@@ -697,6 +697,187 @@ def test_bev_backbone_and_box_decode_vs_reference_golden(dev, golden_dir):
     np.testing.assert_allclose(boxes[0].cpu().numpy(), g["decode_out"], rtol=2e-6, atol=1e-6)
 
 
+def _bev_wide_inputs(golden_dir, dev):
+    """tests/golden/bev_wide.npz -> (fixture, module holder on `dev`, channels-last canvas, PillarMap of its occupied cells)"""
+    import copy
+    from test_oracle_pins import _bev_wide
+    g, h = _bev_wide(golden_dir)
+    h = copy.deepcopy(h).to(dev).to(memory_format=torch.channels_last)
+    x = torch.from_numpy(g["bev_input"])
+    B, C, H, W = x.shape
+    b, yy, xx = (x.abs().sum(1) > 0).nonzero(as_tuple=True)
+    perm = torch.randperm(len(b), generator=torch.Generator().manual_seed(5))       # pillars in no particular order
+    b, yy, xx = b[perm], yy[perm], xx[perm]
+    feats = x.permute(0, 2, 3, 1)[b, yy, xx].contiguous().to(dev)
+    coords = torch.stack([b, torch.zeros_like(b), yy, xx], 1).to(torch.int32).to(dev)
+    total = torch.tensor([len(b)], dtype=torch.int32, device=dev)
+    pm = pillar_ops.PillarMap(feats, coords, total, B, W, H,
+                              lambda f, c, n: pillar_ops.pillar_scatter(f, c, B, W, H, num_voxels_dev=n, channels_last=True))
+    return g, h, x.to(dev).contiguous(memory_format=torch.channels_last), pm
+
+
+def _wide_heads(dev, cin, seed):
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    heads = [torch.nn.Conv2d(cin, 18, 1), torch.nn.Conv2d(cin, 14, 1)]
+    with torch.no_grad():
+        for hd in heads:
+            hd.weight.copy_(torch.randn(hd.weight.shape, generator=g) / cin ** 0.5)
+            hd.bias.copy_(torch.randn(hd.bias.shape, generator=g) * 0.1)
+    return [hd.to(dev).to(memory_format=torch.channels_last) for hd in heads]
+
+
+def _heads_fp64(feat, heads):
+    """fp64 1x1 convolutions of a (B, C, H, W) map -> (B, H, W, sum C_head) in the order merged() writes them"""
+    wt = torch.cat([hd.weight.detach().double().cpu().flatten(1) for hd in heads], 0)
+    b = torch.cat([hd.bias.detach().double().cpu() for hd in heads], 0)
+    return torch.einsum("bchw,nc->bhwn", torch.as_tensor(feat).double(), wt) + b
+
+
+class _Calls:
+    """counts calls of module-level functions (monkeypatched attributes) -> which routes the folded backbone really took"""
+
+    def __init__(self, monkeypatch, *targets):
+        self.n = {}
+        for mod, name in targets:
+            fn = getattr(mod, name)
+            self.n[name] = 0
+
+            def wrapped(*a, _fn=fn, _name=name, **k):
+                self.n[_name] += 1
+                return _fn(*a, **k)
+            monkeypatch.setattr(mod, name, wrapped)
+
+    def take(self):
+        out, self.n = self.n, dict.fromkeys(self.n, 0)
+        return out
+
+
+def _check_folded_entries(bev, canvas, pm, want, want_head, tag, split):
+    """features() from the canvas and from the sparse first layer, merged() from the canvas and from the pillars (as the two-stream
+    split when `split`), against the fp64 feature map / head output: <= 1e-4 of scale.  -> the largest error of each (printed by -s)"""
+    tol = 1e-4 * max(1.0, float(np.abs(want).max()))
+    tol_h = 1e-4 * max(1.0, float(want_head.abs().max()))
+    errs = {}
+    with torch.no_grad():
+        for name, run in (("features(canvas)", lambda: bev.features(canvas)),
+                          ("features(sparse first)", lambda: bev.features(bev.first_layer_from_pillars(pm), first_done=True))):
+            got = run()
+            assert tuple(got.shape) == want.shape, (tag, name)
+            errs[name] = float(np.abs(got.cpu().numpy() - want).max())
+        for name, src in (("merged(canvas)", canvas), ("merged(pillars)", pm)):
+            bev._streams = None
+            got = bev.merged(src)
+            assert tuple(got.shape) == tuple(want_head.shape), (tag, name)
+            assert (bev._streams is not None) == split, (tag, name, "two-stream split taken / not taken")
+            errs[name] = float((got.double().cpu() - want_head).abs().max())
+    print(f"[bev_wide {tag}] " + " ".join(f"{k} {v:.1e}" for k, v in errs.items()) + f" (feature tol {tol:.1e}, head tol {tol_h:.1e})")
+    for k, v in errs.items():
+        assert v <= (tol_h if k.startswith("merged") else tol), (tag, k, v)
+    return errs
+
+
+def test_folded_bev_backbone_production_routes_vs_reference_golden(dev, golden_dir, monkeypatch):
+    """tests/golden/bev_wide.npz: the reference's own BaseBEVBackbone in float64 on a configuration wide enough for the production
+    routes (64 / 64 filters, 128 / 128 upsample filters).  FoldedBEVBackbone must take them — F(4x4, 3x3) Winograd for both
+    stride-1 layers (block 1 runs on a 6 x 5 map: partial tiles at the edges), the fused deblock GEMM (csrc/deconv_gemm.hip) for the
+    stride-2 deblock, the strided-epilogue hipBLASLt GEMM for the stride-1 deblock, the sparse first layer from the pillars — and
+    reproduce the fixture through features() and merged(), from the canvas and from the pillars, whole-batch and as the two-stream
+    split; then again with the byte limits lowered so that every Winograd layer takes F(2x2) and the deblock the two-step GEMM
+    (the >= 2 GiB fallbacks), split included (the F(2x2) filters are packed before either stream runs)."""
+    from lidardetection_amd import bev_backbone as bb, wino
+    from lidardetection_amd.bev_backbone import FoldedBEVBackbone
+    g, h, canvas, pm = _bev_wide_inputs(golden_dir, dev)
+    heads = _wide_heads(dev, 256, 31)
+    want = g["bev_output"]
+    want_head = _heads_fp64(want, heads)
+    bev = FoldedBEVBackbone(h.blocks, h.deblocks, heads)
+    # the routes: stride-1 3x3 layers on F(4x4), deblock 1 fused, deblock 0 the stride-1 GEMM, first layer from the pillars
+    for si in (0, 1):
+        convs = bev.stages[si][0]
+        assert len(convs) == 2 and convs[0][2] == (2, 2) and convs[0][4] is None
+        assert convs[1][4] is not None and convs[1][4][0] == "f43" and len(convs[1][4]) == 4, si
+    assert bev.stages[1][1][0] == "deconv_mfma" and bev.stages[1][1][3] == 2
+    assert bev.stages[0][1][0] == "gemm" and bev.stages[0][1][3] == 1
+    assert bev.sparse_first_ok()
+    calls = _Calls(monkeypatch, (wino, "conv3x3_f43"), (wino, "conv3x3"), (bb, "deconv_gemm_into_"), (bb, "rows_gemm"),
+                   (bb, "gemm_bias_act_into_"))
+    monkeypatch.setattr(bb, "_SPLIT", [2])
+    for fallback in (False, True):
+        if fallback:     # maps "too large" for the F(4x4) kernel and the fused deblock: the >= 2 GiB routes on a small map
+            monkeypatch.setattr(wino, "_F43_MAX_BYTES", [1])
+            monkeypatch.setattr(bb, "_DECONV_MAX_BYTES", [1])
+        for split_min in (8, 1):                                   # B = 2: whole batch, then two part-batches on two streams
+            monkeypatch.setattr(bb, "_SPLIT_MIN", [split_min])
+            tag = ("fallback" if fallback else "production") + (" split" if split_min == 1 else "")
+            _check_folded_entries(bev, canvas, pm, want, want_head, tag, split_min == 1)
+            n = calls.take()
+            # 4 entries, the split ones run two part-batches: 2 Winograd layers and one fused / two-step deblock per part-batch
+            parts = 4 if split_min == 8 else 6
+            if fallback:
+                assert n["conv3x3_f43"] == 0 and n["conv3x3"] == 2 * parts and n["deconv_gemm_into_"] == 0, (tag, n)
+                assert n["rows_gemm"] >= parts, (tag, n)
+            else:
+                assert n["conv3x3_f43"] == 2 * parts and n["conv3x3"] == 0 and n["deconv_gemm_into_"] == parts, (tag, n)
+            assert n["gemm_bias_act_into_"] == parts and bb._LT_GEMM[0], (tag, n)      # the strided-epilogue GEMM ran (and was available)
+
+
+def _randomize_bn(mods, seed):
+    g = torch.Generator().manual_seed(seed)
+    with torch.no_grad():
+        for mod in mods.modules():
+            if isinstance(mod, torch.nn.BatchNorm2d):
+                mod.running_mean.copy_(torch.empty(mod.num_features).uniform_(-0.3, 0.3, generator=g))
+                mod.running_var.copy_(torch.empty(mod.num_features).uniform_(0.6, 1.4, generator=g))
+                mod.weight.copy_(torch.empty(mod.num_features).uniform_(0.5, 1.5, generator=g))
+                mod.bias.copy_(torch.empty(mod.num_features).uniform_(-0.3, 0.3, generator=g))
+
+
+@pytest.mark.parametrize("case", ["asymmetric_zero_pad", "dilation", "groups"])
+def test_folded_bev_backbone_conv_settings_vs_fp64_stock(dev, golden_dir, case):
+    """Conv settings the reference configs do not use but nn.Conv2d / nn.ZeroPad2d allow: the folded backbone computes them (dense
+    path: F.pad + conv2d with dilation and groups) and keeps them off the routes that cannot (Winograd, sparse first layer).
+    features() from the canvas and merged() from a PillarMap against the fp64 stock modules, 1e-4 of scale."""
+    import copy
+    import torch.nn as nn
+    from lidardetection_amd.bev_backbone import FoldedBEVBackbone
+    _, _, canvas, pm = _bev_wide_inputs(golden_dir, dev)
+    torch.manual_seed(41)
+    zp, pad, dil, groups = {"asymmetric_zero_pad": ((0, 1, 0, 1), 1, 1, 1), "dilation": (1, 2, 2, 1), "groups": (1, 1, 1, 2)}[case]
+    blocks = nn.ModuleList([nn.Sequential(
+        nn.ZeroPad2d(zp), nn.Conv2d(64, 64, 3, stride=2, padding=0, bias=False), nn.BatchNorm2d(64, eps=1e-3), nn.ReLU(),
+        nn.Conv2d(64, 64, 3, padding=pad, dilation=dil, groups=groups, bias=False), nn.BatchNorm2d(64, eps=1e-3), nn.ReLU())])
+    deblocks = nn.ModuleList([nn.Sequential(nn.ConvTranspose2d(64, 128, 2, stride=2, bias=False), nn.BatchNorm2d(128, eps=1e-3),
+                                            nn.ReLU())])
+    _randomize_bn(blocks, 42)
+    _randomize_bn(deblocks, 43)
+    blocks, deblocks = blocks.eval(), deblocks.eval()
+    heads = _wide_heads("cpu", 128, 44)
+    with torch.no_grad():                                         # fp64 stock
+        xs = canvas.double().cpu()
+        for mod in (copy.deepcopy(blocks).double(), copy.deepcopy(deblocks).double()):
+            xs = mod[0](xs)
+        want = xs.numpy()
+        want_head = _heads_fp64(xs, heads)
+    blocks, deblocks = blocks.to(dev).to(memory_format=torch.channels_last), deblocks.to(dev).to(memory_format=torch.channels_last)
+    heads = [hd.to(dev) for hd in heads]
+    bev = FoldedBEVBackbone(blocks, deblocks, heads)
+    convs = bev.stages[0][0]
+    assert (convs[0].zero_pad, convs[0][3], convs[1][3], convs[1].dilation, convs[1].groups) == \
+        {"asymmetric_zero_pad": ((0, 1, 0, 1), (0, 0), (1, 1), (1, 1), 1), "dilation": (None, (1, 1), (2, 2), (2, 2), 1),
+         "groups": (None, (1, 1), (1, 1), (1, 1), 2)}[case]                  # the settings the stage keeps
+    assert convs[1][4] is None or case == "asymmetric_zero_pad"             # no Winograd for dilation / groups
+    assert bev.sparse_first_ok() == (case != "asymmetric_zero_pad")          # the neighbour table knows symmetric padding only
+    tol, tol_h = 1e-4 * max(1.0, float(np.abs(want).max())), 1e-4 * max(1.0, float(want_head.abs().max()))
+    with torch.no_grad():
+        got = bev.features(canvas)
+        assert tuple(got.shape) == want.shape, (case, tuple(got.shape), want.shape)
+        err = float(np.abs(got.cpu().numpy() - want).max())
+        got_h = bev.merged(pm)
+        err_h = float((got_h.double().cpu() - want_head).abs().max())
+    print(f"[conv settings {case}] features {err:.1e} (tol {tol:.1e}) merged(pillars) {err_h:.1e} (tol {tol_h:.1e})")
+    assert err <= tol and err_h <= tol_h, (case, err, err_h)
+
+
 def test_resident_canvas_equals_fresh_scatter_over_successive_frames(dev):
     """ResidentCanvas.update (clear last call's cells, write the new pillars) must leave exactly the canvas a fresh
     PointPillarScatter produces, call after call, including shrinking / growing pillar sets and an invalid row."""

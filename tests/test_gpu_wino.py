@@ -254,3 +254,40 @@ def test_wino_f43_random_small_shapes(dev):
         scale = max(1.0, float(want.abs().max()))
         assert float((got - want).abs().max()) <= 1e-4 * scale, (case, B, H, W, cin, cout)
         assert bool((out[:, :off] == -5.0).all()) and bool((out[:, off + cout:] == -5.0).all()), case
+
+
+def test_wino_auto_takes_f23_when_the_output_it_allocates_is_too_large(dev, monkeypatch):
+    """conv3x3_auto with out=None must size the output it allocates itself: with the F(4x4) byte limit lowered between the input
+    (32 channels) and the output (128 channels) it takes F(2x2) with the F(2x2) filters pack_auto packed up front, within 1e-4 of
+    fp64.  (Before wino.f43_fits it checked only a caller-supplied `out`, took F(4x4) and lidar_wino43_conv3x3_nhwc refused the
+    call: SECOND-MultiHead's 64 -> 2304 branch layer at bs >= 15.)"""
+    g = torch.Generator(device="cpu").manual_seed(77)
+    B, cin, cout, H, W = 2, 32, 128, 13, 18
+    x = torch.randn(B, cin, H, W, generator=g)
+    w = torch.randn(cout, cin, 3, 3, generator=g) / np.sqrt(9 * cin)
+    bias = torch.randn(cout, generator=g)
+    packed = wino.pack_auto(w.to(dev))
+    assert packed[0] == "f43" and len(packed) == 4 and torch.equal(packed[3], wino.pack_weights(w.to(dev)))
+    calls = {"f43": 0, "f23": 0}
+    f43, f23 = wino.conv3x3_f43, wino.conv3x3
+
+    def count(name, fn):
+        def wrapped(*a, **k):
+            calls[name] += 1
+            return fn(*a, **k)
+        return wrapped
+    monkeypatch.setattr(wino, "conv3x3_f43", count("f43", f43))
+    monkeypatch.setattr(wino, "conv3x3", count("f23", f23))
+    xd = x.to(dev).contiguous(memory_format=torch.channels_last)
+    want = _ref(x, w, bias, True)
+    scale = max(1.0, float(want.abs().max()))
+    limit = (B * cin * H * W * 4 + B * cout * H * W * 4) // 2
+    for lim, route in ((2 ** 31 - 1, "f43"), (limit, "f23")):
+        monkeypatch.setattr(wino, "_F43_MAX_BYTES", [lim])
+        before = dict(calls)
+        got = wino.conv3x3_auto(xd, packed, cout, bias.to(dev), True)
+        assert calls[route] == before[route] + 1 and sum(calls.values()) == sum(before.values()) + 1, (route, calls)
+        assert got.shape == want.shape and got.is_contiguous(memory_format=torch.channels_last)
+        err = float((got.double().cpu() - want).abs().max())
+        print(f"conv3x3_auto {route}: max err {err:.2e} (scale {scale:.1f})")
+        assert err <= 1e-4 * scale, (route, err, scale)

@@ -202,3 +202,44 @@ def test_spconv_nk_fixture_is_what_the_sparse_oracle_produces():
         if a["kind"] == "subm":
             assert a["n_k"] == a["n_k"][::-1] and a["n_k"][13] == a["rows_out"]
     assert abs(got["gflop_useful_total"] - want["gflop_useful_total"]) < 1e-9
+
+
+def _bev_wide(golden_dir):
+    """tests/golden/bev_wide.npz -> (fixture, nn.Module holding .blocks / .deblocks of this repo's module tree with the reference's
+    state_dict loaded strictly; float32, CPU).  Conv / deconv weights are stored as int8 codes times `weight_scale`."""
+    import torch.nn as nn
+    from lidardetection_amd.pointpillar import make_bev_backbone
+    g = np.load(os.path.join(golden_dir, "bev_wide.npz"))
+
+    class Holder(nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.blocks, self.deblocks = make_bev_backbone(cin=64, layer_nums=(1, 1), strides=(2, 2), filters=(64, 64),
+                                                           up_strides=(1, 2), up_filters=(128, 128))
+    h = Holder()
+    scale = float(g["weight_scale"])
+    sd = {k[4:]: torch.from_numpy(g[k].astype(np.float32) * np.float32(scale) if g[k].dtype == np.int8 else g[k])
+          for k in g.files if k.startswith("bev.")}
+    h.load_state_dict(sd, strict=True)
+    return g, h.eval()
+
+
+def test_bev_wide_fixture_replays_in_float64_on_this_module_tree(golden_dir):
+    """tests/golden/bev_wide.npz is the reference's own BaseBEVBackbone in float64 (tests/golden/make_golden.py).  Its state_dict
+    loads strictly into pointpillar.make_bev_backbone's tree, and that tree, run in float64 on the CPU, gives the stored output:
+    the fixture the GPU routes are held to is this repo's module, not only the reference's."""
+    g, h = _bev_wide(golden_dir)
+    assert g["bev.blocks.0.1.weight"].dtype == np.int8 and g["bev.deblocks.1.0.weight"].dtype == np.int8
+    x = torch.from_numpy(g["bev_input"]).double()
+    occupied = x.abs().sum(1) > 0
+    assert 0.08 < float(occupied.double().mean()) < 0.16          # pillar-like: most cells exactly 0
+    h = h.double()
+    with torch.no_grad():
+        ups, y = [], x
+        for blk, de in zip(h.blocks, h.deblocks):
+            y = blk(y)
+            ups.append(de(y))
+        got = torch.cat(ups, 1)
+    want = g["bev_output"]
+    assert tuple(got.shape) == want.shape == (2, 256, 12, 10)
+    np.testing.assert_allclose(got.numpy(), want.astype(np.float64), rtol=0, atol=1e-6)

@@ -34,10 +34,10 @@ try:
     from lidardetection_amd.bev_backbone import bias_act_
     bias_act_(y0, bev.stages[0][0][0][1])
     ref = torch.relu(F.conv2d(y0, w, bb, stride, pad))
-    got = torch.miopen_convolution_relu(y0, w, bb, list(stride), [pad, pad], [1, 1], 1)
+    got = torch.miopen_convolution_relu(y0, w, bb, list(stride), list(pad), [1, 1], 1)
     print("miopen_convolution_relu diff %.2e" % (got - ref).abs().max().item())
     print("  conv + HIP epilogue  %.3f ms" % run(lambda: bias_act_(F.conv2d(y0, w, None, stride, pad), bb), 20))
-    print("  miopen conv_relu     %.3f ms" % run(lambda: torch.miopen_convolution_relu(y0, w, bb, list(stride), [pad, pad], [1, 1], 1), 20))
+    print("  miopen conv_relu     %.3f ms" % run(lambda: torch.miopen_convolution_relu(y0, w, bb, list(stride), list(pad), [1, 1], 1), 20))
     print("  conv only            %.3f ms" % run(lambda: F.conv2d(y0, w, None, stride, pad), 20))
 except Exception as e:  # noqa: BLE001
     print("miopen_convolution_relu probe failed:", repr(e)[:300])
