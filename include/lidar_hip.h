@@ -500,6 +500,39 @@ int lidar_anchor_assign(const float *const *anchors, const long long *counts, co
                         int max_gt, int gt_cols, int code_size, int sincos, int norm_by_num_examples, int *labels, float *targets,
                         float *weights, void *ws, size_t ws_bytes, void *stream);
 
+/* ------------------------------------------------------------------ anchor-head RPN loss (training), forward + backward
+ * AnchorHeadTemplate.get_loss / AnchorHeadMulti.get_loss for a whole batch and every head, no host synchronisation, no float atomics
+ * (csrc/anchor_loss.hip).  Reference: pcdet/models/dense_heads/anchor_head_template.py:102-224 (get_cls_layer_loss,
+ * add_sin_difference, get_direction_target, get_box_reg_layer_loss, get_loss), anchor_head_multi.py:245-370, pcdet/utils/loss_utils.py
+ * (SigmoidFocalClassificationLoss :9-72, WeightedSmoothL1Loss :75-136, WeightedL1Loss :139-178, WeightedCrossEntropyLoss :181-205).
+ *   cls, box, dir, counts, cols, col_off   HOST arrays of num_heads (<= 16) entries, passed by value in the kernel arguments: DEVICE
+ *       pointers to head k's contiguous (batch, counts[k], cols[k]) class logits, (batch, counts[k], code_size) box encodings and
+ *       (batch, counts[k], num_dir_bins) direction logits (dir NULL without a direction classifier); head k owns anchors
+ *       sum(counts[<k]) .. + counts[k] of the frame, and compares its cols[k] (<= 16) logits with one-hot columns col_off[k] ..
+ *       (SEPARATE_MULTIHEAD; otherwise 0 and cols == num_class).  sum(counts) == n_total.
+ *   labels (batch, n_total) i32, targets (batch, n_total, code_size) f32 (the assigner's box_cls_labels / box_reg_targets),
+ *   anchors (n_total, anchor_dim) f32, shared by every frame (only column 6 is read, for the direction target); code_size 7..16,
+ *   num_dir_bins 1..8
+ *   code_weights HOST (code_size); weights HOST (7): cls_weight, loc_weight, dir_weight, pos_cls_weight, neg_cls_weight,
+ *       DIR_OFFSET, 2 pi / NUM_DIR_BINS
+ *   flags: 1 add_sin_difference on column 6, 2 WeightedL1Loss (else WeightedSmoothL1Loss, beta 1/9), 4 direction classifier
+ *   forward -> losses (3) DEVICE f32: cls, loc, dir terms (each weighted and divided by batch, as the reference returns them); the
+ *       per-frame positive counts stay in the workspace for backward, which must get the same workspace and inputs.
+ *   backward: grad_losses (3) DEVICE f32 -> d_cls / d_box / d_dir HOST arrays of num_heads DEVICE pointers in the layouts of the
+ *       inputs (an array or an entry NULL: not written). */
+size_t lidar_anchor_loss_workspace_bytes(int batch, const long long *counts, int num_heads);
+int lidar_anchor_loss_forward(const float *const *cls, const float *const *box, const float *const *dir, const long long *counts,
+                              const int *cols, const int *col_off, int num_heads, const int *labels, const float *targets,
+                              const float *anchors, int anchor_dim, int batch, long long n_total, int num_class, int code_size,
+                              int num_dir_bins, const float *code_weights, const float *weights, int flags, float *losses, void *ws,
+                              size_t ws_bytes, void *stream);
+int lidar_anchor_loss_backward(const float *const *cls, const float *const *box, const float *const *dir, const long long *counts,
+                               const int *cols, const int *col_off, int num_heads, const int *labels, const float *targets,
+                               const float *anchors, int anchor_dim, int batch, long long n_total, int num_class, int code_size,
+                               int num_dir_bins, const float *code_weights, const float *weights, int flags,
+                               const float *grad_losses, float *const *d_cls, float *const *d_box, float *const *d_dir, void *ws,
+                               size_t ws_bytes, void *stream);
+
 /* HeightCompression in one pass (pcdet/models/backbones_2d/map_to_bev/height_compression.py:21-24): the (N, C*D, H, W) BEV
  * map of a sparse tensor written directly channels-last: out[b][h][w][c*D + d]; D <= 4, channels % 4 == 0; same workspace
  * as lidar_sparse_to_dense. */

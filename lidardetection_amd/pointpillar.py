@@ -21,7 +21,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import anchor_post, pillar_ops, synth
+from . import anchor_loss, anchor_post, pillar_ops, synth
 from .bev_backbone import FoldedBEVBackbone, collect_params, params_key
 from .ext import iou3d_nms_cuda
 from .voxelizer import BatchVoxelizer, grid_size_of
@@ -67,6 +67,19 @@ def generate_anchors(pc_range, feat_hw, device):
         a[..., 2] += a[..., 5] / 2
         out.append(a)
     return torch.cat(out, dim=-3).view(-1, 7).to(device)
+
+
+# pointpillar.yaml DENSE_HEAD: what the training loss reads (anchors, target assigner, loss) — PointPillarKITTI.rpn_loss
+KITTI_THRESHOLDS = [(0.6, 0.45), (0.5, 0.35), (0.5, 0.35)]
+KITTI_CLASS_NAMES = ["Car", "Pedestrian", "Cyclist"]
+DENSE_HEAD_CFG = dict(
+    NAME="AnchorHeadSingle", USE_DIRECTION_CLASSIFIER=True, DIR_OFFSET=0.78539, DIR_LIMIT_OFFSET=0.0, NUM_DIR_BINS=2,
+    ANCHOR_GENERATOR_CONFIG=[dict(class_name=n, anchor_sizes=[s], anchor_rotations=r, anchor_bottom_heights=[h], align_center=False,
+                                  feature_map_stride=2, matched_threshold=t[0], unmatched_threshold=t[1])
+                             for n, (s, r, h), t in zip(KITTI_CLASS_NAMES, KITTI_ANCHORS, KITTI_THRESHOLDS)],
+    TARGET_ASSIGNER_CONFIG=dict(NAME="AxisAlignedTargetAssigner", POS_FRACTION=-1.0, SAMPLE_SIZE=512, NORM_BY_NUM_EXAMPLES=False,
+                                MATCH_HEIGHT=False, BOX_CODER="ResidualCoder"),
+    LOSS_CONFIG=dict(LOSS_WEIGHTS={"cls_weight": 1.0, "loc_weight": 2.0, "dir_weight": 0.2, "code_weights": [1.0] * 7}))
 
 
 def limit_period(val, offset=0.5, period=np.pi):
@@ -178,6 +191,24 @@ class PointPillarKITTI(nn.Module):
         box = self.conv_box(x).permute(0, 2, 3, 1).reshape(self.B, -1, 7)
         dirs = self.conv_dir_cls(x).permute(0, 2, 3, 1).reshape(self.B, -1, self.num_dir_bins)
         return cls, box, dirs
+
+    def rpn_loss(self, head_out, gt_boxes):
+        """the training loss of this head: (cls_loss, loc_loss, dir_loss) of AnchorHeadTemplate.get_loss (pointpillar.yaml weights) for
+        head_out = backbone_head_stock()'s (cls, box, dirs) and gt_boxes (B, M, 8) [box | class id]: the GPU target assigner, then the
+        fused loss, differentiable with respect to the head outputs; no host synchronisation."""
+        head = self._loss_head()
+        t = head.assign_targets(gt_boxes)
+        return anchor_loss.anchor_head_loss(*head_out, t['box_cls_labels'], t['box_reg_targets'], head.loss_anchors(), head.loss_spec)
+
+    def _loss_head(self):
+        if self.__dict__.get("_rpn_loss_head") is None:
+            from .pcdet.models.dense_heads.anchor_head_template import AnchorHeadTemplate
+            from .pcdet.utils.cfg import AttrDict
+            cfg = AttrDict({k: AttrDict(v) if isinstance(v, dict) else v for k, v in DENSE_HEAD_CFG.items()})
+            with torch.cuda.device(self.anchors.device):
+                self.__dict__["_rpn_loss_head"] = AnchorHeadTemplate(cfg, self.num_class, KITTI_CLASS_NAMES,
+                                                                     np.array([self.nx, self.ny, 1]), self.pc_range, False)
+        return self.__dict__["_rpn_loss_head"]
 
     def decode(self, enc, anchors, dir_logits):
         xa, ya, za, dxa, dya, dza, ra = torch.split(anchors, 1, dim=-1)

@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import anchor_post, pillar_ops, synth, wino
+from . import anchor_loss, anchor_post, pillar_ops, synth, wino
 from .bev_backbone import _WINO, FoldedBEVBackbone, bias_act_, collect_params, params_key
 from .bev_backbone import _fold as fold_bn
 from .ext import iou3d_nms_cuda
@@ -40,6 +40,23 @@ NUS_HEADS = [["car"], ["truck", "construction_vehicle"], ["bus", "trailer"], ["b
              ["pedestrian", "traffic_cone"]]                                   # RPN_HEAD_CFGS :150-169
 NUS_REG_LIST = [("reg", 2), ("height", 1), ("size", 3), ("angle", 2), ("velo", 2)]   # SEPARATE_REG_CONFIG :171-174
 NUS_ROTATIONS = [0.0, 1.57]
+
+
+NUS_THRESHOLDS = [(0.6, 0.45), (0.55, 0.4), (0.5, 0.35), (0.55, 0.4), (0.5, 0.35), (0.55, 0.4), (0.5, 0.3), (0.5, 0.35),
+                  (0.6, 0.4), (0.6, 0.4)]                                      # cbgs_second_multihead.yaml :40-137
+# cbgs_second_multihead.yaml DENSE_HEAD: what the training loss reads (anchors, target assigner, loss) — rpn_loss
+DENSE_HEAD_CFG = dict(
+    NAME="AnchorHeadMulti", DIR_OFFSET=0.78539, DIR_LIMIT_OFFSET=0.0, NUM_DIR_BINS=2, USE_MULTIHEAD=True, SEPARATE_MULTIHEAD=True,
+    ANCHOR_GENERATOR_CONFIG=[dict(class_name=n, anchor_sizes=[s], anchor_rotations=NUS_ROTATIONS, anchor_bottom_heights=[h],
+                                  align_center=False, feature_map_stride=8, matched_threshold=t[0], unmatched_threshold=t[1])
+                             for (n, s, h), t in zip(NUS_CLASSES, NUS_THRESHOLDS)],
+    RPN_HEAD_CFGS=[dict(HEAD_CLS_NAME=h) for h in NUS_HEADS],
+    TARGET_ASSIGNER_CONFIG=dict(NAME="AxisAlignedTargetAssigner", POS_FRACTION=-1.0, SAMPLE_SIZE=512, NORM_BY_NUM_EXAMPLES=False,
+                                MATCH_HEIGHT=False, BOX_CODER="ResidualCoder",
+                                BOX_CODER_CONFIG={"code_size": 9, "encode_angle_by_sincos": True}),
+    LOSS_CONFIG=dict(REG_LOSS_TYPE="WeightedL1Loss",
+                     LOSS_WEIGHTS={"pos_cls_weight": 1.0, "neg_cls_weight": 2.0, "cls_weight": 1.0, "loc_weight": 0.25,
+                                   "dir_weight": 0.2, "code_weights": [1.0] * 8 + [0.2, 0.2]}))
 
 
 def class_anchors(pc_range, feat_hw, size, rotations, bottom):
@@ -159,6 +176,25 @@ class SECONDMultiHeadNuScenes(nn.Module):
         """the module sequence as the reference runs it: shared conv, then 6 heads x 6 branches of conv/BN/ReLU/conv (144 launches)"""
         x = self.shared_conv(spatial_2d)
         return [h(x) for h in self.rpn_heads]                   # [(cls (B, n_h, c_h), box (B, n_h, 10))] per head
+
+    def rpn_loss(self, head_out, gt_boxes):
+        """the training loss of these heads: (cls_loss, loc_loss, dir_loss) of AnchorHeadMulti.get_loss (cbgs_second_multihead.yaml:
+        SEPARATE_MULTIHEAD, WeightedL1Loss, no direction classifier, so dir_loss is 0) for head_out = heads_reference_layout()'s
+        [(cls, box)] per head and gt_boxes (B, M, 10) [box, vx, vy | class id]: the GPU target assigner, then the fused loss over the
+        per-head tensors, differentiable with respect to them; no host synchronisation."""
+        head = self._loss_head()
+        t = head.assign_targets(gt_boxes)
+        return anchor_loss.anchor_head_loss([c for c, _ in head_out], [b for _, b in head_out], None, t['box_cls_labels'],
+                                            t['box_reg_targets'], head.loss_anchors(), head.loss_spec)
+
+    def _loss_head(self):
+        if self.__dict__.get("_rpn_loss_head") is None:
+            from .pcdet.models.dense_heads.anchor_head_multi import AnchorHeadMulti
+            cfg = AttrDict({k: AttrDict(v) if isinstance(v, dict) else v for k, v in DENSE_HEAD_CFG.items()})
+            with torch.cuda.device(self.head_anchors[0].device):
+                self.__dict__["_rpn_loss_head"] = AnchorHeadMulti(cfg, 64, len(NUS_CLASSES), [c[0] for c in NUS_CLASSES],
+                                                                  np.array(self.grid), self.pc_range, False)
+        return self.__dict__["_rpn_loss_head"]
 
     def _folded_heads(self):
         """every branch's first 3x3 convolution reads the same 64-channel map: their 36 weight sets stacked give ONE convolution
