@@ -120,3 +120,75 @@ def inverse_conv(feats_small, idx_small, shape_small, idx_orig, shape_orig, weig
 def batchnorm_eval(x, weight, bias, mean, var, eps):
     return (x - np.asarray(mean, np.float64)) / np.sqrt(np.asarray(var, np.float64) + eps) * np.asarray(weight, np.float64) \
         + np.asarray(bias, np.float64)
+
+
+def pairs(idx, shape, ksize, stride, padding, subm):
+    """The rulebook as (offset, input row, output row) triples, from the sorted-key search above (never from a GPU table).
+    idx (N, 4) [b, z, y, x], any order, unique.  -> (out_idx (M, 4) int64, out_shape, k (P,), in_row (P,), out_row (P,)),
+    triples grouped by ascending k.  SubM: outputs are the input rows themselves (stride / padding ignored, neighbour =
+    site + k - centre); regular: outputs as sparse_conv (ascending (b, z, y, x)), o = (in + p - k) / s."""
+    idx = np.asarray(idx, np.int64).reshape(-1, 4)
+    ks, ins, outs = [], [], []
+    if subm:
+        keys = _keys(idx, shape)
+        order = np.argsort(keys, kind="stable")
+        skeys = keys[order]
+        centre = np.asarray([k // 2 for k in ksize], np.int64)
+        lim = np.asarray(shape, np.int64)
+        for k, off in enumerate(_offsets(ksize)):
+            q = idx.copy()
+            q[:, 1:] += np.asarray(off, np.int64) - centre
+            ok = np.all((q[:, 1:] >= 0) & (q[:, 1:] < lim), axis=1)
+            qk = _keys(q[ok], shape)
+            pos = np.searchsorted(skeys, qk)
+            pos[pos >= skeys.size] = 0
+            hit = skeys[pos] == qk if skeys.size else np.zeros(qk.shape, bool)
+            outs.append(np.nonzero(ok)[0][hit])
+            ins.append(order[pos[hit]])
+            ks.append(np.full(outs[-1].size, k, np.int64))
+        out_idx, osz = idx, [int(v) for v in shape]
+    else:
+        osz = out_shape(shape, ksize, stride, padding)
+        s = np.asarray(stride, np.int64)
+        per_k = []
+        for off in _offsets(ksize):
+            t = idx[:, 1:] + np.asarray(padding, np.int64) - np.asarray(off, np.int64)
+            ok = np.all((t >= 0) & (t % s == 0), axis=1)
+            o = t // s
+            ok &= np.all(o < np.asarray(osz, np.int64), axis=1)
+            rows_in = np.nonzero(ok)[0]
+            oc = np.concatenate([idx[rows_in, :1], o[rows_in]], axis=1)
+            per_k.append((rows_in, _keys(oc, osz), oc))
+        all_keys = np.concatenate([p[1] for p in per_k])
+        ukeys, first = np.unique(all_keys, return_index=True)
+        out_idx = np.concatenate([p[2] for p in per_k])[first].reshape(-1, 4)
+        for k, (rows_in, okeys, _) in enumerate(per_k):
+            ins.append(rows_in)
+            outs.append(np.searchsorted(ukeys, okeys))
+            ks.append(np.full(rows_in.size, k, np.int64))
+    return out_idx, osz, np.concatenate(ks), np.concatenate(ins).astype(np.int64), np.concatenate(outs).astype(np.int64)
+
+
+def inverse_pairs(idx_small, shape_small, idx_orig, shape_orig, ksize, stride, padding):
+    """SparseInverseConv3d's triples with the semantics of inverse_conv: for every (k, i -> o) of the paired convolution,
+    (k, row of o in idx_small, row of i in idx_orig).  Outputs are idx_orig's rows.  -> (k, in_row, out_row), by ascending k."""
+    idx_orig = np.asarray(idx_orig, np.int64).reshape(-1, 4)
+    skeys = _keys(np.asarray(idx_small, np.int64).reshape(-1, 4), shape_small)
+    order = np.argsort(skeys, kind="stable")
+    skeys = skeys[order]
+    s = np.asarray(stride, np.int64)
+    ks, ins, outs = [], [], []
+    for k, off in enumerate(_offsets(ksize)):
+        t = idx_orig[:, 1:] + np.asarray(padding, np.int64) - np.asarray(off, np.int64)
+        ok = np.all((t >= 0) & (t % s == 0), axis=1)
+        o = t // s
+        ok &= np.all(o < np.asarray(shape_small, np.int64), axis=1)
+        rows_i = np.nonzero(ok)[0]
+        okeys = _keys(np.concatenate([idx_orig[rows_i, :1], o[rows_i]], axis=1), shape_small)
+        pos = np.searchsorted(skeys, okeys)
+        pos[pos >= skeys.size] = 0
+        hit = skeys[pos] == okeys if skeys.size else np.zeros(okeys.shape, bool)
+        outs.append(rows_i[hit])
+        ins.append(order[pos[hit]])
+        ks.append(np.full(outs[-1].size, k, np.int64))
+    return np.concatenate(ks), np.concatenate(ins).astype(np.int64), np.concatenate(outs).astype(np.int64)
