@@ -167,6 +167,28 @@ int lidar_pillar_scatter_backward(const float *grad_canvas, const void *coords, 
                                   const int *num_voxels_dev, int channels, int batch, int nx, int ny, int channels_last,
                                   float *grad_features, void *stream);
 
+/* ------------------------------------------------------------------ BatchNorm2d + ReLU, TRAIN mode (csrc/bn_train.hip)
+ * Replaces the train-mode BatchNorm2d -> ReLU pairs of BaseBEVBackbone and the concat of its deblocks
+ * (pcdet/models/backbones_2d/base_bev_backbone.py:31-69, 103) on channels-last fp32 maps.  A map is `rows` = B * H * W rows of
+ * channels at row stride ld (floats), starting at channel offset off.  One call takes nseg (1..4) input maps as one concatenated
+ * channel space (segment i owns channels [sum seg_C[:i], + seg_C[i]) of gamma, beta, y and every per-channel output); x, x_ld,
+ * x_off, seg_C and dx are HOST arrays of nseg entries (x / dx hold device pointers).  Supported: seg_C % 4 == 0, 4 <= seg_C <= 1024,
+ * ld % 4 == 0, off % 4 == 0, off + C <= ld, 16-byte aligned pointers, rows >= 2 (torch refuses one value per channel).
+ * Forward: batch statistics over the rows (fp64 sums, fixed-order reduction), y = max(z * gamma / sigma + beta - mu gamma / sigma, 0)
+ * into channels [y_off, y_off + sum seg_C) of the (rows, y_ld) output; stats (2 * ctot doubles: mean, 1 / sigma), scale_shift
+ * (2 * ctot floats) for the backward; batch_stats (3 * ctot floats: mean, biased variance, unbiased variance -- the caller applies
+ * the running-statistics update).  Backward: grad_y read at (g_ld, g_off), the ReLU mask recomputed from z; dz written to dx[i] at
+ * x_ld[i] / x_off[i] (the layout of its z), d_gamma / d_beta (ctot).  No float atomics, no host read: bitwise reproducible and
+ * graph-capturable.  ws: lidar_bn_relu_train_workspace_bytes(rows, ctot) (pure host; 0 for rows < 1 or channels < 1). */
+size_t lidar_bn_relu_train_workspace_bytes(long long rows, int channels);
+int lidar_bn_relu_train_forward(int nseg, void *const *x, const int *x_ld, const int *x_off, const int *seg_C, long long rows,
+                                const float *gamma, const float *beta, float eps, float *y, int y_ld, int y_off, double *stats,
+                                float *scale_shift, float *batch_stats, void *ws, size_t ws_bytes, void *stream);
+int lidar_bn_relu_train_backward(int nseg, void *const *x, const int *x_ld, const int *x_off, const int *seg_C, long long rows,
+                                 const float *grad_y, int g_ld, int g_off, const float *gamma, const double *stats,
+                                 const float *scale_shift, void *const *dx, float *d_gamma, float *d_beta, void *ws, size_t ws_bytes,
+                                 void *stream);
+
 /* ------------------------------------------------------------------ iou3d_nms
  * boxes are (N,7) f32 [x, y, z, dx, dy, dz, heading].
  * mode 0 = boxes_overlap_bev_gpu (pcdet/ops/iou3d_nms/src/iou3d_nms.cpp:49-68, kernel.cu:236-249)

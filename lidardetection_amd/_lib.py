@@ -37,6 +37,9 @@ SIGNATURES = {
     "lidar_pfn_train_backward": (i32, [vp, vp, vp, i32, vp, i32, i32, vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp,
                                        vp, vp, sz, vp]),
     "lidar_pillar_scatter_backward": (i32, [vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, vp, vp]),
+    "lidar_bn_relu_train_workspace_bytes": (sz, [C.c_longlong, i32]),
+    "lidar_bn_relu_train_forward": (i32, [i32, vp, vp, vp, vp, C.c_longlong, vp, vp, f32, vp, i32, i32, vp, vp, vp, vp, sz, vp]),
+    "lidar_bn_relu_train_backward": (i32, [i32, vp, vp, vp, vp, C.c_longlong, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
     "lidar_iou_workspace_bytes": (sz, [i32, i32]),
     "lidar_boxes_pairwise_bev": (i32, [vp, i32, vp, i32, i32, vp, vp, sz, vp]),
     "lidar_nms_workspace_bytes": (sz, [i32, i32]),

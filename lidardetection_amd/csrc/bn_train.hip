@@ -1,0 +1,309 @@
+// Train-mode BatchNorm2d + ReLU on channels-last fp32 maps, forward and backward.
+//   reference: pcdet/models/backbones_2d/base_bev_backbone.py:31-69 (Conv2d / ConvTranspose2d -> BatchNorm2d(eps, momentum) -> ReLU),
+//              :103 (torch.cat of the deblock outputs)
+//
+// A map is (rows = B * H * W) x (C channels) with a row stride `ld` and a channel offset `off` (a slice of a wider map).  One call
+// normalises up to BT_MAX_SEG such inputs ("segments") as ONE concatenated channel space: segment s owns channels [c0_s, c0_s + C_s)
+// of the output (and of gamma, beta, the statistics), so the deblock outputs land in their slices of the concatenated map and their
+// gradients are read back from the concatenated gradient without a torch.cat or a split.
+//   forward:  per-channel sum z and sum z^2 in fp64 (one partial per block), a fixed-order reduction, a finalize that writes the
+//             batch mean, the biased variance, 1 / sigma, fp32 scale = gamma / sigma and shift = beta - mu gamma / sigma, and the
+//             running-statistics inputs (mean, unbiased variance); then y = max(z scale + shift, 0).
+//   backward: delta = g [y > 0] with y recomputed from z bit for bit (no mask is stored); sum delta and sum delta z in fp64, reduced
+//             the same way; dbeta = sum delta, dgamma = sum delta zh = (sum delta z - mu sum delta) / sigma,
+//             dz = gamma / sigma (delta - dbeta / N - zh dgamma / N).
+// No float atomics and no host read: every result is bitwise reproducible and every call can be captured in a graph.
+#include "common.h"
+
+#define BT_MAX_SEG 4
+#define BT_MAX_C 1024              // channels of one segment: a 256-thread block covers a row's C / 4 quads at once
+#define BT_MAX_BLOCKS 1024
+
+struct BtSeg {
+    const float *x;                // z (forward and backward input)
+    float *dx;                     // dz (backward output; same row stride and channel offset as x)
+    int C, ld, off, c0;
+};
+struct BtSegs {
+    BtSeg s[BT_MAX_SEG];
+    int n, ctot;
+};
+
+// thread layout of every pass: Q = C / 4 channel quads per row, R = 256 / Q rows side by side; thread (r, q), rows r, r + R nb, ...
+struct BtLane {
+    int Q, R, r, q;
+    bool live;
+};
+__device__ __forceinline__ BtLane bt_lane(int C) {
+    BtLane L;
+    L.Q = C >> 2;
+    L.R = 256 / L.Q;
+    L.r = (int)threadIdx.x / L.Q;
+    L.q = (int)threadIdx.x - L.r * L.Q;
+    L.live = L.r < L.R;
+    return L;
+}
+
+__device__ __forceinline__ float4 bt_ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
+__device__ __forceinline__ void bt_st4(float *p, float4 v) { *reinterpret_cast<float4 *>(p) = v; }
+
+// the per-block sums of thread (r, q) -> part[(which * ctot + channel) * nb + block], summed over r in a fixed order
+__device__ __forceinline__ void bt_block_partials(const double (&a)[8], const BtLane &L, int C, int c0, int ctot, int nb,
+                                                  double *__restrict__ part) {
+    __shared__ double sh[8][256];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) sh[k][threadIdx.x] = a[k];
+    __syncthreads();
+    for (int e = threadIdx.x; e < 2 * C; e += 256) {
+        const int which = e >= C, c = e - which * C, q = c >> 2, k = which * 4 + (c & 3);
+        double t = 0.0;
+        for (int r = 0; r < L.R; ++r) t += sh[k][r * L.Q + q];
+        part[((size_t)which * ctot + c0 + c) * nb + blockIdx.x] = t;
+    }
+}
+
+// forward pass 1: sum z, sum z^2 (fp64) per channel and block.  grid (nb, segments)
+__global__ __launch_bounds__(256) void bt_stats_kernel(BtSegs segs, long long rows, int nb, double *__restrict__ part) {
+    const BtSeg sg = segs.s[blockIdx.y];
+    const BtLane L = bt_lane(sg.C);
+    double a[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (L.live) {
+        const float *base = sg.x + sg.off + 4 * L.q;
+        const long long step = (long long)nb * L.R;
+        long long row = (long long)blockIdx.x * L.R + L.r;
+        for (; row + 3 * step < rows; row += 4 * step) {     // four rows in flight
+            float4 v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) v[u] = bt_ld4(base + (row + u * step) * sg.ld);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                a[0] += v[u].x; a[1] += v[u].y; a[2] += v[u].z; a[3] += v[u].w;
+                a[4] += (double)v[u].x * v[u].x; a[5] += (double)v[u].y * v[u].y;
+                a[6] += (double)v[u].z * v[u].z; a[7] += (double)v[u].w * v[u].w;
+            }
+        }
+        for (; row < rows; row += step) {
+            const float4 v = bt_ld4(base + row * sg.ld);
+            a[0] += v.x; a[1] += v.y; a[2] += v.z; a[3] += v.w;
+            a[4] += (double)v.x * v.x; a[5] += (double)v.y * v.y; a[6] += (double)v.z * v.z; a[7] += (double)v.w * v.w;
+        }
+    }
+    bt_block_partials(a, L, sg.C, sg.c0, segs.ctot, nb, part);
+}
+
+// rows of `part` ([entries][nparts]) -> tot[entry]; one block per entry, fixed summation order
+__global__ __launch_bounds__(256) void bt_reduce_kernel(const double *__restrict__ part, int nparts, double *__restrict__ tot) {
+    __shared__ double s[256];
+    const double *row = part + (size_t)blockIdx.x * nparts;
+    double a = 0.0;
+    for (int b = threadIdx.x; b < nparts; b += 256) a += row[b];
+    s[threadIdx.x] = a;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) s[threadIdx.x] += s[threadIdx.x + h];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) tot[blockIdx.x] = s[0];
+}
+
+// forward pass 2 (thread = channel): mean, biased variance, 1 / sigma in fp64; fp32 scale / shift; the running-statistics inputs
+__global__ __launch_bounds__(256) void bt_finalize_kernel(const double *__restrict__ tot, int ctot, long long rows,
+                                                          const float *__restrict__ gamma, const float *__restrict__ beta, float eps,
+                                                          double *__restrict__ stats, float *__restrict__ scale_shift,
+                                                          float *__restrict__ batch_stats) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= ctot) return;
+    const double N = (double)rows;
+    const double mu = tot[c] / N;
+    const double var = fmax(tot[ctot + c] / N - mu * mu, 0.0);
+    const double inv = 1.0 / sqrt(var + (double)eps);
+    const double a = (double)gamma[c] * inv;
+    stats[c] = mu;
+    stats[ctot + c] = inv;
+    scale_shift[c] = (float)a;
+    scale_shift[ctot + c] = (float)((double)beta[c] - mu * a);
+    batch_stats[c] = (float)mu;
+    batch_stats[ctot + c] = (float)var;
+    batch_stats[2 * ctot + c] = (float)(var * N / (N - 1.0));
+}
+
+// forward pass 3: y = max(z scale + shift, 0) into channels [y_off + c0, + C) of the (rows, y_ld) output.  grid (nb, segments)
+__global__ __launch_bounds__(256) void bt_apply_kernel(BtSegs segs, long long rows, int nb, const float *__restrict__ scale_shift,
+                                                       float *__restrict__ y, int y_ld, int y_off) {
+    const BtSeg sg = segs.s[blockIdx.y];
+    const BtLane L = bt_lane(sg.C);
+    if (!L.live) return;
+    const int c = sg.c0 + 4 * L.q;
+    const float4 sc = bt_ld4(scale_shift + c), sh = bt_ld4(scale_shift + segs.ctot + c);
+    const float *src = sg.x + sg.off + 4 * L.q;
+    float *dst = y + y_off + c;
+    const long long step = (long long)nb * L.R;
+    for (long long row = (long long)blockIdx.x * L.R + L.r; row < rows; row += step) {
+        const float4 v = bt_ld4(src + row * sg.ld);
+        float4 o;
+        o.x = fmaxf(fmaf(v.x, sc.x, sh.x), 0.f); o.y = fmaxf(fmaf(v.y, sc.y, sh.y), 0.f);
+        o.z = fmaxf(fmaf(v.z, sc.z, sh.z), 0.f); o.w = fmaxf(fmaf(v.w, sc.w, sh.w), 0.f);
+        bt_st4(dst + row * (long long)y_ld, o);
+    }
+}
+
+__device__ __forceinline__ float bt_delta(float z, float g, float sc, float sh) {
+    return fmaxf(fmaf(z, sc, sh), 0.f) > 0.f ? g : 0.f;        // the forward's y, bit for bit
+}
+
+// backward pass 1: sum delta, sum delta z (fp64) per channel and block.  grid (nb, segments)
+__global__ __launch_bounds__(256) void bt_bwd_stats_kernel(BtSegs segs, long long rows, int nb, const float *__restrict__ scale_shift,
+                                                           const float *__restrict__ g, int g_ld, int g_off, double *__restrict__ part) {
+    const BtSeg sg = segs.s[blockIdx.y];
+    const BtLane L = bt_lane(sg.C);
+    double a[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (L.live) {
+        const int c = sg.c0 + 4 * L.q;
+        const float4 sc = bt_ld4(scale_shift + c), sh = bt_ld4(scale_shift + segs.ctot + c);
+        const float *zs = sg.x + sg.off + 4 * L.q, *gs = g + g_off + c;
+        const long long step = (long long)nb * L.R;
+        long long row = (long long)blockIdx.x * L.R + L.r;
+        for (; row + step < rows; row += 2 * step) {          // two rows in flight
+            float4 z[2], gv[2];
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                z[u] = bt_ld4(zs + (row + u * step) * sg.ld);
+                gv[u] = bt_ld4(gs + (row + u * step) * (long long)g_ld);
+            }
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const float d0 = bt_delta(z[u].x, gv[u].x, sc.x, sh.x), d1 = bt_delta(z[u].y, gv[u].y, sc.y, sh.y);
+                const float d2 = bt_delta(z[u].z, gv[u].z, sc.z, sh.z), d3 = bt_delta(z[u].w, gv[u].w, sc.w, sh.w);
+                a[0] += d0; a[1] += d1; a[2] += d2; a[3] += d3;
+                a[4] += (double)d0 * z[u].x; a[5] += (double)d1 * z[u].y; a[6] += (double)d2 * z[u].z; a[7] += (double)d3 * z[u].w;
+            }
+        }
+        for (; row < rows; row += step) {
+            const float4 z = bt_ld4(zs + row * sg.ld), gv = bt_ld4(gs + row * (long long)g_ld);
+            const float d0 = bt_delta(z.x, gv.x, sc.x, sh.x), d1 = bt_delta(z.y, gv.y, sc.y, sh.y);
+            const float d2 = bt_delta(z.z, gv.z, sc.z, sh.z), d3 = bt_delta(z.w, gv.w, sc.w, sh.w);
+            a[0] += d0; a[1] += d1; a[2] += d2; a[3] += d3;
+            a[4] += (double)d0 * z.x; a[5] += (double)d1 * z.y; a[6] += (double)d2 * z.z; a[7] += (double)d3 * z.w;
+        }
+    }
+    bt_block_partials(a, L, sg.C, sg.c0, segs.ctot, nb, part);
+}
+
+// backward pass 2 (thread = channel): dgamma, dbeta, and the fp32 coefficients of dz = A (delta - m1 - (z - mu) m2)
+__global__ __launch_bounds__(256) void bt_bwd_finalize_kernel(const double *__restrict__ tot, int ctot, long long rows,
+                                                              const float *__restrict__ gamma, const double *__restrict__ stats,
+                                                              float *__restrict__ coef, float *__restrict__ d_gamma,
+                                                              float *__restrict__ d_beta) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= ctot) return;
+    const double N = (double)rows;
+    const double mu = stats[c], inv = stats[ctot + c];
+    const double db = tot[c], dg = (tot[ctot + c] - mu * db) * inv;
+    coef[c] = (float)((double)gamma[c] * inv);
+    coef[ctot + c] = (float)(db / N);
+    coef[2 * ctot + c] = (float)(dg / N * inv);
+    coef[3 * ctot + c] = (float)mu;
+    d_gamma[c] = (float)dg;
+    d_beta[c] = (float)db;
+}
+
+// backward pass 3: dz into the segment's dx (the row stride and channel offset of its z).  grid (nb, segments)
+__global__ __launch_bounds__(256) void bt_bwd_apply_kernel(BtSegs segs, long long rows, int nb, const float *__restrict__ scale_shift,
+                                                           const float *__restrict__ coef, const float *__restrict__ g, int g_ld,
+                                                           int g_off) {
+    const BtSeg sg = segs.s[blockIdx.y];
+    const BtLane L = bt_lane(sg.C);
+    if (!L.live) return;
+    const int ct = segs.ctot, c = sg.c0 + 4 * L.q;
+    const float4 sc = bt_ld4(scale_shift + c), sh = bt_ld4(scale_shift + ct + c);
+    const float4 A = bt_ld4(coef + c), m1 = bt_ld4(coef + ct + c), m2 = bt_ld4(coef + 2 * ct + c), mu = bt_ld4(coef + 3 * ct + c);
+    const float *zs = sg.x + sg.off + 4 * L.q, *gs = g + g_off + c;
+    float *ds = sg.dx + sg.off + 4 * L.q;
+    const long long step = (long long)nb * L.R;
+    for (long long row = (long long)blockIdx.x * L.R + L.r; row < rows; row += step) {
+        const float4 z = bt_ld4(zs + row * sg.ld), gv = bt_ld4(gs + row * (long long)g_ld);
+        float4 o;
+        o.x = A.x * (bt_delta(z.x, gv.x, sc.x, sh.x) - m1.x - (z.x - mu.x) * m2.x);
+        o.y = A.y * (bt_delta(z.y, gv.y, sc.y, sh.y) - m1.y - (z.y - mu.y) * m2.y);
+        o.z = A.z * (bt_delta(z.z, gv.z, sc.z, sh.z) - m1.z - (z.z - mu.z) * m2.z);
+        o.w = A.w * (bt_delta(z.w, gv.w, sc.w, sh.w) - m1.w - (z.w - mu.w) * m2.w);
+        bt_st4(ds + row * sg.ld, o);
+    }
+}
+
+static int bt_blocks(long long rows) {
+    const long long b = (rows + 255) / 256;
+    return (int)(b < 1 ? 1 : (b > BT_MAX_BLOCKS ? BT_MAX_BLOCKS : b));
+}
+
+// [partials: 2 ctot nb doubles][totals: 2 ctot doubles][backward coefficients: 4 ctot floats]
+LIDAR_EXPORT size_t lidar_bn_relu_train_workspace_bytes(long long rows, int channels) {
+    if (rows < 1 || channels < 1) return 0;
+    const size_t c = (size_t)channels;
+    return align_up((2 * c * bt_blocks(rows) + 2 * c) * sizeof(double) + 4 * c * sizeof(float), 256);
+}
+
+static bool bt_aligned(const void *p) { return p && ((uintptr_t)p & 15) == 0; }
+
+// host segment tables -> BtSegs; LIDAR_ERR_ARG on anything the kernels do not take
+static int bt_segs(int nseg, void *const *x, void *const *dx, const int *x_ld, const int *x_off, const int *seg_C, BtSegs &S) {
+    if (nseg < 1 || nseg > BT_MAX_SEG || !x || !x_ld || !x_off || !seg_C) return LIDAR_ERR_ARG;
+    S.n = nseg;
+    S.ctot = 0;
+    for (int i = 0; i < nseg; ++i) {
+        const int C = seg_C[i], ld = x_ld[i], off = x_off[i];
+        if (!bt_aligned(x[i]) || C < 4 || C > BT_MAX_C || C % 4 || ld % 4 || off % 4 || off < 0 || off + C > ld) return LIDAR_ERR_ARG;
+        if (dx && !bt_aligned(dx[i])) return LIDAR_ERR_ARG;
+        S.s[i].x = (const float *)x[i];
+        S.s[i].dx = dx ? (float *)dx[i] : nullptr;
+        S.s[i].C = C; S.s[i].ld = ld; S.s[i].off = off; S.s[i].c0 = S.ctot;
+        S.ctot += C;
+    }
+    return LIDAR_OK;
+}
+
+static bool bt_map_ok(const void *p, int ld, int off, int ctot) {
+    return bt_aligned(p) && ld % 4 == 0 && off % 4 == 0 && off >= 0 && off + ctot <= ld;
+}
+
+LIDAR_EXPORT int lidar_bn_relu_train_forward(int nseg, void *const *x, const int *x_ld, const int *x_off, const int *seg_C,
+                                             long long rows, const float *gamma, const float *beta, float eps, float *y, int y_ld,
+                                             int y_off, double *stats, float *scale_shift, float *batch_stats, void *ws,
+                                             size_t ws_bytes, void *stream) {
+    BtSegs S;
+    if (bt_segs(nseg, x, nullptr, x_ld, x_off, seg_C, S) != LIDAR_OK) return LIDAR_ERR_ARG;
+    if (rows < 2 || !gamma || !beta || !stats || !bt_aligned(scale_shift) || !batch_stats || !bt_aligned(ws) || !(eps >= 0.f))
+        return LIDAR_ERR_ARG;
+    if (!bt_map_ok(y, y_ld, y_off, S.ctot)) return LIDAR_ERR_ARG;
+    if (ws_bytes < lidar_bn_relu_train_workspace_bytes(rows, S.ctot)) return LIDAR_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    const int nb = bt_blocks(rows);
+    double *part = (double *)ws, *tot = part + (size_t)2 * S.ctot * nb;
+    hipLaunchKernelGGL(bt_stats_kernel, dim3(nb, nseg), dim3(256), 0, s, S, rows, nb, part);
+    hipLaunchKernelGGL(bt_reduce_kernel, dim3(2 * S.ctot), dim3(256), 0, s, part, nb, tot);
+    hipLaunchKernelGGL(bt_finalize_kernel, dim3(divup(S.ctot, 256)), dim3(256), 0, s, tot, S.ctot, rows, gamma, beta, eps, stats,
+                       scale_shift, batch_stats);
+    hipLaunchKernelGGL(bt_apply_kernel, dim3(nb, nseg), dim3(256), 0, s, S, rows, nb, scale_shift, y, y_ld, y_off);
+    return lidar_check_launch("lidar_bn_relu_train_forward");
+}
+
+LIDAR_EXPORT int lidar_bn_relu_train_backward(int nseg, void *const *x, const int *x_ld, const int *x_off, const int *seg_C,
+                                              long long rows, const float *grad_y, int g_ld, int g_off, const float *gamma,
+                                              const double *stats, const float *scale_shift, void *const *dx, float *d_gamma,
+                                              float *d_beta, void *ws, size_t ws_bytes, void *stream) {
+    BtSegs S;
+    if (!dx || bt_segs(nseg, x, dx, x_ld, x_off, seg_C, S) != LIDAR_OK) return LIDAR_ERR_ARG;
+    if (rows < 2 || !gamma || !stats || !bt_aligned(scale_shift) || !d_gamma || !d_beta || !bt_aligned(ws)) return LIDAR_ERR_ARG;
+    if (!bt_map_ok(grad_y, g_ld, g_off, S.ctot)) return LIDAR_ERR_ARG;
+    if (ws_bytes < lidar_bn_relu_train_workspace_bytes(rows, S.ctot)) return LIDAR_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    const int nb = bt_blocks(rows);
+    double *part = (double *)ws, *tot = part + (size_t)2 * S.ctot * nb;
+    float *coef = (float *)(tot + 2 * S.ctot);
+    hipLaunchKernelGGL(bt_bwd_stats_kernel, dim3(nb, nseg), dim3(256), 0, s, S, rows, nb, scale_shift, grad_y, g_ld, g_off, part);
+    hipLaunchKernelGGL(bt_reduce_kernel, dim3(2 * S.ctot), dim3(256), 0, s, part, nb, tot);
+    hipLaunchKernelGGL(bt_bwd_finalize_kernel, dim3(divup(S.ctot, 256)), dim3(256), 0, s, tot, S.ctot, rows, gamma, stats, coef,
+                       d_gamma, d_beta);
+    hipLaunchKernelGGL(bt_bwd_apply_kernel, dim3(nb, nseg), dim3(256), 0, s, S, rows, nb, scale_shift, coef, grad_y, g_ld, g_off);
+    return lidar_check_launch("lidar_bn_relu_train_backward");
+}

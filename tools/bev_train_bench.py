@@ -1,0 +1,121 @@
+"""Times the bs-16 PointPillar-KITTI training step with the stock train-mode backbone and with the fused one (bev_train.py:
+csrc/bn_train.hip BatchNorm + ReLU, Winograd stride-1 convolutions forward and input gradient), alternated in one process:
+
+  step      PointPillarKITTI.train_loss(backbone=...) + backward (gradients of every parameter);
+  backbone  backbone_head_stock / backbone_head_train + backward alone on a fixed channels-last canvas (no PFN, scatter or loss).
+
+Inputs: 16 synthetic KITTI-like clouds and boxes (tests/test_gpu_pfn_train.py's workload).  Device events, each iteration times
+one stock and one fused call back to back; medians after warm-up; peak memory from torch.cuda.max_memory_allocated above what was
+allocated before the call.  Prints one JSON line.
+
+  python tools/bev_train_bench.py [--iters 20] [--only stock|fused] [--rocprof OUTDIR]
+
+--rocprof OUTDIR: afterwards runs this script twice more in child processes (--only stock, then --only fused) under
+`rocprofv3 --kernel-trace --stats --output-format csv -d OUTDIR/<backbone>`, so each backbone's kernel statistics come from a run of
+their own.
+"""
+import argparse
+import importlib.util
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def load_test_module():
+    spec = importlib.util.spec_from_file_location("_pfn_train_tests", os.path.join(ROOT, "tests", "test_gpu_pfn_train.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def peak_mb(fn):
+    torch.cuda.synchronize()
+    base = torch.cuda.memory_allocated()
+    torch.cuda.reset_peak_memory_stats()
+    fn()
+    torch.cuda.synchronize()
+    return round((torch.cuda.max_memory_allocated() - base) / 2 ** 20, 1)
+
+
+def alternate(fns, iters, warmup):
+    """{name: (median ms, min ms)}, the callables timed in turn within every iteration"""
+    for _ in range(warmup):
+        for fn in fns.values():
+            fn()
+    torch.cuda.synchronize()
+    ev = {k: (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for k in fns}
+    times = {k: [] for k in fns}
+    for _ in range(iters):
+        for k, fn in fns.items():
+            ev[k][0].record()
+            fn()
+            ev[k][1].record()
+            ev[k][1].synchronize()
+            times[k].append(ev[k][0].elapsed_time(ev[k][1]))
+    return {k: (float(np.median(v)), float(np.min(v))) for k, v in times.items()}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--only", choices=("stock", "fused"), default=None)
+    ap.add_argument("--rocprof", default=None)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("bev_train_bench: no GPU")
+    from lidardetection_amd.pointpillar import PointPillarKITTI
+    T = load_test_module()
+    dev, B = T.DEV, 16
+    pts, offs, gt = T._pp_inputs(B, 5)
+    torch.manual_seed(4)
+    pp = PointPillarKITTI(batch_size=B, device=dev).train()
+    params = [p for p in pp.parameters() if p.requires_grad]
+    bev_params = [p for m in (pp.blocks, pp.deblocks, pp.conv_cls, pp.conv_box, pp.conv_dir_cls) for p in m.parameters()]
+    g = torch.Generator(device="cpu").manual_seed(1)
+    canvas = torch.relu(torch.randn(B, 64, pp.ny, pp.nx, generator=g)).to(dev).contiguous(memory_format=torch.channels_last)
+    heads_g = None
+
+    def step(kind):
+        return lambda: torch.autograd.grad(sum(pp.train_loss(pts, offs, gt, backbone=kind)), params)
+
+    def backbone(kind):
+        def run():
+            nonlocal heads_g
+            head = pp.backbone_head_train(canvas) if kind == "fused" else pp.backbone_head_stock(canvas)
+            if heads_g is None:
+                heads_g = [torch.randn(h.shape, generator=g).to(dev) for h in head]
+            torch.autograd.grad(sum((h * hg).sum() for h, hg in zip(head, heads_g)), bev_params)
+        return run
+
+    kinds = [args.only] if args.only else ["stock", "fused"]
+    result = {"tool": "bev_train_bench", "device": torch.cuda.get_device_name(0), "batch": B}
+    for name, make in (("backbone", backbone), ("step", step)):
+        fns = {k: make(k) for k in kinds}
+        t = alternate(fns, args.iters, 3)
+        w = {}
+        for k in kinds:
+            w.update({f"{k}_ms_median": round(t[k][0], 3), f"{k}_ms_min": round(t[k][1], 3), f"{k}_peak_mb": peak_mb(fns[k])})
+        if len(kinds) == 2:
+            w["speedup"] = round(t["stock"][0] / t["fused"][0], 3)
+        result[name] = w
+    print(json.dumps(result), flush=True)
+    if args.rocprof:
+        for k in ("stock", "fused"):
+            # `timeout -k 10` bounds the whole process group, the profiled Python child included
+            cmd = ["timeout", "-k", "10", "600", "rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d",
+                   os.path.join(args.rocprof, k), "-o", "bev_train", "--", sys.executable, os.path.abspath(__file__), "--only", k,
+                   "--iters", "5"]
+            rc = subprocess.run(cmd).returncode
+            if rc != 0:
+                sys.exit(f"bev_train_bench: rocprofv3 pass ({k}) exited with {rc}")
+
+
+if __name__ == "__main__":
+    main()
