@@ -469,6 +469,19 @@ int lidar_wino43_pack_weights(const float *w, int Cin, int Cout, float *packed, 
 int lidar_wino43_conv3x3_nhwc(const float *in, int B, int H, int W, int Cin, int in_C, const float *packed, const float *bias, int relu,
                               int Cout, float *out, int out_C, int out_off, void *stream);
 
+/* The WEIGHT GRADIENT of the same layers (training; torch hands it to MIOpen) as Winograd F(3x3, 4x4) on the fp32 matrix cores
+ * (csrc/wino43_wgrad.hip): dw[co][ci][a][b] = sum_{n,h,w} g[n][h][w][co] x[n][h + a - 1][w + b - 1][ci] with zero padding, 36
+ * multiplications per 4 x 4 tile and (ci, co) where the direct sum needs 144.  x: (B, H, W) pixels of x_ld floats, channels [0, Cin);
+ * g (the output gradient): (B, H, W) pixels of g_ld floats, channels [0, Cout); any H, W >= 1; each map below 2^31 - 1 bytes.
+ * dw: contiguous (Cout, Cin, 3, 3), OVERWRITTEN.  Supported: Cin, Cout multiples of 32 in [32, 512].  fp32 MFMA accumulation over
+ * at most 512 tiles, partial sums in ws (plain stores; its previous contents do not matter), summed in fixed order in fp64 together
+ * with the output transform, one rounding to fp32: no float atomics, bitwise reproducible, no host read, graph-capturable.
+ * ws: lidar_wino43_wgrad_workspace_bytes (pure host; 0 for unsupported or empty shapes), 16-byte aligned. */
+int lidar_wino43_wgrad_supported(int Cin, int Cout);
+size_t lidar_wino43_wgrad_workspace_bytes(int B, int H, int W, int Cin, int Cout);
+int lidar_wino43_wgrad_nhwc(const float *x, int x_ld, const float *g, int g_ld, int B, int H, int W, int Cin, int Cout, float *dw,
+                            void *ws, size_t ws_bytes, void *stream);
+
 /* ConvTranspose2d with kernel == stride == s (the deblocks of BaseBEVBackbone, base_bev_backbone.py:51-57) + folded BatchNorm shift
  * + ReLU + the write into the layer's channel slice of the concatenated map (base_bev_backbone.py:103) as ONE fp32-MFMA kernel
  * (csrc/deconv_gemm.hip): out[b][s y + ky][s x + kx][out_off + c] = act(sum_k in[b][y][x][k] W[k][(ky, kx, c)] + bias[c]).

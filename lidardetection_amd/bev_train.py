@@ -11,9 +11,11 @@ inference path does.  What runs here instead:
   * stride-1 3x3 convolutions run forward on the Winograd kernels (wino.conv3x3_auto's routing: F(4x4, 3x3) in csrc/wino43_conv.hip,
     F(2x2, 3x3) in csrc/wino_conv.hip for maps too large for F(4x4)), and so does their input gradient: a stride-1, pad-1 3x3
     convolution of the output gradient with the filters flipped by 180 degrees and Cin / Cout swapped (repacked every step);
-  * their weight gradient stays on the library (torch.ops.aten.convolution_backward, MIOpen), as do the stride-2 convolutions,
-    the deblock convolutions and everything after the backbone.
-Routing is per layer (TrainBEVBackbone.routes): anything the kernels do not take runs the stock module for that layer.
+  * their weight gradient runs on the library by default (torch.ops.aten.convolution_backward, MIOpen: split-K with float atomics,
+    not bitwise reproducible) and, with wgrad="wino", on the Winograd F(3x3, 4x4) weight-gradient kernel (csrc/wino43_wgrad.hip,
+    wino.conv3x3_wgrad_f43: bitwise reproducible) for every layer it supports and whose map fits (wgrad_route / wino.wgrad43_fits);
+  * the stride-2 convolutions, the deblock convolutions and everything after the backbone stay on the library.
+Routing is per layer (TrainBEVBackbone.routes / wgrad_routes): anything the kernels do not take runs the stock module for that layer.
 """
 import ctypes as C
 
@@ -190,11 +192,29 @@ def _wino(x, w):
     return wino.conv3x3(x, wino.pack_weights(w), cout, None, relu=False)
 
 
+WGRAD_OPTIONS = ("library", "wino")
+
+
+def _check_wgrad(wgrad, who):
+    if wgrad not in WGRAD_OPTIONS:
+        raise _lib.LidarHipError(f"{who}: wgrad must be one of {WGRAD_OPTIONS}, got {wgrad!r}")
+    return wgrad
+
+
+def wgrad_route(cin, cout, wgrad="library"):
+    """who computes the weight gradient of a Winograd-routed (Cin -> Cout) layer under the option `wgrad`: "wino" (the F(3x3, 4x4)
+    kernel) when the option asks for it and the kernel supports the widths, else "library".  Pure host.  (A host-side rule that
+    leaves a measured-slower shape on the library would live here; none is needed: DESIGN 3.17.)"""
+    _check_wgrad(wgrad, "wgrad_route")
+    return "wino" if wgrad == "wino" and wino.wgrad43_supported(cin, cout) else "library"
+
+
 class _WinoConv3x3Train(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight):
+    def forward(ctx, x, weight, wgrad="library"):
         w = weight.detach()
         ctx.save_for_backward(x, weight)
+        ctx.wgrad = wgrad
         return _wino(x, w)
 
     @staticmethod
@@ -204,20 +224,28 @@ class _WinoConv3x3Train(torch.autograd.Function):
         dx = dw = None
         if ctx.needs_input_grad[0]:    # dx = conv3x3(g, flip(w) with Cin / Cout swapped, padding=1): the same kernels
             dx = _wino(g, weight.detach().flip(2, 3).transpose(0, 1))
-        if ctx.needs_input_grad[1]:    # the weight gradient stays on the library (MIOpen)
-            dw = torch.ops.aten.convolution_backward(g, x, weight.detach(), None, [1, 1], [1, 1], [1, 1], False, [0, 0], 1,
-                                                     [False, True, False])[1]
-        return dx, dw
+        if ctx.needs_input_grad[1]:
+            cout, cin = weight.shape[:2]
+            # decided on the host from the shapes: the kernel where the option asks for it, the widths are supported and the maps
+            # fit its 32-bit offsets; the library (MIOpen) otherwise
+            if wgrad_route(cin, cout, ctx.wgrad) == "wino" and wino.wgrad43_fits(x.shape, cout):
+                dw = wino.conv3x3_wgrad_f43(x, g)
+            else:
+                dw = torch.ops.aten.convolution_backward(g, x, weight.detach(), None, [1, 1], [1, 1], [1, 1], False, [0, 0], 1,
+                                                         [False, True, False])[1]
+        return dx, dw, None
 
 
-def conv3x3_train(x, weight):
+def conv3x3_train(x, weight, wgrad="library"):
     """conv2d(x, weight, stride=1, padding=1) (no bias) on a channels-last fp32 map, forward and input gradient on the Winograd
-    kernels, weight gradient on the library; saves x only"""
+    kernels; weight gradient on the library (wgrad="library", the default) or on the Winograd weight-gradient kernel where it takes
+    the layer (wgrad="wino"); saves x only"""
+    _check_wgrad(wgrad, "conv3x3_train")
     if not wino_train_supported(weight.shape[1], weight.shape[0]):
         raise _lib.LidarHipError(f"conv3x3_train: (Cout, Cin) = {tuple(weight.shape[:2])} is not taken by the Winograd kernels in both directions")
     if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous(memory_format=torch.channels_last)):
         raise _lib.LidarHipError("conv3x3_train: expected a channels-last float32 CUDA tensor")
-    return _WinoConv3x3Train.apply(x, weight)
+    return _WinoConv3x3Train.apply(x, weight, wgrad)
 
 
 # ------------------------------------------------------------------ the backbone
@@ -267,9 +295,11 @@ class TrainBEVBackbone:
     """BaseBEVBackbone's train-mode forward on the reference-shaped modules themselves (`blocks`, `deblocks` as
     pointpillar.make_bev_backbone / the reference build them): their parameters receive the gradients and their BatchNorm running
     statistics are updated.  Call with the channels-last fp32 BEV map -> the concatenated deblock map (channels-last); autograd
-    does the backward.  Building it is pure host (routes are decided from the modules' settings)."""
+    does the backward.  Building it is pure host (routes are decided from the modules' settings).  wgrad: who computes the weight
+    gradients of the "wino"-routed layers ("library", the default, or "wino": see wgrad_routes)."""
 
-    def __init__(self, blocks, deblocks):
+    def __init__(self, blocks, deblocks, wgrad="library"):
+        self.wgrad = _check_wgrad(wgrad, "TrainBEVBackbone")
         self.blocks, self.deblocks = list(blocks), list(deblocks)
         self.plan = []
         for blk in self.blocks:
@@ -294,15 +324,21 @@ class TrainBEVBackbone:
         """-> [[route of each layer] per block], [route of each deblock]  (a block of unknown structure: ["stock"])"""
         return ([[s[0] for s in steps] if kind == "layers" else ["stock"] for kind, steps in self.plan], list(self.de_routes))
 
-    @staticmethod
-    def _layer(step, x):
+    def wgrad_routes(self):
+        """-> [[who computes each layer's weight gradient] per block]: "wino" (csrc/wino43_wgrad.hip), "library" (MIOpen), or None for
+        a layer that is not on the Winograd route at all (routes() != "wino": autograd's own backward).  From the widths alone; a
+        "wino" layer whose map does not fit the kernel's 32-bit offsets (wino.wgrad43_fits) still takes the library at run time."""
+        return [[(wgrad_route(s[3].in_channels, s[3].out_channels, self.wgrad) if s[0] == "wino" else None) for s in steps]
+                if kind == "layers" else [None] for kind, steps in self.plan]
+
+    def _layer(self, step, x):
         route, zp, pad, conv, bn, act = step
         if route == "stock":
             if zp != (0, 0, 0, 0):
                 x = F.pad(x, zp)
             return _cl(act(bn(conv(x))))
         if route == "wino":
-            z = conv3x3_train(x, conv.weight)
+            z = conv3x3_train(x, conv.weight, self.wgrad)
         else:
             z = _cl(F.conv2d(x, conv.weight, conv.bias, conv.stride, pad))
         return bn_relu_train(z, bn)

@@ -192,16 +192,20 @@ class PointPillarKITTI(nn.Module):
         dirs = self.conv_dir_cls(x).permute(0, 2, 3, 1).reshape(self.B, -1, self.num_dir_bins)
         return cls, box, dirs
 
-    def backbone_head_train(self, canvas):
+    def backbone_head_train(self, canvas, wgrad="library"):
         """backbone_head_stock() in train mode on this package's kernels (bev_train.TrainBEVBackbone: fused train-mode BatchNorm +
         ReLU, Winograd stride-1 convolutions forward and input gradient, the deblocks' BatchNorm written straight into the
-        concatenated map); the heads stay stock.  Needs the channels-last model (channels_last=True) and a channels-last canvas."""
+        concatenated map); the heads stay stock.  Needs the channels-last model (channels_last=True) and a channels-last canvas.
+        wgrad: who computes the weight gradients of the stride-1 3x3 layers, "library" (MIOpen) or "wino" (csrc/wino43_wgrad.hip)."""
+        from .bev_train import WGRAD_OPTIONS, TrainBEVBackbone
+        if wgrad not in WGRAD_OPTIONS:
+            raise pillar_ops._lib.LidarHipError(f"PointPillarKITTI.backbone_head_train: wgrad must be one of {WGRAD_OPTIONS}, got {wgrad!r}")
         if not self.channels_last:
             raise pillar_ops._lib.LidarHipError("PointPillarKITTI.backbone_head_train needs the channels-last model (channels_last=True)")
-        if self.__dict__.get("_bev_train") is None:
-            from .bev_train import TrainBEVBackbone
-            self.__dict__["_bev_train"] = TrainBEVBackbone(self.blocks, self.deblocks)
-        x = self.__dict__["_bev_train"](canvas)
+        key = "_bev_train" if wgrad == "library" else "_bev_train_" + wgrad
+        if self.__dict__.get(key) is None:
+            self.__dict__[key] = TrainBEVBackbone(self.blocks, self.deblocks, wgrad=wgrad)
+        x = self.__dict__[key](canvas)
         cls = self.conv_cls(x).permute(0, 2, 3, 1).reshape(self.B, -1, self.num_class)
         box = self.conv_box(x).permute(0, 2, 3, 1).reshape(self.B, -1, 7)
         dirs = self.conv_dir_cls(x).permute(0, 2, 3, 1).reshape(self.B, -1, self.num_dir_bins)
@@ -215,16 +219,19 @@ class PointPillarKITTI(nn.Module):
         t = head.assign_targets(gt_boxes)
         return anchor_loss.anchor_head_loss(*head_out, t['box_cls_labels'], t['box_reg_targets'], head.loss_anchors(), head.loss_spec)
 
-    def train_loss(self, points, point_offsets, gt_boxes, host_offsets=None, backbone="stock"):
+    def train_loss(self, points, point_offsets, gt_boxes, host_offsets=None, backbone="stock", wgrad="library"):
         """One training forward of PointPillar-KITTI on this package's kernels: voxelise (no gradient), the train-mode PillarVFE
         (batch statistics; pfn_norm's running statistics are updated), the differentiable scatter into a fresh canvas, the backbone
         and head (train-mode BatchNorm) and rpn_loss.  -> (cls_loss, loc_loss, dir_loss), differentiable with respect to
         every parameter.  gt_boxes (B, M, 8) [box | class id].  No host synchronisation.
-        backbone: "stock" (backbone_head_stock: torch modules) or "fused" (backbone_head_train; needs channels_last)."""
+        backbone: "stock" (backbone_head_stock: torch modules) or "fused" (backbone_head_train; needs channels_last).
+        wgrad ("library" or "wino"): backbone_head_train's option; it has no effect on the "stock" backbone."""
         if not self.training:
             raise pillar_ops._lib.LidarHipError("PointPillarKITTI.train_loss needs train mode (call .train() first)")
         if backbone not in ("stock", "fused"):
             raise pillar_ops._lib.LidarHipError(f"PointPillarKITTI.train_loss: backbone must be 'stock' or 'fused', got {backbone!r}")
+        if wgrad not in ("library", "wino"):
+            raise pillar_ops._lib.LidarHipError(f"PointPillarKITTI.train_loss: wgrad must be 'library' or 'wino', got {wgrad!r}")
         if backbone == "fused" and not self.channels_last:
             raise pillar_ops._lib.LidarHipError("PointPillarKITTI.train_loss(backbone='fused') needs the channels-last model")
         with torch.no_grad():   # fresh voxel buffers: the PFN's backward reads them after the next step may have voxelised
@@ -236,7 +243,7 @@ class PointPillarKITTI(nn.Module):
                                            momentum=n.momentum, num_batches_tracked=n.num_batches_tracked, num_voxels_dev=total)
         canvas = pillar_ops.pillar_scatter_train(feat, vox["voxel_coords"], self.B, self.nx, self.ny, num_voxels_dev=total,
                                                  channels_last=self.channels_last)
-        head = self.backbone_head_train(canvas) if backbone == "fused" else self.backbone_head_stock(canvas)
+        head = self.backbone_head_train(canvas, wgrad) if backbone == "fused" else self.backbone_head_stock(canvas)
         return self.rpn_loss(head, gt_boxes)
 
     def _loss_head(self):

@@ -1,5 +1,6 @@
-"""Host side of csrc/wino_conv.hip: the stride-1 3x3 convolutions of the dense BEV backbone (pcdet/models/backbones_2d/
-base_bev_backbone.py:34-45) as Winograd F(2x2, 3x3) on the fp32 matrix cores, shift + ReLU in the kernel's epilogue."""
+"""Host side of csrc/wino_conv.hip and csrc/wino43_conv.hip: the stride-1 3x3 convolutions of the dense BEV backbone
+(pcdet/models/backbones_2d/base_bev_backbone.py:34-45) as Winograd F(2x2, 3x3) / F(4x4, 3x3) on the fp32 matrix cores, shift + ReLU in
+the kernels' epilogue; and of csrc/wino43_wgrad.hip: the same layers' weight gradient as Winograd F(3x3, 4x4) (conv3x3_wgrad_f43)."""
 import os
 
 import torch
@@ -175,3 +176,52 @@ def conv3x3_grouped(x, packed, group_cin, n_groups, bias=None, relu=False, out=N
                                                  int(bool(relu)), _lib.ptr(out), out.shape[1], int(out_offset), _lib.stream()),
                "lidar_wino_conv3x3_grouped_nhwc")
     return out
+
+
+# ------------------------------------------------------------------ weight gradient (csrc/wino43_wgrad.hip)
+def wgrad43_supported(cin, cout):
+    """the F(3x3, 4x4) weight-gradient kernel takes this layer: Cin and Cout multiples of 32 in [32, 512]"""
+    return bool(_lib.lib().lidar_wino43_wgrad_supported(int(cin), int(cout)))
+
+
+def wgrad43_fits(x_shape, cout, x_ld=None, g_ld=None):
+    """the weight-gradient kernel can address an x of shape x_shape (B, Cin, H, W) and its (B, cout, H, W) output gradient: both
+    maps (at their row strides x_ld / g_ld, default: the channel counts) under _F43_MAX_BYTES and not empty.  Pure host arithmetic
+    (no library call)."""
+    B, cin, H, W = (int(v) for v in x_shape)
+    x_ld, g_ld = cin if x_ld is None else int(x_ld), int(cout) if g_ld is None else int(g_ld)
+    return (B > 0 and H > 0 and W > 0 and B * H * W * x_ld * 4 < _F43_MAX_BYTES[0] and B * H * W * g_ld * 4 < _F43_MAX_BYTES[0])
+
+
+def _nhwc_ld(t, what):
+    """-> row stride (floats) of a channels-last (B, C, H, W) fp32 CUDA map or of a channel slice of one"""
+    if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 4):
+        raise _lib.LidarHipError(f"{what}: expected a 4-d float32 CUDA (ROCm) tensor, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    B, Cc, H, W = t.shape
+    ld = t.stride(3)
+    if t.stride() != (H * W * ld, 1, W * ld, ld) or ld < Cc:
+        raise _lib.LidarHipError(f"{what}: expected a channels-last map (or a channel slice of one), got strides {t.stride()}")
+    return ld
+
+
+def conv3x3_wgrad_f43(x, g):
+    """the weight gradient of conv2d(x, w, stride=1, padding=1): x (B, Cin, H, W) and the output gradient g (B, Cout, H, W), both
+    channels-last fp32 maps or channel slices of such maps -> dW (Cout, Cin, 3, 3) fp32, contiguous.  Winograd F(3x3, 4x4) on the
+    matrix cores, partial sums over <= 512 tiles in fp32, the rest in fp64; bitwise reproducible; no host synchronisation."""
+    from . import workspace
+    x_ld, g_ld = _nhwc_ld(x, "wino.conv3x3_wgrad_f43 x"), _nhwc_ld(g, "wino.conv3x3_wgrad_f43 g")
+    B, cin, H, W = x.shape
+    cout = g.shape[1]
+    if g.shape[0] != B or tuple(g.shape[2:]) != (H, W) or g.device != x.device:
+        raise _lib.LidarHipError(f"wino.conv3x3_wgrad_f43: x {tuple(x.shape)} and g {tuple(g.shape)} must share batch, height, width and device")
+    if not wgrad43_supported(cin, cout):
+        raise _lib.LidarHipError(f"wino.conv3x3_wgrad_f43: (Cin, Cout) = ({cin}, {cout}) is not supported (multiples of 32 in [32, 512])")
+    if not wgrad43_fits(x.shape, cout, x_ld, g_ld):
+        raise _lib.LidarHipError(f"wino.conv3x3_wgrad_f43: maps of shape {tuple(x.shape)} / {tuple(g.shape)} are empty or too large (wgrad43_fits)")
+    L = _lib.lib()
+    wsb = L.lidar_wino43_wgrad_workspace_bytes(B, H, W, cin, cout)
+    ws = workspace.get("wino43_wgrad", wsb, x.device)
+    dw = torch.empty((cout, cin, 3, 3), dtype=torch.float32, device=x.device)
+    _lib.check(L.lidar_wino43_wgrad_nhwc(_lib.ptr(x), x_ld, _lib.ptr(g), g_ld, B, H, W, cin, cout, _lib.ptr(dw), _lib.ptr(ws), wsb,
+                                         _lib.stream()), "lidar_wino43_wgrad_nhwc")
+    return dw

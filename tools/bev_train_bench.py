@@ -1,18 +1,19 @@
-"""Times the bs-16 PointPillar-KITTI training step with the stock train-mode backbone and with the fused one (bev_train.py:
-csrc/bn_train.hip BatchNorm + ReLU, Winograd stride-1 convolutions forward and input gradient), alternated in one process:
+"""Times the bs-16 PointPillar-KITTI training step with the stock train-mode backbone, with the fused one (bev_train.py:
+csrc/bn_train.hip BatchNorm + ReLU, Winograd stride-1 convolutions forward and input gradient, weight gradients on the library) and
+with the fused one + wgrad="wino" (csrc/wino43_wgrad.hip for the stride-1 3x3 weight gradients), alternated in one process:
 
   step      PointPillarKITTI.train_loss(backbone=...) + backward (gradients of every parameter);
   backbone  backbone_head_stock / backbone_head_train + backward alone on a fixed channels-last canvas (no PFN, scatter or loss).
 
 Inputs: 16 synthetic KITTI-like clouds and boxes (tests/test_gpu_pfn_train.py's workload).  Device events, each iteration times
-one stock and one fused call back to back; medians after warm-up; peak memory from torch.cuda.max_memory_allocated above what was
+one call of each column back to back; medians after warm-up; peak memory from torch.cuda.max_memory_allocated above what was
 allocated before the call.  Prints one JSON line.
 
-  python tools/bev_train_bench.py [--iters 20] [--only stock|fused] [--rocprof OUTDIR]
+  python tools/bev_train_bench.py [--iters 20] [--only stock|fused|fused_wino] [--rocprof OUTDIR]
 
---rocprof OUTDIR: afterwards runs this script twice more in child processes (--only stock, then --only fused) under
-`rocprofv3 --kernel-trace --stats --output-format csv -d OUTDIR/<backbone>`, so each backbone's kernel statistics come from a run of
-their own.
+--rocprof OUTDIR: afterwards runs this script once more per column in child processes (--only stock, fused, fused_wino) under
+`rocprofv3 --kernel-trace --stats --output-format csv -d OUTDIR/<column>` (kernel trace only, no counters), so each column's kernel
+statistics come from a run of their own.
 """
 import argparse
 import importlib.util
@@ -26,6 +27,11 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+
+KINDS = ("stock", "fused", "fused_wino")
+# column -> (backbone option, wgrad option) of PointPillarKITTI.train_loss / backbone_head_train
+OPTIONS = {"stock": ("stock", "library"), "fused": ("fused", "library"), "fused_wino": ("fused", "wino")}
 
 
 def load_test_module():
@@ -65,7 +71,7 @@ def alternate(fns, iters, warmup):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--only", choices=("stock", "fused"), default=None)
+    ap.add_argument("--only", choices=KINDS, default=None)
     ap.add_argument("--rocprof", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -83,18 +89,19 @@ def main():
     heads_g = None
 
     def step(kind):
-        return lambda: torch.autograd.grad(sum(pp.train_loss(pts, offs, gt, backbone=kind)), params)
+        bb, wg = OPTIONS[kind]
+        return lambda: torch.autograd.grad(sum(pp.train_loss(pts, offs, gt, backbone=bb, wgrad=wg)), params)
 
     def backbone(kind):
         def run():
             nonlocal heads_g
-            head = pp.backbone_head_train(canvas) if kind == "fused" else pp.backbone_head_stock(canvas)
+            head = pp.backbone_head_stock(canvas) if kind == "stock" else pp.backbone_head_train(canvas, OPTIONS[kind][1])
             if heads_g is None:
                 heads_g = [torch.randn(h.shape, generator=g).to(dev) for h in head]
             torch.autograd.grad(sum((h * hg).sum() for h, hg in zip(head, heads_g)), bev_params)
         return run
 
-    kinds = [args.only] if args.only else ["stock", "fused"]
+    kinds = [args.only] if args.only else list(KINDS)
     result = {"tool": "bev_train_bench", "device": torch.cuda.get_device_name(0), "batch": B}
     for name, make in (("backbone", backbone), ("step", step)):
         fns = {k: make(k) for k in kinds}
@@ -102,12 +109,13 @@ def main():
         w = {}
         for k in kinds:
             w.update({f"{k}_ms_median": round(t[k][0], 3), f"{k}_ms_min": round(t[k][1], 3), f"{k}_peak_mb": peak_mb(fns[k])})
-        if len(kinds) == 2:
+        if len(kinds) == len(KINDS):
             w["speedup"] = round(t["stock"][0] / t["fused"][0], 3)
+            w["wino_wgrad_speedup"] = round(t["fused"][0] / t["fused_wino"][0], 3)        # over the fused column (wgrad="library")
         result[name] = w
     print(json.dumps(result), flush=True)
     if args.rocprof:
-        for k in ("stock", "fused"):
+        for k in KINDS:
             # `timeout -k 10` bounds the whole process group, the profiled Python child included
             cmd = ["timeout", "-k", "10", "600", "rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d",
                    os.path.join(args.rocprof, k), "-o", "bev_train", "--", sys.executable, os.path.abspath(__file__), "--only", k,
