@@ -119,6 +119,8 @@ int lidar_mean_vfe(const float *voxels, const void *num_points, int num_voxels, 
 
 /* PointPillarScatter.forward (pcdet/models/backbones_2d/map_to_bev/pointpillar_scatter.py:14-37), nz == 1:
  * canvas (batch, channels, ny, nx) f32, every element written exactly once. channels in {32,64,128}.
+ * A pillar with b outside [0, batch), x outside [0, nx) or a row outside [0, ny) lies outside the canvas and is left out
+ * (x == nx is not the first cell of the next row).
  * channels_last = 1 writes the same logical tensor with NHWC strides (torch.channels_last), which MIOpen's fp32
  * convolutions consume without layout transposes. */
 /* Resident-canvas variant: ONE persistent channels-last canvas (B, ny, nx, C); a call clears the cells the previous call wrote
@@ -162,7 +164,8 @@ int lidar_pfn_train_backward(const float *voxels, const void *num_points, const 
                              const float *scale_shift, float *d_weight, float *d_gamma, float *d_beta, void *ws, size_t ws_bytes,
                              void *stream);
 /* PointPillarScatter backward: grad_features (V, channels) = grad_canvas at each pillar's cell (lidar_pillar_scatter's cell
- * rule), zero for rows past num_voxels_dev and pillars outside the canvas.  channels_last: grad_canvas has NHWC strides. */
+ * rule), zero for rows past num_voxels_dev and pillars outside the canvas (b outside [0, batch), x outside [0, nx), row outside
+ * [0, ny)).  channels in {32, 64, 128}; channels_last: grad_canvas has NHWC strides. */
 int lidar_pillar_scatter_backward(const float *grad_canvas, const void *coords, int coords_are_float, int num_voxels,
                                   const int *num_voxels_dev, int channels, int batch, int nx, int ny, int channels_last,
                                   float *grad_features, void *stream);

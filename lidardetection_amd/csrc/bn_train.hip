@@ -11,7 +11,10 @@
 //             running-statistics inputs (mean, unbiased variance); then y = max(z scale + shift, 0).
 //   backward: delta = g [y > 0] with y recomputed from z bit for bit (no mask is stored); sum delta and sum delta z in fp64, reduced
 //             the same way; dbeta = sum delta, dgamma = sum delta zh = (sum delta z - mu sum delta) / sigma,
-//             dz = gamma / sigma (delta - dbeta / N - zh dgamma / N).
+//             dz = gamma / sigma (delta - dbeta / N - zh dgamma / N), evaluated per element in fp64 (fp64 coefficients and mu in
+//             the workspace) and rounded once: the three terms cancel, to ~eps / var of their size at N = 2, where fp32
+//             coefficients left dz at 4.5e-5 of its scale against float64 (now 6.8e-8).  The pass moves 12 bytes
+//             per element for five fp64 operations; its time with fp64 has not been measured in isolation.
 // No float atomics and no host read: every result is bitwise reproducible and every call can be captured in a graph.
 #include "common.h"
 
@@ -189,44 +192,48 @@ __global__ __launch_bounds__(256) void bt_bwd_stats_kernel(BtSegs segs, long lon
     bt_block_partials(a, L, sg.C, sg.c0, segs.ctot, nb, part);
 }
 
-// backward pass 2 (thread = channel): dgamma, dbeta, and the fp32 coefficients of dz = A (delta - m1 - (z - mu) m2)
+// backward pass 2 (thread = channel): dgamma, dbeta, and the fp64 coefficients of dz = A (delta - m1 - (z - mu) m2)
 __global__ __launch_bounds__(256) void bt_bwd_finalize_kernel(const double *__restrict__ tot, int ctot, long long rows,
                                                               const float *__restrict__ gamma, const double *__restrict__ stats,
-                                                              float *__restrict__ coef, float *__restrict__ d_gamma,
+                                                              double *__restrict__ coef, float *__restrict__ d_gamma,
                                                               float *__restrict__ d_beta) {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= ctot) return;
     const double N = (double)rows;
     const double mu = stats[c], inv = stats[ctot + c];
     const double db = tot[c], dg = (tot[ctot + c] - mu * db) * inv;
-    coef[c] = (float)((double)gamma[c] * inv);
-    coef[ctot + c] = (float)(db / N);
-    coef[2 * ctot + c] = (float)(dg / N * inv);
-    coef[3 * ctot + c] = (float)mu;
+    coef[c] = (double)gamma[c] * inv;
+    coef[ctot + c] = db / N;
+    coef[2 * ctot + c] = dg / N * inv;
+    coef[3 * ctot + c] = mu;
     d_gamma[c] = (float)dg;
     d_beta[c] = (float)db;
 }
 
 // backward pass 3: dz into the segment's dx (the row stride and channel offset of its z).  grid (nb, segments)
 __global__ __launch_bounds__(256) void bt_bwd_apply_kernel(BtSegs segs, long long rows, int nb, const float *__restrict__ scale_shift,
-                                                           const float *__restrict__ coef, const float *__restrict__ g, int g_ld,
+                                                           const double *__restrict__ coef, const float *__restrict__ g, int g_ld,
                                                            int g_off) {
     const BtSeg sg = segs.s[blockIdx.y];
     const BtLane L = bt_lane(sg.C);
     if (!L.live) return;
     const int ct = segs.ctot, c = sg.c0 + 4 * L.q;
     const float4 sc = bt_ld4(scale_shift + c), sh = bt_ld4(scale_shift + ct + c);
-    const float4 A = bt_ld4(coef + c), m1 = bt_ld4(coef + ct + c), m2 = bt_ld4(coef + 2 * ct + c), mu = bt_ld4(coef + 3 * ct + c);
+    double A[4], m1[4], m2[4], mu[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        A[k] = coef[c + k]; m1[k] = coef[ct + c + k]; m2[k] = coef[2 * ct + c + k]; mu[k] = coef[3 * ct + c + k];
+    }
     const float *zs = sg.x + sg.off + 4 * L.q, *gs = g + g_off + c;
     float *ds = sg.dx + sg.off + 4 * L.q;
     const long long step = (long long)nb * L.R;
     for (long long row = (long long)blockIdx.x * L.R + L.r; row < rows; row += step) {
         const float4 z = bt_ld4(zs + row * sg.ld), gv = bt_ld4(gs + row * (long long)g_ld);
         float4 o;
-        o.x = A.x * (bt_delta(z.x, gv.x, sc.x, sh.x) - m1.x - (z.x - mu.x) * m2.x);
-        o.y = A.y * (bt_delta(z.y, gv.y, sc.y, sh.y) - m1.y - (z.y - mu.y) * m2.y);
-        o.z = A.z * (bt_delta(z.z, gv.z, sc.z, sh.z) - m1.z - (z.z - mu.z) * m2.z);
-        o.w = A.w * (bt_delta(z.w, gv.w, sc.w, sh.w) - m1.w - (z.w - mu.w) * m2.w);
+        o.x = (float)(A[0] * ((double)bt_delta(z.x, gv.x, sc.x, sh.x) - m1[0] - ((double)z.x - mu[0]) * m2[0]));
+        o.y = (float)(A[1] * ((double)bt_delta(z.y, gv.y, sc.y, sh.y) - m1[1] - ((double)z.y - mu[1]) * m2[1]));
+        o.z = (float)(A[2] * ((double)bt_delta(z.z, gv.z, sc.z, sh.z) - m1[2] - ((double)z.z - mu[2]) * m2[2]));
+        o.w = (float)(A[3] * ((double)bt_delta(z.w, gv.w, sc.w, sh.w) - m1[3] - ((double)z.w - mu[3]) * m2[3]));
         bt_st4(ds + row * sg.ld, o);
     }
 }
@@ -236,11 +243,11 @@ static int bt_blocks(long long rows) {
     return (int)(b < 1 ? 1 : (b > BT_MAX_BLOCKS ? BT_MAX_BLOCKS : b));
 }
 
-// [partials: 2 ctot nb doubles][totals: 2 ctot doubles][backward coefficients: 4 ctot floats]
+// [partials: 2 ctot nb doubles][totals: 2 ctot doubles][backward coefficients: 4 ctot doubles]
 LIDAR_EXPORT size_t lidar_bn_relu_train_workspace_bytes(long long rows, int channels) {
     if (rows < 1 || channels < 1) return 0;
     const size_t c = (size_t)channels;
-    return align_up((2 * c * bt_blocks(rows) + 2 * c) * sizeof(double) + 4 * c * sizeof(float), 256);
+    return align_up((2 * c * bt_blocks(rows) + 2 * c + 4 * c) * sizeof(double), 256);
 }
 
 static bool bt_aligned(const void *p) { return p && ((uintptr_t)p & 15) == 0; }
@@ -299,7 +306,7 @@ LIDAR_EXPORT int lidar_bn_relu_train_backward(int nseg, void *const *x, const in
     hipStream_t s = (hipStream_t)stream;
     const int nb = bt_blocks(rows);
     double *part = (double *)ws, *tot = part + (size_t)2 * S.ctot * nb;
-    float *coef = (float *)(tot + 2 * S.ctot);
+    double *coef = tot + 2 * S.ctot;
     hipLaunchKernelGGL(bt_bwd_stats_kernel, dim3(nb, nseg), dim3(256), 0, s, S, rows, nb, scale_shift, grad_y, g_ld, g_off, part);
     hipLaunchKernelGGL(bt_reduce_kernel, dim3(2 * S.ctot), dim3(256), 0, s, part, nb, tot);
     hipLaunchKernelGGL(bt_bwd_finalize_kernel, dim3(divup(S.ctot, 256)), dim3(256), 0, s, tot, S.ctot, rows, gamma, stats, coef,

@@ -397,7 +397,8 @@ LIDAR_EXPORT int lidar_pfn_train_backward(const float *voxels, const void *num_p
 
 // ------------------------------------------------------------------ PointPillarScatter backward
 // d features[v][c] = d canvas at the pillar's cell (the cell rule of scatter_index_kernel in pillar.hip); rows past the device
-// count and pillars outside the canvas get zero.  channels_last: the gradient has NHWC strides (a cell's channels contiguous).
+// count and pillars outside the canvas (x outside [0, nx) or y outside [0, ny) included: the flattened index would alias a cell
+// of the neighbouring row) get zero.  channels_last: the gradient has NHWC strides (a cell's channels contiguous).
 template <bool NHWC>
 __global__ __launch_bounds__(256) void scatter_bwd_kernel(const float *__restrict__ gcanvas, const void *__restrict__ coords,
                                                           int coords_are_float, int nvox_host, const int *__restrict__ nvox_dev, int CH,
@@ -418,7 +419,7 @@ __global__ __launch_bounds__(256) void scatter_bwd_kernel(const float *__restric
                 b = cc.x; z = cc.y; y = cc.z; x = cc.w;
             }
             const long long cell = ((long long)z * ny + y) * nx + x;
-            if (b >= 0 && b < B && cell >= 0 && cell < plane)
+            if (b >= 0 && b < B && x >= 0 && x < nx && y >= 0 && y < ny && cell >= 0 && cell < plane)
                 g = NHWC ? gcanvas[((long long)b * plane + cell) * CH + c] : gcanvas[((long long)b * CH + c) * plane + cell];
         }
         gfeat[i] = g;

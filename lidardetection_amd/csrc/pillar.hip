@@ -365,7 +365,10 @@ __global__ void scatter_index_kernel(const void *__restrict__ coords, int coords
         // PointPillarScatter: z + y*nx + x with nz == 1 (pointpillar_scatter.py:27) == (z*hrows + y)*nx + x with z == 0;
         // SparseConvTensor.dense(): the (D*H, W) view of a (D, H, W) volume, hrows = H
         const long long cell = ((long long)z * hrows + y) * nx + x;
-        if (b >= 0 && b < B && cell >= 0 && cell < (long long)nx * ny) map[(size_t)b * nx * ny + cell] = v;
+        // x outside [0, nx) would alias a cell of the neighbouring row, y outside [0, hrows) one of the neighbouring z slab: such a
+        // pillar (voxel) lies outside the canvas (volume)
+        if (b >= 0 && b < B && x >= 0 && x < nx && y >= 0 && y < hrows && cell >= 0 && cell < (long long)nx * ny)
+            map[(size_t)b * nx * ny + cell] = v;
     }
 }
 
