@@ -228,6 +228,41 @@ def require_cuda(*tensors, allow=()):
             raise LidarHipError(f"expected a float32 / int32 tensor, got {t.dtype} (shape {tuple(t.shape)})")
 
 
+def require_nhwc(x, what):
+    """a kernel's input map: a fully contiguous channels-last (B, C, H, W) float32 tensor on the device"""
+    import torch
+    if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and x.is_contiguous(memory_format=torch.channels_last)):
+        raise LidarHipError(f"{what}: expected a channels-last float32 CUDA tensor")
+
+
+def nhwc_ld(t, what):
+    """-> row stride (floats) of a channels-last (B, C, H, W) fp32 CUDA map or of a channel slice of one"""
+    import torch
+    if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 4):
+        raise LidarHipError(f"{what}: expected a 4-d float32 CUDA (ROCm) tensor, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    B, Cc, H, W = t.shape
+    ld = t.stride(3)
+    if t.stride() != (H * W * ld, 1, W * ld, ld) or ld < Cc:
+        raise LidarHipError(f"{what}: expected a channels-last map (or a channel slice of one), got strides {t.stride()}")
+    return ld
+
+
+def nhwc_out(what, B, hw, cout, device, out=None, out_offset=0, sliced=False):
+    """where a kernel writes its `cout` channels for a map of batch B and spatial shape hw: -> (out, out_offset).  out=None: a new
+    channels-last float32 (B, cout, *hw) map, offset 0.  Otherwise `out`, checked: a fully contiguous channels-last float32 CUDA map
+    (sliced=True: or a channel slice of one, nhwc_ld) of that batch and spatial shape with channels [out_offset, out_offset + cout)."""
+    import torch
+    if out is None:
+        return torch.empty((B, cout, *hw), dtype=torch.float32, device=device, memory_format=torch.channels_last), 0
+    if sliced:
+        nhwc_ld(out, what + " out")
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous(memory_format=torch.channels_last)):
+        raise LidarHipError(f"{what}: output must be a channels-last float32 CUDA tensor")
+    if out.shape[0] != B or tuple(out.shape[2:]) != tuple(hw) or not 0 <= out_offset <= out.shape[1] - cout:
+        raise LidarHipError(f"{what}: output must be ({B}, >= out_offset + {cout}, *{tuple(hw)}), got {tuple(out.shape)} with out_offset {out_offset}")
+    return out, out_offset
+
+
 def require_last(t, k, what):
     """last dimension of `t` must be k (boxes: 7, points: 3, ...)"""
     if t is not None and (t.dim() == 0 or t.shape[-1] != k):

@@ -15,6 +15,7 @@ Results match the unfolded modules to fp32 rounding (folding re-associates one m
 """
 import ctypes as C
 import os
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -30,10 +31,7 @@ def bias_act_(x, bias, relu=True, out=None, out_offset=0):
     if not (x.is_cuda and x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last)):
         raise _lib.LidarHipError("bias_act_: expected a channels-last CUDA tensor")
     B, C, H, W = x.shape
-    if out is None:
-        out, out_offset = x, 0
-    elif not (out.is_contiguous(memory_format=torch.channels_last) and out.shape[0] == B and out.shape[2:] == x.shape[2:]):
-        raise _lib.LidarHipError("bias_act_: output must be channels-last with the same batch / spatial shape")
+    out, out_offset = (x, 0) if out is None else _lib.nhwc_out("bias_act_", B, (H, W), C, x.device, out, out_offset)
     _lib.check(_lib.lib().lidar_bias_act_nhwc(_lib.ptr(x), _lib.ptr(bias), B * H * W, C, int(bool(relu)), _lib.ptr(out),
                                               out.shape[1], int(out_offset), _lib.stream()), "lidar_bias_act_nhwc")
     return out
@@ -80,14 +78,12 @@ def gemm_bias_act_into_(x, w_kn, bias, out, out_offset, relu=True):
     (B, C_out, h, w) channels-last — one hipBLASLt GEMM whose epilogue writes at the map's row pitch.
     Returns False when the library path is not available (nothing written)."""
     _lib.require_cuda(w_kn, bias)
-    if not (x.is_cuda and out.is_cuda and x.dtype == torch.float32 and out.dtype == torch.float32):
-        raise _lib.LidarHipError("gemm_bias_act_into_: expected float32 CUDA (ROCm) tensors")
+    _lib.require_nhwc(x, "gemm_bias_act_into_")
     B, K, h, w = x.shape
     N = w_kn.shape[1]
-    if (not x.is_contiguous(memory_format=torch.channels_last) or not out.is_contiguous(memory_format=torch.channels_last)
-            or out.shape[0] != B or out.shape[2:] != x.shape[2:] or w_kn.shape[0] != K or bias.numel() != N
-            or out_offset + N > out.shape[1] or not w_kn.is_contiguous()):
-        raise _lib.LidarHipError("gemm_bias_act_into_: shapes / layouts do not match")
+    if w_kn.shape[0] != K or bias.numel() != N:
+        raise _lib.LidarHipError("gemm_bias_act_into_: shapes do not match")
+    out, out_offset = _lib.nhwc_out("gemm_bias_act_into_", B, (h, w), N, x.device, out, out_offset)
     return _lt_gemm(_lib.ptr(x), B * h * w, K, w_kn, bias, relu, C.c_void_p(out.data_ptr() + 4 * out_offset), out.shape[1], x.device)
 
 
@@ -138,13 +134,12 @@ def deconv_gemm_into_(x, packed, bias, s, out, out_offset=0, relu=True):
     """x (B, K, h, w) channels-last -> out[:, out_offset:out_offset + C_up] (B, C_out, s*h, s*w channels-last) = act(ConvTranspose2d
     (kernel == stride == s)(x) + bias): one fp32-MFMA kernel, no temporary, no pixel-shuffle pass (csrc/deconv_gemm.hip)"""
     _lib.require_cuda(packed, bias)
+    _lib.require_nhwc(x, "deconv_gemm_into_")
     B, K, h, w = x.shape
     c_up = bias.numel()
-    if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous(memory_format=torch.channels_last) and out.is_cuda
-            and out.dtype == torch.float32 and out.is_contiguous(memory_format=torch.channels_last) and out.shape[0] == B
-            and tuple(out.shape[2:]) == (s * h, s * w) and 0 <= out_offset and out_offset + c_up <= out.shape[1]
-            and packed.numel() == K * s * s * c_up):
-        raise _lib.LidarHipError("deconv_gemm_into_: shapes / layouts do not match")
+    if packed.numel() != K * s * s * c_up:
+        raise _lib.LidarHipError("deconv_gemm_into_: packed weights do not match (K, s, C_up)")
+    out, out_offset = _lib.nhwc_out("deconv_gemm_into_", B, (s * h, s * w), c_up, x.device, out, out_offset)
     _lib.check(_lib.lib().lidar_deconv_gemm_nhwc(_lib.ptr(x), B, h, w, K, _lib.ptr(packed), _lib.ptr(bias), int(bool(relu)), int(s), c_up,
                                                  _lib.ptr(out), out.shape[1], int(out_offset), _lib.stream()), "lidar_deconv_gemm_nhwc")
     return out
@@ -157,9 +152,7 @@ def bias_act_upsample_(y2d, bias, batch, h, w, s, out, out_offset=0, relu=True):
     C = bias.numel()
     if y2d.shape != (batch * h * w, s * s * C):
         raise _lib.LidarHipError("bias_act_upsample_: GEMM output shape does not match (batch*h*w, s*s*C)")
-    if not (out.is_contiguous(memory_format=torch.channels_last) and out.shape[0] == batch
-            and tuple(out.shape[2:]) == (h * s, w * s)):
-        raise _lib.LidarHipError("bias_act_upsample_: output must be channels-last (batch, C_out, h*s, w*s)")
+    out, out_offset = _lib.nhwc_out("bias_act_upsample_", batch, (h * s, w * s), C, y2d.device, out, out_offset)
     _lib.check(_lib.lib().lidar_bias_act_upsample_nhwc(_lib.ptr(y2d), _lib.ptr(bias), batch, h, w, s, C, int(bool(relu)),
                                                        _lib.ptr(out), out.shape[1], int(out_offset), _lib.stream()),
                "lidar_bias_act_upsample_nhwc")
@@ -192,69 +185,120 @@ def _fold(weight, bn, out_dim, conv_bias=None):
     return (weight.detach() * scale.view(shape)), shift.contiguous()
 
 
-class _FoldedConv(tuple):
-    """One folded Conv2d/BN/ReLU layer of a block.  Unpacks as (weight, shift, stride, conv padding (h, w), Winograd filters or None);
-    .dilation, .groups and .zero_pad (an asymmetric ZeroPad2d (left, right, top, bottom), applied with F.pad, or None: a symmetric one
-    is folded into the padding) carry the rest of the layer's settings."""
+class BlockLayer(NamedTuple):
+    """One [ZeroPad2d] Conv2d BatchNorm2d ReLU group of a block (parse_block): the modules and the padding they add up to.  The
+    folded inference path (FoldedBEVBackbone) and the train path (bev_train) both route from this record."""
+    zpad: Optional[nn.ZeroPad2d]
+    conv: nn.Conv2d
+    bn: nn.BatchNorm2d
+    act: Optional[nn.ReLU]
+    pad: Optional[tuple]              # the conv's zero padding (h, w) with a symmetric ZeroPad2d folded in (no padded copy); None: string padding / another padding mode
+    zero_pad: Optional[tuple]         # (left, right, top, bottom) of a ZeroPad2d that is not folded and stays a separate F.pad, else None
 
-    def __new__(cls, w, b, stride, pad, packed, dilation, groups, zero_pad):
-        self = super().__new__(cls, (w, b, stride, pad, packed))
-        self.dilation, self.groups, self.zero_pad = dilation, groups, zero_pad
-        return self
+    @property
+    def plain3x3(self):
+        """stride 1, 3x3, zero padding 1 and nothing else: the geometry the Winograd kernels compute (LAYER_NUMS per block,
+        base_bev_backbone.py:40-45; SECOND's first block opens with one too).  The widths: wino.supported / wino_train_supported."""
+        c = self.conv
+        return (self.pad == (1, 1) and self.zero_pad is None and tuple(c.kernel_size) == (3, 3) and tuple(c.stride) == (1, 1)
+                and tuple(c.dilation) == (1, 1) and c.groups == 1)
+
+
+def block_layer(zpad, conv, bn, act=None):
+    """-> the BlockLayer of ZeroPad2d `zpad` (or None), Conv2d, BatchNorm2d, ReLU.  Pure host."""
+    pad, zero_pad = None, None if zpad is None else tuple(int(v) for v in zpad.padding)
+    if conv.padding_mode == "zeros" and not isinstance(conv.padding, str):
+        pad = tuple(int(v) for v in conv.padding)
+        if zero_pad is not None and zero_pad[0] == zero_pad[1] >= 0 and zero_pad[2] == zero_pad[3] >= 0:
+            pad, zero_pad = (pad[0] + zero_pad[2], pad[1] + zero_pad[0]), None
+    return BlockLayer(zpad, conv, bn, act, pad, zero_pad)
+
+
+def parse_block(blk):
+    """Sequential of [ZeroPad2d] Conv2d BatchNorm2d ReLU ... -> [BlockLayer], or None for any other structure"""
+    mods, out, i = list(blk), [], 0
+    while i < len(mods):
+        zpad = None
+        if isinstance(mods[i], nn.ZeroPad2d):
+            zpad, i = mods[i], i + 1
+        if i + 3 > len(mods):
+            return None
+        conv, bn, act = mods[i:i + 3]
+        if not (isinstance(conv, nn.Conv2d) and isinstance(bn, nn.BatchNorm2d) and isinstance(act, nn.ReLU)):
+            return None
+        out.append(block_layer(zpad, conv, bn, act))
+        i += 3
+    return out
+
+
+class FoldedConv(NamedTuple):
+    """one folded Conv2d/BN/ReLU layer of a stage"""
+    weight: torch.Tensor              # BatchNorm scale folded in, channels-last
+    shift: torch.Tensor
+    stride: tuple
+    pad: tuple                        # BlockLayer.pad
+    dilation: tuple
+    groups: int
+    zero_pad: Optional[tuple]         # BlockLayer.zero_pad
+    wino: Optional[list]              # wino.pack_auto's filters for a layer on the Winograd kernels, else None
+
+
+class FoldedDeblock(NamedTuple):
+    """the folded deblock of a stage.  kind: "gemm" (ConvTranspose2d with kernel == stride: a plain GEMM on the NHWC map),
+    "deconv_mfma" (the same on csrc/deconv_gemm.hip), "deconv" / "conv" (any other ConvTranspose2d / a strided Conv2d: the library)"""
+    kind: str
+    weight: torch.Tensor              # "gemm" / "deconv_mfma": (K, s*s*C_up), columns (ky, kx, c); else the module's, channels-last
+    packed: Optional[torch.Tensor]    # "deconv_mfma": deconv_pack(weight)
+    shift: torch.Tensor
+    stride: int                       # "gemm" / "deconv_mfma": s (0 for the library kinds)
+    args: tuple                       # "deconv" / "conv": what F.conv_transpose2d / F.conv2d take after the bias (() for the others)
+
+
+def _cl(t):
+    return t if t.is_contiguous(memory_format=torch.channels_last) else t.contiguous(memory_format=torch.channels_last)
 
 
 class FoldedBEVBackbone:
-    """Built from the (eval-mode) reference-shaped modules; call with the channels-last canvas."""
+    """Built from the (eval-mode) reference-shaped modules; call with the channels-last canvas.  self.stages: one
+    ([FoldedConv], FoldedDeblock) per block."""
 
     def __init__(self, blocks, deblocks, heads):
         self.sources = collect_params(blocks, deblocks, *heads)
         self.source_key = params_key(self.sources)                  # owners rebuild when this no longer matches
         self.stages = []
         for blk, de in zip(blocks, deblocks):
-            convs, mods, i = [], list(blk), 0
-            while i < len(mods):
-                zpad = (0, 0, 0, 0)
-                if isinstance(mods[i], nn.ZeroPad2d):
-                    zpad, i = tuple(int(v) for v in mods[i].padding), i + 1         # (left, right, top, bottom)
-                conv, bn = mods[i], mods[i + 1]
-                assert isinstance(conv, nn.Conv2d) and isinstance(bn, nn.BatchNorm2d) and isinstance(mods[i + 2], nn.ReLU)
-                assert conv.padding_mode == "zeros" and not isinstance(conv.padding, str), "FoldedBEVBackbone: explicit zero padding only"
-                w, b = _fold(conv.weight, bn, 0, conv.bias)
-                # a symmetric ZeroPad2d is the conv's own zero padding (no padded copy); anything else stays a separate F.pad
-                pad, zp = tuple(int(v) for v in conv.padding), None
-                if zpad[0] == zpad[1] >= 0 and zpad[2] == zpad[3] >= 0:
-                    pad = (pad[0] + zpad[2], pad[1] + zpad[0])
-                else:
-                    zp = zpad
-                plain = tuple(conv.dilation) == (1, 1) and conv.groups == 1 and zp is None
-                # stride-1 3x3 layers (LAYER_NUMS per block, base_bev_backbone.py:40-45; SECOND's first block opens with one too):
-                # Winograd on the matrix cores with shift + ReLU in the kernel (csrc/wino43_conv.hip F(4x4, 3x3), csrc/wino_conv.hip F(2x2, 3x3))
+            layers = parse_block(blk)
+            assert layers is not None, "FoldedBEVBackbone: blocks must be [ZeroPad2d] Conv2d BatchNorm2d ReLU groups"
+            convs = []
+            for l in layers:
+                assert l.pad is not None, "FoldedBEVBackbone: explicit zero padding only"
+                w, b = _fold(l.conv.weight, l.bn, 0, l.conv.bias)
                 packed = None
-                if (_WINO[0] and w.is_cuda and plain and tuple(conv.kernel_size) == (3, 3) and tuple(conv.stride) == (1, 1)
-                        and pad == (1, 1) and wino.supported(w.shape[1], w.shape[0])):
-                    packed = wino.pack_auto(w)        # F(4x4, 3x3) where supported (Cout % 64 == 0), else F(2x2, 3x3)
-                convs.append(_FoldedConv(w.contiguous(memory_format=torch.channels_last), b, tuple(conv.stride), pad, packed,
-                                         tuple(conv.dilation), conv.groups, zp))
-                i += 3
+                if _WINO[0] and w.is_cuda and l.plain3x3 and wino.supported(w.shape[1], w.shape[0]):
+                    packed = wino.pack_auto(w)        # Winograd on the matrix cores, shift + ReLU in the kernel (csrc/wino43_conv.hip, csrc/wino_conv.hip)
+                convs.append(FoldedConv(w.contiguous(memory_format=torch.channels_last), b, tuple(l.conv.stride), l.pad,
+                                        tuple(l.conv.dilation), l.conv.groups, l.zero_pad, packed))
             up, bn = de[0], de[1]
             assert tuple(up.dilation) == (1, 1) and up.groups == 1 and up.padding_mode == "zeros", \
                 "FoldedBEVBackbone: deblocks with dilation, groups or non-zero padding modes are not supported"
             if isinstance(up, nn.ConvTranspose2d):
                 w, b = _fold(up.weight, bn, 1, up.bias)
-                if tuple(up.kernel_size) == tuple(up.stride) and up.stride[0] == up.stride[1] and \
+                s = up.stride[0]
+                if tuple(up.kernel_size) == tuple(up.stride) and s == up.stride[1] and \
                         tuple(up.padding) == (0, 0) and tuple(up.output_padding) == (0, 0):
                     # kernel == stride: every input pixel owns its own s x s output patch -> a plain GEMM
                     w_kn = w.permute(0, 2, 3, 1).reshape(w.shape[0], -1).contiguous()
-                    upc = ("gemm", w_kn, b, up.stride[0])
-                    if (_DECONV[0] and w.is_cuda and up.stride[0] > 1 and deconv_supported(w_kn.shape[0], up.stride[0], b.numel())):
-                        upc = ("deconv_mfma", (deconv_pack(w_kn), w_kn), b, up.stride[0])   # csrc/deconv_gemm.hip (+ the plain weight: maps of 2 GiB and more take the two-step path)
+                    upc = FoldedDeblock("gemm", w_kn, None, b, s, ())
+                    if _DECONV[0] and w.is_cuda and s > 1 and deconv_supported(w_kn.shape[0], s, b.numel()):
+                        upc = upc._replace(kind="deconv_mfma", packed=deconv_pack(w_kn))   # csrc/deconv_gemm.hip (maps of 2 GiB and more: the plain weight)
                 else:
-                    upc = ("deconv", w.contiguous(memory_format=torch.channels_last), b, (up.stride, up.padding, up.output_padding))
+                    upc = FoldedDeblock("deconv", w.contiguous(memory_format=torch.channels_last), None, b, 0,
+                                        (up.stride, up.padding, up.output_padding))
             else:   # stride < 1 in the reference config: a strided Conv2d (base_bev_backbone.py:60-69)
                 w, b = _fold(up.weight, bn, 0, up.bias)
-                upc = ("conv", w.contiguous(memory_format=torch.channels_last), b, (up.stride, up.padding))
+                upc = FoldedDeblock("conv", w.contiguous(memory_format=torch.channels_last), None, b, 0, (up.stride, up.padding))
             self.stages.append((convs, upc))
-        self.up_channels = [s[1][2].numel() for s in self.stages]
+        self.up_channels = [up.shift.numel() for _, up in self.stages]
         for h in heads:
             assert tuple(h.kernel_size) == (1, 1) and tuple(h.stride) == (1, 1)
         self.head_split = [h.weight.shape[0] for h in heads]
@@ -267,7 +311,7 @@ class FoldedBEVBackbone:
         # the first layer as a sparse implicit GEMM over the pillars (csrc/pillar.hip lidar_pillar_conv_table): (k*k, Cin, Cout) weights
         self._first_sparse = None
         c0 = self.stages[0][0][0]
-        w0, b0, st0, pad0, _ = c0
+        w0, b0, st0, pad0 = c0.weight, c0.shift, c0.stride, c0.pad
         k0 = w0.shape[2]
         if (w0.is_cuda and w0.shape[2] == w0.shape[3] and st0[0] == st0[1] and pad0[0] == pad0[1] and k0 * k0 <= 31
                 and c0.dilation == (1, 1) and c0.groups == 1 and c0.zero_pad is None):   # (the neighbour table knows one stride and one symmetric pad)
@@ -294,58 +338,47 @@ class FoldedBEVBackbone:
         """-> the concatenated upsampled map (B, sum(up_channels), H, W), channels-last.  first_done: `canvas` is already the output
         of the first layer (first_layer_from_pillars)."""
         x, cat, off = canvas, None, 0
-        for si, (convs, (kind, uw, ub, ustride)) in enumerate(self.stages):
+        for si, (convs, up) in enumerate(self.stages):
             for ci, cv in enumerate(convs):
                 if first_done and si == 0 and ci == 0:
                     continue
-                w, b, stride, pad, packed = cv
-                if packed is not None and _WINO[0] and x.is_contiguous(memory_format=torch.channels_last):
-                    x = wino.conv3x3_auto(x, packed, w.shape[0], b, True)
+                if cv.wino is not None and _WINO[0] and x.is_contiguous(memory_format=torch.channels_last):
+                    x = wino.conv3x3_auto(x, cv.wino, cv.weight.shape[0], cv.shift, True)
                     continue
                 if cv.zero_pad is not None:
                     x = F.pad(x, cv.zero_pad)
-                x = F.conv2d(x, w, None, stride, pad, cv.dilation, cv.groups)
-                if not x.is_contiguous(memory_format=torch.channels_last):
-                    x = x.contiguous(memory_format=torch.channels_last)
-                bias_act_(x, b)
+                x = _cl(F.conv2d(x, cv.weight, None, cv.stride, cv.pad, cv.dilation, cv.groups))
+                bias_act_(x, cv.shift)
             B, _, h, w = x.shape
             y = None
-            if kind == "deconv_mfma":
-                oh, ow = h * ustride, w * ustride
-                if not deconv_fits(B, x.shape[1], h, w, ustride, sum(self.up_channels)):
-                    kind, uw = "gemm", uw[1]
-                    y = rows_gemm(x.permute(0, 2, 3, 1).reshape(B * h * w, -1), uw)
-                else:
-                    uw = uw[0]
-            elif kind == "gemm":
-                oh, ow = h * ustride, w * ustride
-                if not (ustride == 1 and _LT_GEMM[0]):
-                    y = rows_gemm(x.permute(0, 2, 3, 1).reshape(B * h * w, -1), uw)  # the NHWC map IS the row-major A
-            else:
-                y = F.conv_transpose2d(x, uw, None, *ustride) if kind == "deconv" else F.conv2d(x, uw, None, *ustride)
-                if not y.is_contiguous(memory_format=torch.channels_last):
-                    y = y.contiguous(memory_format=torch.channels_last)
-                oh, ow = y.shape[2], y.shape[3]
+            if up.kind in ("deconv", "conv"):            # the library convolution; its epilogue follows once the concat map exists
+                y = _cl((F.conv_transpose2d if up.kind == "deconv" else F.conv2d)(x, up.weight, None, *up.args))
+            oh, ow = (h * up.stride, w * up.stride) if y is None else y.shape[2:]
             if cat is None:
                 shape = (B, sum(self.up_channels), oh, ow)
                 cat = self._cats.get(slot)
                 if cat is None or cat.shape != shape or cat.device != x.device:
                     cat = self._cats[slot] = torch.empty(shape, dtype=torch.float32, device=x.device,
                                                          memory_format=torch.channels_last)
-            if kind == "gemm" and y is None:
-                # stride 1: GEMM + shift + ReLU + concat in ONE hipBLASLt call writing with the map's row pitch
-                if not gemm_bias_act_into_(x, uw, ub, cat, off):
-                    _LT_GEMM[0] = False                                             # not available here: the two-step path from now on
-                    y = rows_gemm(x.permute(0, 2, 3, 1).reshape(B * h * w, -1), uw)
-            if kind == "deconv_mfma":
-                deconv_gemm_into_(x, uw, ub, ustride, cat, off)
-            elif kind == "gemm":
-                if y is not None:
-                    bias_act_upsample_(y, ub, B, h, w, ustride, cat, off)
+            if y is not None:
+                bias_act_(y, up.shift, out=cat, out_offset=off)
             else:
-                bias_act_(y, ub, out=cat, out_offset=off)
-            off += ub.numel()
+                self._deblock_gemm(x, up, cat, off)
+            off += up.shift.numel()
         return cat
+
+    def _deblock_gemm(self, x, up, cat, off):
+        """a kernel == stride deblock into its channel slice of `cat`, on the first route that applies"""
+        B, K, h, w = x.shape
+        if up.kind == "deconv_mfma" and deconv_fits(B, K, h, w, up.stride, cat.shape[1]):
+            return deconv_gemm_into_(x, up.packed, up.shift, up.stride, cat, off)                 # one fused kernel
+        if up.kind == "gemm" and up.stride == 1 and _LT_GEMM[0]:
+            # stride 1: GEMM + shift + ReLU + concat in ONE hipBLASLt call writing with the map's row pitch
+            if gemm_bias_act_into_(x, up.weight, up.shift, cat, off):
+                return cat
+            _LT_GEMM[0] = False                                                                   # not available here: the two-step path from now on
+        y = rows_gemm(x.permute(0, 2, 3, 1).reshape(B * h * w, -1), up.weight)                    # the NHWC map IS the row-major A
+        return bias_act_upsample_(y, up.shift, B, h, w, up.stride, cat, off)                      # + shift, ReLU, pixel shuffle
 
     def stale(self):
         return params_key(self.sources) != self.source_key

@@ -24,6 +24,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib, wino, workspace
+from .bev_backbone import _cl, block_layer, parse_block
 
 _MAX_SEG = 4          # inputs of one fused call (csrc/bn_train.hip BT_MAX_SEG)
 _MAX_C = 1024         # channels of one input (BT_MAX_C)
@@ -41,17 +42,6 @@ def bn_supported(bn, channels=None):
             and c == bn.num_features and c % 4 == 0 and 4 <= c <= _MAX_C)
 
 
-def _nhwc(t, what):
-    """-> row stride (floats) of a channels-last (B, C, H, W) fp32 CUDA map or of a channel slice of one"""
-    if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 4):
-        raise _lib.LidarHipError(f"{what}: expected a 4-d float32 CUDA (ROCm) tensor, got {t.dtype} {tuple(t.shape)} on {t.device}")
-    B, Cc, H, W = t.shape
-    ld = t.stride(3)
-    if t.stride() != (H * W * ld, 1, W * ld, ld) or ld < Cc:
-        raise _lib.LidarHipError(f"{what}: expected a channels-last map (or a channel slice of one), got strides {t.stride()}")
-    return ld
-
-
 def _segments(zs):
     zs = list(zs)
     if not 1 <= len(zs) <= _MAX_SEG:
@@ -59,7 +49,7 @@ def _segments(zs):
     B, _, H, W = zs[0].shape
     lds = []
     for z in zs:
-        lds.append(_nhwc(z, "bn_relu input"))
+        lds.append(_lib.nhwc_ld(z, "bn_relu input"))
         if z.shape[0] != B or tuple(z.shape[2:]) != (H, W):
             raise _lib.LidarHipError("bn_relu: every input must have the same batch and spatial shape")
         if z.shape[1] % 4 or not 4 <= z.shape[1] <= _MAX_C:
@@ -81,11 +71,8 @@ def bn_relu_forward(zs, gamma, beta, eps, out=None, out_offset=0):
         raise _lib.LidarHipError(f"bn_relu_forward: gamma / beta must hold {ctot} values")
     z0 = zs[0]
     B, _, H, W = z0.shape
-    if out is None:
-        out, out_offset = torch.empty((B, ctot, H, W), dtype=torch.float32, device=z0.device, memory_format=torch.channels_last), 0
-    elif out.shape[0] != B or tuple(out.shape[2:]) != (H, W) or not 0 <= out_offset <= out.shape[1] - ctot:
-        raise _lib.LidarHipError("bn_relu_forward: out must be (B, >= out_offset + sum C, H, W)")
-    y_ld = _nhwc(out, "bn_relu_forward out")
+    out, out_offset = _lib.nhwc_out("bn_relu_forward", B, (H, W), ctot, z0.device, out, out_offset, sliced=True)
+    y_ld = out.stride(3)
     dev = z0.device
     stats = torch.empty(2 * ctot, dtype=torch.float64, device=dev)
     scale_shift = torch.empty(2 * ctot, dtype=torch.float32, device=dev)
@@ -104,7 +91,7 @@ def bn_relu_backward(zs, grad_y, gamma, stats, scale_shift, grad_offset=0):
     grad_offset) -> ([dz per input, laid out like its z: a channel slice of a z-wide buffer when z is a slice], d_gamma, d_beta)"""
     _lib.require_cuda(gamma, scale_shift)
     n, ptrs, lds, offs, cs, rows, ctot = _segments(zs)
-    g_ld = _nhwc(grad_y, "bn_relu_backward grad")
+    g_ld = _lib.nhwc_ld(grad_y, "bn_relu_backward grad")
     if grad_y.shape[0] != zs[0].shape[0] or grad_y.shape[2:] != zs[0].shape[2:] or not 0 <= grad_offset <= grad_y.shape[1] - ctot:
         raise _lib.LidarHipError("bn_relu_backward: the gradient must be (B, >= grad_offset + sum C, H, W)")
     dzs = []
@@ -122,10 +109,6 @@ def bn_relu_backward(zs, grad_y, gamma, stats, scale_shift, grad_offset=0):
                                               _lib.ptr(stats), _lib.ptr(scale_shift), dptrs, _lib.ptr(d_gamma), _lib.ptr(d_beta),
                                               _lib.ptr(ws), wsb, _lib.stream()), "lidar_bn_relu_train_backward")
     return dzs, d_gamma, d_beta
-
-
-def _cl(t):
-    return t if t.is_contiguous(memory_format=torch.channels_last) else t.contiguous(memory_format=torch.channels_last)
 
 
 class _BNReLUTrain(torch.autograd.Function):
@@ -184,10 +167,10 @@ def wino_train_supported(cin, cout):
 
 
 def _wino(x, w):
-    """conv3x3(x, w, padding=1) with no bias or ReLU, routed like wino.conv3x3_auto: F(4x4, 3x3) where csrc/wino43_conv.hip takes
-    the layer and the map fits its 32-bit offsets, F(2x2, 3x3) otherwise (only the filters the chosen kernel reads are packed)"""
-    cout = w.shape[0]
-    if wino._F43[0] and wino.supported43(w.shape[1], cout) and wino.f43_fits(x.shape, cout):
+    """conv3x3(x, w, padding=1) with no bias or ReLU on the kernel wino.kernel_for names for this layer and map (the filters are
+    repacked every step: only those the chosen kernel reads)"""
+    cout, cin = w.shape[:2]
+    if wino.kernel_for(cin, cout, x.shape) == "f43":
         return wino.conv3x3_f43(x, wino.pack_weights43(w), cout, None, relu=False)
     return wino.conv3x3(x, wino.pack_weights(w), cout, None, relu=False)
 
@@ -243,27 +226,29 @@ def conv3x3_train(x, weight, wgrad="library"):
     _check_wgrad(wgrad, "conv3x3_train")
     if not wino_train_supported(weight.shape[1], weight.shape[0]):
         raise _lib.LidarHipError(f"conv3x3_train: (Cout, Cin) = {tuple(weight.shape[:2])} is not taken by the Winograd kernels in both directions")
-    if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous(memory_format=torch.channels_last)):
-        raise _lib.LidarHipError("conv3x3_train: expected a channels-last float32 CUDA tensor")
+    _lib.require_nhwc(x, "conv3x3_train")
     return _WinoConv3x3Train.apply(x, weight, wgrad)
 
 
 # ------------------------------------------------------------------ the backbone
-def conv_route(conv, bn, zero_pad=(0, 0, 0, 0)):
-    """how TrainBEVBackbone runs one Conv2d -> BatchNorm2d -> ReLU layer (preceded by ZeroPad2d(zero_pad), or not): "wino" (Winograd
-    forward and input gradient + fused BN / ReLU), "conv" (stock F.conv2d + fused BN / ReLU) or "stock" (the modules themselves).
-    Pure host."""
-    if not (isinstance(conv, nn.Conv2d) and type(conv) is nn.Conv2d and bn_supported(bn, conv.out_channels)):
+def _route(l):
+    """conv_route of a bev_backbone.BlockLayer"""
+    conv = l.conv
+    if (type(conv) is not nn.Conv2d or not bn_supported(l.bn, conv.out_channels) or l.pad is None or l.zero_pad is not None
+            or tuple(conv.dilation) != (1, 1) or conv.groups != 1):
         return "stock"
-    zl, zr, zt, zb = (int(v) for v in zero_pad)
-    if (conv.padding_mode != "zeros" or isinstance(conv.padding, str) or tuple(conv.dilation) != (1, 1) or conv.groups != 1
-            or zl != zr or zt != zb or min(zero_pad) < 0):
-        return "stock"
-    pad = (conv.padding[0] + zt, conv.padding[1] + zl)
-    if (tuple(conv.kernel_size) == (3, 3) and tuple(conv.stride) == (1, 1) and pad == (1, 1) and conv.bias is None
-            and wino_train_supported(conv.in_channels, conv.out_channels)):
+    if l.plain3x3 and conv.bias is None and wino_train_supported(conv.in_channels, conv.out_channels):
         return "wino"
     return "conv"
+
+
+def conv_route(conv, bn, zero_pad=(0, 0, 0, 0)):
+    """how TrainBEVBackbone runs one Conv2d -> BatchNorm2d -> ReLU layer (preceded by ZeroPad2d(zero_pad), or not): "wino" (Winograd
+    forward and input gradient + fused BN / ReLU), "conv" (stock F.conv2d on the folded padding + fused BN / ReLU) or "stock" (the
+    modules themselves).  Pure host."""
+    if not isinstance(conv, nn.Conv2d):
+        return "stock"
+    return _route(block_layer(nn.ZeroPad2d(tuple(int(v) for v in zero_pad)), conv, bn))
 
 
 def deblock_route(de):
@@ -272,23 +257,6 @@ def deblock_route(de):
     if len(mods) != 3 or not isinstance(mods[2], nn.ReLU) or not isinstance(mods[0], (nn.ConvTranspose2d, nn.Conv2d)):
         return "stock"
     return "fused" if bn_supported(mods[1], mods[0].out_channels) else "stock"
-
-
-def _parse_block(blk):
-    """Sequential of [ZeroPad2d] Conv2d BatchNorm2d ReLU ... -> [(zero_pad, conv, bn, relu)], or None for any other structure"""
-    mods, out, i = list(blk), [], 0
-    while i < len(mods):
-        zp = (0, 0, 0, 0)
-        if isinstance(mods[i], nn.ZeroPad2d):
-            zp, i = tuple(int(v) for v in mods[i].padding), i + 1
-        if i + 3 > len(mods):
-            return None
-        conv, bn, act = mods[i], mods[i + 1], mods[i + 2]
-        if not (isinstance(conv, nn.Conv2d) and isinstance(bn, nn.BatchNorm2d) and isinstance(act, nn.ReLU)):
-            return None
-        out.append((zp, conv, bn, act))
-        i += 3
-    return out
 
 
 class TrainBEVBackbone:
@@ -303,16 +271,8 @@ class TrainBEVBackbone:
         self.blocks, self.deblocks = list(blocks), list(deblocks)
         self.plan = []
         for blk in self.blocks:
-            layers = _parse_block(blk)
-            if layers is None:
-                self.plan.append(("stock", blk))
-                continue
-            steps = []
-            for zp, conv, bn, act in layers:
-                route = conv_route(conv, bn, zp)
-                pad = (conv.padding[0] + zp[2], conv.padding[1] + zp[0]) if route != "stock" else None
-                steps.append((route, zp, pad, conv, bn, act))
-            self.plan.append(("layers", steps))
+            layers = parse_block(blk)
+            self.plan.append(("stock", blk) if layers is None else ("layers", [(_route(l), l) for l in layers]))
         n = len(self.blocks)
         self.de_routes = [deblock_route(de) for de in self.deblocks[:n]]
         self.extra = self.deblocks[n] if len(self.deblocks) > n else None       # a final deblock on the concatenated map (stock)
@@ -322,31 +282,28 @@ class TrainBEVBackbone:
 
     def routes(self):
         """-> [[route of each layer] per block], [route of each deblock]  (a block of unknown structure: ["stock"])"""
-        return ([[s[0] for s in steps] if kind == "layers" else ["stock"] for kind, steps in self.plan], list(self.de_routes))
+        return ([[route for route, _ in steps] if kind == "layers" else ["stock"] for kind, steps in self.plan], list(self.de_routes))
 
     def wgrad_routes(self):
         """-> [[who computes each layer's weight gradient] per block]: "wino" (csrc/wino43_wgrad.hip), "library" (MIOpen), or None for
         a layer that is not on the Winograd route at all (routes() != "wino": autograd's own backward).  From the widths alone; a
         "wino" layer whose map does not fit the kernel's 32-bit offsets (wino.wgrad43_fits) still takes the library at run time."""
-        return [[(wgrad_route(s[3].in_channels, s[3].out_channels, self.wgrad) if s[0] == "wino" else None) for s in steps]
+        return [[(wgrad_route(l.conv.in_channels, l.conv.out_channels, self.wgrad) if route == "wino" else None) for route, l in steps]
                 if kind == "layers" else [None] for kind, steps in self.plan]
 
     def _layer(self, step, x):
-        route, zp, pad, conv, bn, act = step
+        route, l = step
         if route == "stock":
-            if zp != (0, 0, 0, 0):
-                x = F.pad(x, zp)
-            return _cl(act(bn(conv(x))))
+            return _cl(l.act(l.bn(l.conv(x if l.zpad is None else l.zpad(x)))))
         if route == "wino":
-            z = conv3x3_train(x, conv.weight, self.wgrad)
+            z = conv3x3_train(x, l.conv.weight, self.wgrad)
         else:
-            z = _cl(F.conv2d(x, conv.weight, conv.bias, conv.stride, pad))
-        return bn_relu_train(z, bn)
+            z = _cl(F.conv2d(x, l.conv.weight, l.conv.bias, l.conv.stride, l.pad))
+        return bn_relu_train(z, l.bn)
 
     def __call__(self, x, return_blocks=False):
         """x (B, C, H, W) channels-last fp32 CUDA -> the concatenated map; return_blocks: (map, [each block's output])"""
-        if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and x.is_contiguous(memory_format=torch.channels_last)):
-            raise _lib.LidarHipError("TrainBEVBackbone: expected a channels-last float32 CUDA (ROCm) map")
+        _lib.require_nhwc(x, "TrainBEVBackbone")
         feats = []
         for kind, steps in self.plan:
             if kind == "stock":

@@ -23,6 +23,7 @@ import torch.nn as nn
 
 from . import anchor_loss, anchor_post, pillar_ops, synth
 from .bev_backbone import FoldedBEVBackbone, collect_params, params_key
+from .bev_train import TrainBEVBackbone, _check_wgrad
 from .ext import iou3d_nms_cuda
 from .voxelizer import BatchVoxelizer, grid_size_of
 
@@ -186,7 +187,10 @@ class PointPillarKITTI(nn.Module):
         for blk, de in zip(self.blocks, self.deblocks):
             x = blk(x)
             ups.append(de(x))
-        x = torch.cat(ups, dim=1)
+        return self._head_maps(torch.cat(ups, dim=1))
+
+    def _head_maps(self, x):
+        """the stock heads on the concatenated map -> cls (B, N, 3), box (B, N, 7), dirs (B, N, 2)"""
         cls = self.conv_cls(x).permute(0, 2, 3, 1).reshape(self.B, -1, self.num_class)
         box = self.conv_box(x).permute(0, 2, 3, 1).reshape(self.B, -1, 7)
         dirs = self.conv_dir_cls(x).permute(0, 2, 3, 1).reshape(self.B, -1, self.num_dir_bins)
@@ -197,19 +201,13 @@ class PointPillarKITTI(nn.Module):
         ReLU, Winograd stride-1 convolutions forward and input gradient, the deblocks' BatchNorm written straight into the
         concatenated map); the heads stay stock.  Needs the channels-last model (channels_last=True) and a channels-last canvas.
         wgrad: who computes the weight gradients of the stride-1 3x3 layers, "library" (MIOpen) or "wino" (csrc/wino43_wgrad.hip)."""
-        from .bev_train import WGRAD_OPTIONS, TrainBEVBackbone
-        if wgrad not in WGRAD_OPTIONS:
-            raise pillar_ops._lib.LidarHipError(f"PointPillarKITTI.backbone_head_train: wgrad must be one of {WGRAD_OPTIONS}, got {wgrad!r}")
+        _check_wgrad(wgrad, "PointPillarKITTI.backbone_head_train")
         if not self.channels_last:
             raise pillar_ops._lib.LidarHipError("PointPillarKITTI.backbone_head_train needs the channels-last model (channels_last=True)")
         key = "_bev_train" if wgrad == "library" else "_bev_train_" + wgrad
         if self.__dict__.get(key) is None:
             self.__dict__[key] = TrainBEVBackbone(self.blocks, self.deblocks, wgrad=wgrad)
-        x = self.__dict__[key](canvas)
-        cls = self.conv_cls(x).permute(0, 2, 3, 1).reshape(self.B, -1, self.num_class)
-        box = self.conv_box(x).permute(0, 2, 3, 1).reshape(self.B, -1, 7)
-        dirs = self.conv_dir_cls(x).permute(0, 2, 3, 1).reshape(self.B, -1, self.num_dir_bins)
-        return cls, box, dirs
+        return self._head_maps(self.__dict__[key](canvas))
 
     def rpn_loss(self, head_out, gt_boxes):
         """the training loss of this head: (cls_loss, loc_loss, dir_loss) of AnchorHeadTemplate.get_loss (pointpillar.yaml weights) for
@@ -230,8 +228,7 @@ class PointPillarKITTI(nn.Module):
             raise pillar_ops._lib.LidarHipError("PointPillarKITTI.train_loss needs train mode (call .train() first)")
         if backbone not in ("stock", "fused"):
             raise pillar_ops._lib.LidarHipError(f"PointPillarKITTI.train_loss: backbone must be 'stock' or 'fused', got {backbone!r}")
-        if wgrad not in ("library", "wino"):
-            raise pillar_ops._lib.LidarHipError(f"PointPillarKITTI.train_loss: wgrad must be 'library' or 'wino', got {wgrad!r}")
+        _check_wgrad(wgrad, "PointPillarKITTI.train_loss")
         if backbone == "fused" and not self.channels_last:
             raise pillar_ops._lib.LidarHipError("PointPillarKITTI.train_loss(backbone='fused') needs the channels-last model")
         with torch.no_grad():   # fresh voxel buffers: the PFN's backward reads them after the next step may have voxelised

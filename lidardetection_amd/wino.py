@@ -34,19 +34,14 @@ def conv3x3(x, packed, cout, bias=None, relu=True, out=None, out_offset=0):
     """x (B, Cin, H, W) channels-last fp32 -> act(conv3x3(x, w, padding=1) + bias) as a channels-last (B, cout, H, W) tensor, or
     into channels [out_offset, out_offset + cout) of the channels-last `out` (B, C_out, H, W)."""
     _lib.require_cuda(packed, bias)
-    if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and x.is_contiguous(memory_format=torch.channels_last)):
-        raise _lib.LidarHipError("wino.conv3x3: expected a channels-last float32 CUDA tensor")
+    _lib.require_nhwc(x, "wino.conv3x3")
     B, cin, H, W = x.shape
     L = _lib.lib()
     if packed.numel() != L.lidar_wino_packed_floats(cin, cout) or packed.numel() == 0:
         raise _lib.LidarHipError("wino.conv3x3: packed filters do not match (Cin, Cout)")
     if bias is not None and bias.numel() != cout:
         raise _lib.LidarHipError("wino.conv3x3: bias must hold Cout values")
-    if out is None:
-        out, out_offset = torch.empty((B, cout, H, W), dtype=torch.float32, device=x.device, memory_format=torch.channels_last), 0
-    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous(memory_format=torch.channels_last)
-              and out.shape[0] == B and tuple(out.shape[2:]) == (H, W) and 0 <= out_offset and out_offset + cout <= out.shape[1]):
-        raise _lib.LidarHipError("wino.conv3x3: output must be channels-last (B, C_out, H, W) with room for the slice")
+    out, out_offset = _lib.nhwc_out("wino.conv3x3", B, (H, W), cout, x.device, out, out_offset)
     _lib.check(L.lidar_wino_conv3x3_nhwc(_lib.ptr(x), B, H, W, cin, _lib.ptr(packed), _lib.ptr(bias), int(bool(relu)), int(cout),
                                          _lib.ptr(out), out.shape[1], int(out_offset), _lib.stream()), "lidar_wino_conv3x3_nhwc")
     return out
@@ -74,8 +69,7 @@ def pack_weights43(w):
 def conv3x3_f43(x, packed, cout, bias=None, relu=True, out=None, out_offset=0, cin=None):
     """conv3x3 through the F(4x4, 3x3) kernel.  cin: the layer reads channels [0, cin) of x (default: all of them)."""
     _lib.require_cuda(packed, bias)
-    if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and x.is_contiguous(memory_format=torch.channels_last)):
-        raise _lib.LidarHipError("wino.conv3x3_f43: expected a channels-last float32 CUDA tensor")
+    _lib.require_nhwc(x, "wino.conv3x3_f43")
     B, in_c, H, W = x.shape
     cin = in_c if cin is None else int(cin)
     L = _lib.lib()
@@ -83,24 +77,10 @@ def conv3x3_f43(x, packed, cout, bias=None, relu=True, out=None, out_offset=0, c
         raise _lib.LidarHipError("wino.conv3x3_f43: packed filters do not match (Cin, Cout)")
     if bias is not None and bias.numel() != cout:
         raise _lib.LidarHipError("wino.conv3x3_f43: bias must hold Cout values")
-    if out is None:
-        out, out_offset = torch.empty((B, cout, H, W), dtype=torch.float32, device=x.device, memory_format=torch.channels_last), 0
-    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous(memory_format=torch.channels_last)
-              and out.shape[0] == B and tuple(out.shape[2:]) == (H, W) and 0 <= out_offset and out_offset + cout <= out.shape[1]):
-        raise _lib.LidarHipError("wino.conv3x3_f43: output must be channels-last (B, C_out, H, W) with room for the slice")
+    out, out_offset = _lib.nhwc_out("wino.conv3x3_f43", B, (H, W), cout, x.device, out, out_offset)
     _lib.check(L.lidar_wino43_conv3x3_nhwc(_lib.ptr(x), B, H, W, cin, in_c, _lib.ptr(packed), _lib.ptr(bias), int(bool(relu)), int(cout),
                                            _lib.ptr(out), out.shape[1], int(out_offset), _lib.stream()), "lidar_wino43_conv3x3_nhwc")
     return out
-
-
-def pack_auto(w):
-    """-> [kind, packed filters, weight, F(2x2) filters]: F(4x4, 3x3) where csrc/wino43_conv.hip takes the layer (and LIDAR_WINO_F43
-    != 0), else F(2x2, 3x3).  An "f43" entry carries the F(2x2, 3x3) filters too (16 Cin Cout more floats), packed here on the
-    caller's stream: a map too large for the F(4x4) kernel's 32-bit byte offsets (f43_fits) is served by F(2x2), and filters packed
-    on first need would be written on whichever stream met that map first while another stream may already read them."""
-    if _F43[0] and supported43(w.shape[1], w.shape[0]):
-        return ["f43", pack_weights43(w), w.detach(), pack_weights(w)]
-    return ["f23", pack_weights(w), None]
 
 
 # largest map (input or output, bytes) the F(4x4, 3x3) kernel addresses: it stores with 32-bit byte offsets
@@ -117,22 +97,35 @@ def f43_fits(x_shape, cout, out=None):
     return B * cin * H * W * 4 < _F43_MAX_BYTES[0] and out_elems * 4 < _F43_MAX_BYTES[0]
 
 
+def kernel_for(cin, cout, x_shape=None, out=None):
+    """which kernel runs a (Cin -> Cout) layer: "f43" (csrc/wino43_conv.hip) where LIDAR_WINO_F43 != 0, the kernel takes the widths
+    and, for a map of shape x_shape (written into `out` when given), the map fits its 32-bit byte offsets (f43_fits); else "f23"
+    (csrc/wino_conv.hip).  x_shape=None: the widths alone, before any map is known.  Pure host."""
+    return "f43" if _F43[0] and supported43(cin, cout) and (x_shape is None or f43_fits(x_shape, cout, out)) else "f23"
+
+
+def pack_auto(w):
+    """-> [kind, packed filters, weight, F(2x2) filters]: the filters of kernel_for(Cin, Cout).  An "f43" entry carries the
+    F(2x2, 3x3) filters too (16 Cin Cout more floats), packed here on the caller's stream: a map too large for the F(4x4) kernel's
+    32-bit byte offsets (f43_fits) is served by F(2x2), and filters packed on first need would be written on whichever stream met
+    that map first while another stream may already read them."""
+    if kernel_for(w.shape[1], w.shape[0]) == "f43":
+        return ["f43", pack_weights43(w), w.detach(), pack_weights(w)]
+    return ["f23", pack_weights(w), None]
+
+
 def conv3x3_auto(x, packed, cout, bias=None, relu=True, out=None, out_offset=0):
-    """conv3x3 with the filters of pack_auto"""
-    kind, p = packed[0], packed[1]
-    if kind == "f43":
-        if f43_fits(x.shape, cout, out):
-            return conv3x3_f43(x, p, cout, bias, relu, out, out_offset)
-        p = packed[3]                                  # oversize map: F(2x2)
-    return conv3x3(x, p, cout, bias, relu, out, out_offset)
+    """conv3x3 with the filters of pack_auto: the kernel kernel_for names for this map, among those the filters were packed for"""
+    if packed[0] == "f43" and kernel_for(x.shape[1], cout, x.shape, out) == "f43":
+        return conv3x3_f43(x, packed[1], cout, bias, relu, out, out_offset)
+    return conv3x3(x, packed[3 if packed[0] == "f43" else 1], cout, bias, relu, out, out_offset)   # ("f43" entry, oversize map: its F(2x2) filters)
 
 
 def conv3x3_grouped_compact(x, packed, group_cin, couts, bias=None, relu=False, tables=None):
     """conv3x3_grouped with only the REAL output channels written: -> (B, sum(couts), H, W) channels-last, group g at channels
     [sum(couts[:g]), + couts[g]).  tables = (grp_cout, grp_ooff) device int32 tensors from a previous call (returned as second value)."""
     _lib.require_cuda(packed, bias)
-    if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and x.is_contiguous(memory_format=torch.channels_last)):
-        raise _lib.LidarHipError("wino.conv3x3_grouped_compact: expected a channels-last float32 CUDA tensor")
+    _lib.require_nhwc(x, "wino.conv3x3_grouped_compact")
     B, C, H, W = x.shape
     n = len(couts)
     L = _lib.lib()
@@ -146,7 +139,7 @@ def conv3x3_grouped_compact(x, packed, group_cin, couts, bias=None, relu=False, 
             offs.append(offs[-1] + int(c))
         tables = (torch.tensor([int(c) for c in couts], dtype=torch.int32, device=x.device), torch.tensor(offs, dtype=torch.int32, device=x.device))
     ctot = int(sum(couts))
-    out = torch.empty((B, ctot, H, W), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+    out, _ = _lib.nhwc_out("wino.conv3x3_grouped_compact", B, (H, W), ctot, x.device)
     _lib.check(L.lidar_wino_conv3x3_grouped_compact_nhwc(_lib.ptr(x), B, H, W, C, int(group_cin), n, _lib.ptr(packed), _lib.ptr(bias),
                                                          int(bool(relu)), _lib.ptr(tables[0]), _lib.ptr(tables[1]), _lib.ptr(out), ctot, 0,
                                                          _lib.stream()), "lidar_wino_conv3x3_grouped_compact_nhwc")
@@ -158,8 +151,7 @@ def conv3x3_grouped(x, packed, group_cin, n_groups, bias=None, relu=False, out=N
     channels-last x (B, C >= n_groups * group_cin, H, W) and writes channels [32 g, 32 g + 32) of the result (B, 32 n_groups, H, W).
     packed = pack_weights of the stacked (32 n_groups, group_cin, 3, 3) filters (groups with fewer outputs: zero rows)."""
     _lib.require_cuda(packed, bias)
-    if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and x.is_contiguous(memory_format=torch.channels_last)):
-        raise _lib.LidarHipError("wino.conv3x3_grouped: expected a channels-last float32 CUDA tensor")
+    _lib.require_nhwc(x, "wino.conv3x3_grouped")
     B, C, H, W = x.shape
     cout = 32 * int(n_groups)
     L = _lib.lib()
@@ -167,11 +159,7 @@ def conv3x3_grouped(x, packed, group_cin, n_groups, bias=None, relu=False, out=N
         raise _lib.LidarHipError("wino.conv3x3_grouped: groups / packed filters do not match the input")
     if bias is not None and bias.numel() != cout:
         raise _lib.LidarHipError("wino.conv3x3_grouped: bias must hold 32 * n_groups values")
-    if out is None:
-        out, out_offset = torch.empty((B, cout, H, W), dtype=torch.float32, device=x.device, memory_format=torch.channels_last), 0
-    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous(memory_format=torch.channels_last)
-              and out.shape[0] == B and tuple(out.shape[2:]) == (H, W) and 0 <= out_offset and out_offset + cout <= out.shape[1]):
-        raise _lib.LidarHipError("wino.conv3x3_grouped: output must be channels-last (B, C_out, H, W) with room for the slice")
+    out, out_offset = _lib.nhwc_out("wino.conv3x3_grouped", B, (H, W), cout, x.device, out, out_offset)
     _lib.check(L.lidar_wino_conv3x3_grouped_nhwc(_lib.ptr(x), B, H, W, C, int(group_cin), int(n_groups), _lib.ptr(packed), _lib.ptr(bias),
                                                  int(bool(relu)), _lib.ptr(out), out.shape[1], int(out_offset), _lib.stream()),
                "lidar_wino_conv3x3_grouped_nhwc")
@@ -193,23 +181,12 @@ def wgrad43_fits(x_shape, cout, x_ld=None, g_ld=None):
     return (B > 0 and H > 0 and W > 0 and B * H * W * x_ld * 4 < _F43_MAX_BYTES[0] and B * H * W * g_ld * 4 < _F43_MAX_BYTES[0])
 
 
-def _nhwc_ld(t, what):
-    """-> row stride (floats) of a channels-last (B, C, H, W) fp32 CUDA map or of a channel slice of one"""
-    if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 4):
-        raise _lib.LidarHipError(f"{what}: expected a 4-d float32 CUDA (ROCm) tensor, got {t.dtype} {tuple(t.shape)} on {t.device}")
-    B, Cc, H, W = t.shape
-    ld = t.stride(3)
-    if t.stride() != (H * W * ld, 1, W * ld, ld) or ld < Cc:
-        raise _lib.LidarHipError(f"{what}: expected a channels-last map (or a channel slice of one), got strides {t.stride()}")
-    return ld
-
-
 def conv3x3_wgrad_f43(x, g):
     """the weight gradient of conv2d(x, w, stride=1, padding=1): x (B, Cin, H, W) and the output gradient g (B, Cout, H, W), both
     channels-last fp32 maps or channel slices of such maps -> dW (Cout, Cin, 3, 3) fp32, contiguous.  Winograd F(3x3, 4x4) on the
     matrix cores, partial sums over <= 512 tiles in fp32, the rest in fp64; bitwise reproducible; no host synchronisation."""
     from . import workspace
-    x_ld, g_ld = _nhwc_ld(x, "wino.conv3x3_wgrad_f43 x"), _nhwc_ld(g, "wino.conv3x3_wgrad_f43 g")
+    x_ld, g_ld = _lib.nhwc_ld(x, "wino.conv3x3_wgrad_f43 x"), _lib.nhwc_ld(g, "wino.conv3x3_wgrad_f43 g")
     B, cin, H, W = x.shape
     cout = g.shape[1]
     if g.shape[0] != B or tuple(g.shape[2:]) != (H, W) or g.device != x.device:

@@ -166,7 +166,8 @@ def test_pointpillar_kitti_bs16_timed_path_over_successive_batches(dev):
             # the stock convolution of that canvas: ZeroPad2d(1) + Conv2d(3x3, stride 2) + folded BatchNorm + ReLU
             bev = m._bev_folded()
             x1 = bev.first_layer_from_pillars(pmap)
-            w0, b0, st0, pad0, _ = bev.stages[0][0][0]
+            c0 = bev.stages[0][0][0]
+            w0, b0, st0, pad0 = c0.weight, c0.shift, c0.stride, c0.pad
             ref1 = torch.relu(torch.nn.functional.conv2d(canvas, w0, b0, st0, pad0))
             assert x1.shape == ref1.shape and x1.is_contiguous(memory_format=torch.channels_last)
             e1 = float((x1 - ref1).abs().max())

@@ -794,10 +794,11 @@ def test_folded_bev_backbone_production_routes_vs_reference_golden(dev, golden_d
     # the routes: stride-1 3x3 layers on F(4x4), deblock 1 fused, deblock 0 the stride-1 GEMM, first layer from the pillars
     for si in (0, 1):
         convs = bev.stages[si][0]
-        assert len(convs) == 2 and convs[0][2] == (2, 2) and convs[0][4] is None
-        assert convs[1][4] is not None and convs[1][4][0] == "f43" and len(convs[1][4]) == 4, si
-    assert bev.stages[1][1][0] == "deconv_mfma" and bev.stages[1][1][3] == 2
-    assert bev.stages[0][1][0] == "gemm" and bev.stages[0][1][3] == 1
+        assert len(convs) == 2 and convs[0].stride == (2, 2) and convs[0].wino is None
+        assert convs[1].wino is not None and convs[1].wino[0] == "f43" and len(convs[1].wino) == 4, si
+    (_, up0), (_, up1) = bev.stages
+    assert up1.kind == "deconv_mfma" and up1.stride == 2
+    assert up0.kind == "gemm" and up0.stride == 1
     assert bev.sparse_first_ok()
     calls = _Calls(monkeypatch, (wino, "conv3x3_f43"), (wino, "conv3x3"), (bb, "deconv_gemm_into_"), (bb, "rows_gemm"),
                    (bb, "gemm_bias_act_into_"))
@@ -862,10 +863,10 @@ def test_folded_bev_backbone_conv_settings_vs_fp64_stock(dev, golden_dir, case):
     heads = [hd.to(dev) for hd in heads]
     bev = FoldedBEVBackbone(blocks, deblocks, heads)
     convs = bev.stages[0][0]
-    assert (convs[0].zero_pad, convs[0][3], convs[1][3], convs[1].dilation, convs[1].groups) == \
+    assert (convs[0].zero_pad, convs[0].pad, convs[1].pad, convs[1].dilation, convs[1].groups) == \
         {"asymmetric_zero_pad": ((0, 1, 0, 1), (0, 0), (1, 1), (1, 1), 1), "dilation": (None, (1, 1), (2, 2), (2, 2), 1),
          "groups": (None, (1, 1), (1, 1), (1, 1), 2)}[case]                  # the settings the stage keeps
-    assert convs[1][4] is None or case == "asymmetric_zero_pad"             # no Winograd for dilation / groups
+    assert convs[1].wino is None or case == "asymmetric_zero_pad"           # no Winograd for dilation / groups
     assert bev.sparse_first_ok() == (case != "asymmetric_zero_pad")          # the neighbour table knows symmetric padding only
     tol, tol_h = 1e-4 * max(1.0, float(np.abs(want).max())), 1e-4 * max(1.0, float(want_head.abs().max()))
     with torch.no_grad():
