@@ -496,6 +496,30 @@ int lidar_deconv_pack_weights(const float *W, int K, int N, float *packed, void 
 int lidar_deconv_gemm_nhwc(const float *in, int B, int h, int w, int K, const float *packed, const float *bias, int relu, int s, int C_up,
                            float *out, int out_C, int out_off, void *stream);
 
+/* The two GRADIENTS of the same layer without bias (training; torch hands them to MIOpen) as fp32-MFMA GEMMs on the NHWC maps
+ * (csrc/deconv_train.hip).  p = (b, y, x) runs over the P = B h w input pixels; W is the module's weight in torch's own layout
+ * (K, C_up, s, s), contiguous; g (the gradient of the layer's output): (B, s h, s w) pixels of g_ld floats, channels [0, C_up).
+ *   lidar_deconv_dgrad_nhwc:  dx[p][k] = sum_{ky,kx,c} g[b][s y + ky][s x + kx][c] W[k][c][ky][kx], written at the row stride
+ *     dx_ld >= K (columns [K, dx_ld) are not touched); the reduction (s^2 C_up long) is not split: bitwise reproducible.
+ *   lidar_deconv_wgrad_nhwc:  dw[k][c][ky][kx] = sum_p x[p][k] g[b][s y + ky][s x + kx][c]; x: P pixels of x_ld floats, channels
+ *     [0, K); dw: contiguous (K, C_up, s, s), OVERWRITTEN (never read).  fp32 MFMA accumulation over at most 4096 pixels, partial sums
+ *     in ws (plain stores; its previous contents do not matter), summed in fixed order in fp64, one rounding to fp32: no float
+ *     atomics, bitwise reproducible, no host read, graph-capturable.  ws: lidar_deconv_wgrad_workspace_bytes (pure host; 0 for
+ *     unsupported or empty shapes), 16-byte aligned; LIDAR_ERR_WORKSPACE when it is missing or short.
+ * Supported (lidar_deconv_train_supported, pure host; everything else is refused with LIDAR_ERR_ARG): s in {1, 2, 4}, K % 8 == 0 in
+ * [LIDAR_DECONV_TRAIN_MIN_K, LIDAR_DECONV_TRAIN_MAX_C], C_up % 32 == 0 in [LIDAR_DECONV_TRAIN_MIN_CUP, LIDAR_DECONV_TRAIN_MAX_C].
+ * x and g are 16-byte aligned with x_ld % 4 == 0 and g_ld % 4 == 0; each map (x, g, dx at their row strides) stays below 2^31 - 1
+ * bytes.  Every argument is checked before any launch. */
+#define LIDAR_DECONV_TRAIN_MIN_K 16
+#define LIDAR_DECONV_TRAIN_MIN_CUP 32
+#define LIDAR_DECONV_TRAIN_MAX_C 512
+int lidar_deconv_train_supported(int K, int s, int C_up);
+size_t lidar_deconv_wgrad_workspace_bytes(int B, int h, int w, int K, int s, int C_up);
+int lidar_deconv_dgrad_nhwc(const float *g, int g_ld, const float *W, int B, int h, int w, int K, int s, int C_up, float *dx, int dx_ld,
+                            void *stream);
+int lidar_deconv_wgrad_nhwc(const float *x, int x_ld, const float *g, int g_ld, int B, int h, int w, int K, int s, int C_up, float *dw,
+                            void *ws, size_t ws_bytes, void *stream);
+
 /* ------------------------------------------------------------------ anchor-head post-processing feeding NMS (8f rank 1)
  * head: (n_loc = B*H*W, row_stride) rows of the merged head output [cls | box | dir] as the 1x1 heads emit it
  * (pcdet/models/dense_heads/anchor_head_single.py:45-55).  Anchor index = loc * anchors_per_loc + a, class logit

@@ -14,8 +14,13 @@ inference path does.  What runs here instead:
   * their weight gradient runs on the library by default (torch.ops.aten.convolution_backward, MIOpen: split-K with float atomics,
     not bitwise reproducible) and, with wgrad="wino", on the Winograd F(3x3, 4x4) weight-gradient kernel (csrc/wino43_wgrad.hip,
     wino.conv3x3_wgrad_f43: bitwise reproducible) for every layer it supports and whose map fits (wgrad_route / wino.wgrad43_fits);
-  * the stride-2 convolutions, the deblock convolutions and everything after the backbone stay on the library.
-Routing is per layer (TrainBEVBackbone.routes / wgrad_routes): anything the kernels do not take runs the stock module for that layer.
+  * the deblocks' up-convolutions (ConvTranspose2d, kernel == stride, no bias) run on the library by default and, with
+    deblock="gemm", on this package's GEMM kernels: the forward on csrc/deconv_gemm.hip (weights repacked every step) and both
+    gradients on csrc/deconv_train.hip (bitwise reproducible), each direction where its kernel takes the layer and the map fits
+    (deblock_conv_route / deconv_train_fits);
+  * the stride-2 convolutions and everything after the backbone stay on the library.
+Routing is per layer (TrainBEVBackbone.routes / wgrad_routes / deblock_conv_routes): anything the kernels do not take runs the stock
+module for that layer.
 """
 import ctypes as C
 
@@ -230,6 +235,173 @@ def conv3x3_train(x, weight, wgrad="library"):
     return _WinoConv3x3Train.apply(x, weight, wgrad)
 
 
+# ------------------------------------------------------------------ deblock up-convolution: ConvTranspose2d, kernel == stride, no bias
+DEBLOCK_OPTIONS = ("library", "gemm")
+
+# largest map (bytes, at its row stride) csrc/deconv_train.hip addresses with its 32-bit offsets (the launchers refuse 2^31 - 1 and
+# more).  A list so that tests can lower it.
+_DECONV_TRAIN_MAX_BYTES = [2 ** 31 - 1]
+
+
+def _check_deblock(deblock, who):
+    if deblock not in DEBLOCK_OPTIONS:
+        raise _lib.LidarHipError(f"{who}: deblock must be one of {DEBLOCK_OPTIONS}, got {deblock!r}")
+    return deblock
+
+
+def deconv_train_supported(K, s, c_up):
+    """the gradient kernels of csrc/deconv_train.hip take this layer: s in {1, 2, 4}, K % 8 == 0 in [16, 512], C_up % 32 == 0 in
+    [32, 512].  Pure host."""
+    return bool(_lib.lib().lidar_deconv_train_supported(int(K), int(s), int(c_up)))
+
+
+def deconv_train_fits(B, h, w, s, x_ld, g_ld):
+    """the gradient kernels can address B x h x w pixels of x_ld floats (x, dx) and the s-times upsampled gradient map of g_ld floats
+    per pixel: not empty, row strides multiples of 4 floats, each map under _DECONV_TRAIN_MAX_BYTES.  Pure host arithmetic."""
+    P = int(B) * int(h) * int(w)
+    return (P > 0 and x_ld % 4 == 0 and g_ld % 4 == 0 and P * x_ld * 4 < _DECONV_TRAIN_MAX_BYTES[0]
+            and P * s * s * g_ld * 4 < _DECONV_TRAIN_MAX_BYTES[0])
+
+
+def _deconv_shapes(what, x_shape, g, weight, s):
+    B, K, h, w = x_shape
+    c_up = weight.shape[1]
+    if tuple(weight.shape) != (K, c_up, s, s) or tuple(g.shape) != (B, c_up, s * h, s * w) or g.device != weight.device:
+        raise _lib.LidarHipError(f"{what}: x {tuple(x_shape)}, weight {tuple(weight.shape)}, stride {s} and gradient {tuple(g.shape)} do not "
+                                 "belong to one kernel == stride ConvTranspose2d")
+    if not deconv_train_supported(K, s, c_up):
+        raise _lib.LidarHipError(f"{what}: (K, s, C_up) = ({K}, {s}, {c_up}) is not supported (deconv_train_supported)")
+    return B, K, h, w, c_up
+
+
+def deconv_forward_gemm(x, weight, s):
+    """conv_transpose2d(x, weight, stride=s) for kernel == stride == s and no bias on csrc/deconv_gemm.hip: x (B, K, h, w) channels-last,
+    weight the module's (K, C_up, s, s) -> a new channels-last (B, C_up, s h, s w) map.  The weights are repacked on every call."""
+    from .bev_backbone import deconv_pack
+    _lib.require_nhwc(x, "deconv_forward_gemm")
+    B, K, h, w = x.shape
+    c_up = weight.shape[1]
+    if tuple(weight.shape) != (K, c_up, s, s):
+        raise _lib.LidarHipError(f"deconv_forward_gemm: weight {tuple(weight.shape)} does not match x {tuple(x.shape)} and stride {s}")
+    packed = deconv_pack(weight.permute(0, 2, 3, 1).reshape(K, s * s * c_up))       # columns (ky, kx, c)
+    out = torch.empty((B, c_up, s * h, s * w), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+    _lib.check(_lib.lib().lidar_deconv_gemm_nhwc(_lib.ptr(x), B, h, w, K, _lib.ptr(packed), None, 0, int(s), c_up, _lib.ptr(out), c_up, 0,
+                                                 _lib.stream()), "lidar_deconv_gemm_nhwc")
+    return out
+
+
+def deconv_dgrad(g, weight, s):
+    """the input gradient of conv_transpose2d(x, weight, stride=s) (kernel == stride == s): g (B, C_up, s h, s w), a channels-last fp32
+    map or a channel slice of one, weight (K, C_up, s, s) -> dx (B, K, h, w) channels-last.  One fixed summation order: bitwise
+    reproducible; no host synchronisation (csrc/deconv_train.hip)."""
+    g_ld = _lib.nhwc_ld(g, "deconv_dgrad g")
+    wc = weight.contiguous()               # torch's own (K, C_up, s, s) layout (a channels-last model holds it permuted)
+    _lib.require_cuda(wc)
+    if g.shape[2] % s or g.shape[3] % s:
+        raise _lib.LidarHipError(f"deconv_dgrad: the gradient map {tuple(g.shape)} is no multiple of the stride {s}")
+    x_shape = (g.shape[0], weight.shape[0], g.shape[2] // s, g.shape[3] // s)
+    B, K, h, w, c_up = _deconv_shapes("deconv_dgrad", x_shape, g, weight, s)
+    if not deconv_train_fits(B, h, w, s, K, g_ld) or g.data_ptr() % 16:
+        raise _lib.LidarHipError(f"deconv_dgrad: a gradient map of shape {tuple(g.shape)} is empty, misaligned or too large (deconv_train_fits)")
+    dx = torch.empty((B, K, h, w), dtype=torch.float32, device=g.device, memory_format=torch.channels_last)
+    _lib.check(_lib.lib().lidar_deconv_dgrad_nhwc(_lib.ptr(g), g_ld, _lib.ptr(wc), B, h, w, K, int(s), c_up, _lib.ptr(dx), K,
+                                                  _lib.stream()), "lidar_deconv_dgrad_nhwc")
+    return dx
+
+
+def deconv_wgrad(x, g, s):
+    """the weight gradient of conv_transpose2d(x, weight, stride=s) (kernel == stride == s): x (B, K, h, w) and g (B, C_up, s h, s w),
+    channels-last fp32 maps or channel slices of such maps -> dW (K, C_up, s, s) fp32, contiguous.  fp32 partial sums over <= 4096
+    pixels, the rest in fp64; bitwise reproducible; no host synchronisation (csrc/deconv_train.hip)."""
+    x_ld, g_ld = _lib.nhwc_ld(x, "deconv_wgrad x"), _lib.nhwc_ld(g, "deconv_wgrad g")
+    K, c_up = x.shape[1], g.shape[1]
+    dw = torch.empty((K, c_up, s, s), dtype=torch.float32, device=x.device)
+    B, K, h, w, c_up = _deconv_shapes("deconv_wgrad", x.shape, g, dw, s)
+    if not deconv_train_fits(B, h, w, s, x_ld, g_ld) or x.data_ptr() % 16 or g.data_ptr() % 16:
+        raise _lib.LidarHipError(f"deconv_wgrad: maps of shape {tuple(x.shape)} / {tuple(g.shape)} are empty, misaligned or too large "
+                                 "(deconv_train_fits)")
+    L = _lib.lib()
+    wsb = L.lidar_deconv_wgrad_workspace_bytes(B, h, w, K, int(s), c_up)
+    ws = workspace.get("deconv_wgrad", wsb, x.device)
+    _lib.check(L.lidar_deconv_wgrad_nhwc(_lib.ptr(x), x_ld, _lib.ptr(g), g_ld, B, h, w, K, int(s), c_up, _lib.ptr(dw), _lib.ptr(ws), wsb,
+                                         _lib.stream()), "lidar_deconv_wgrad_nhwc")
+    return dw
+
+
+class _DeconvTrain(torch.autograd.Function):
+    """deblock="gemm": each direction on this package's kernel where the kernel takes the layer and the maps fit, else the library"""
+
+    @staticmethod
+    def forward(ctx, x, weight, s):
+        from .bev_backbone import deconv_fits, deconv_supported
+        w = weight.detach()
+        ctx.save_for_backward(x, weight)
+        ctx.s = s
+        B, K, h, wd = x.shape
+        c_up = w.shape[1]
+        if deconv_supported(K, s, c_up) and deconv_fits(B, K, h, wd, s, c_up):
+            return deconv_forward_gemm(x, w, s)
+        return _cl(F.conv_transpose2d(x, w, None, s))
+
+    @staticmethod
+    def backward(ctx, grad_z):
+        x, weight = ctx.saved_tensors
+        g, w, s = _cl(grad_z), weight.detach(), ctx.s
+        B, K, h, wd = x.shape
+        c_up = w.shape[1]
+        # decided on the host from the shapes, as the weight gradient of the 3x3 layers is (_WinoConv3x3Train.backward)
+        own = (deconv_train_supported(K, s, c_up) and deconv_train_fits(B, h, wd, s, K, c_up)
+               and x.data_ptr() % 16 == 0 and g.data_ptr() % 16 == 0)
+
+        def library(mask):
+            return torch.ops.aten.convolution_backward(g, x, w, None, [s, s], [0, 0], [1, 1], True, [0, 0], 1, mask)
+
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = deconv_dgrad(g, w, s) if own else library([True, False, False])[0]
+        if ctx.needs_input_grad[1]:
+            dw = deconv_wgrad(x, g, s) if own else library([False, True, False])[1]
+        return dx, dw, None
+
+
+def deconv_train(x, weight, stride, deblock="library"):
+    """conv_transpose2d(x, weight, stride=stride) for a bias-free ConvTranspose2d with kernel == stride on a channels-last fp32 map ->
+    a channels-last map.  deblock="library" (the default): torch's own call and backward.  deblock="gemm": the forward on
+    csrc/deconv_gemm.hip where bev_backbone.deconv_supported / deconv_fits hold, the input and the weight gradient on
+    csrc/deconv_train.hip where deconv_train_supported / deconv_train_fits hold (bitwise reproducible), the library for whatever
+    they do not take; saves x and the weight only."""
+    _check_deblock(deblock, "deconv_train")
+    s = int(stride[0] if isinstance(stride, (tuple, list)) else stride)
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (s, s) or weight.shape[0] != x.shape[1]:
+        raise _lib.LidarHipError(f"deconv_train: weight {tuple(weight.shape)} is no (K, C_up, {s}, {s}) filter for x {tuple(x.shape)}")
+    _lib.require_nhwc(x, "deconv_train")
+    if deblock == "library":
+        return _cl(F.conv_transpose2d(x, weight, None, s))
+    return _DeconvTrain.apply(x, weight, s)
+
+
+def deblock_conv_route(de, deblock="library"):
+    """who runs (forward, input gradient, weight gradient) of one deblock's up-convolution under the option `deblock`, each "gemm"
+    (csrc/deconv_gemm.hip / csrc/deconv_train.hip) or "library".  All "library" unless the option asks for "gemm" and the deblock
+    opens with a bias-free ConvTranspose2d with kernel == stride, no padding, dilation or groups; then per direction by the kernels'
+    supported widths.  Pure host, from the module alone; a map that does not fit the kernels' 32-bit offsets still takes the library
+    at run time.  (A host-side rule that leaves a measured-slower shape on the library would live here: DESIGN 3.20.)"""
+    from .bev_backbone import deconv_supported
+    _check_deblock(deblock, "deblock_conv_route")
+    library = ("library", "library", "library")
+    mods = list(de) if isinstance(de, (nn.Sequential, list, tuple)) else [de]
+    up = mods[0] if mods else None
+    if deblock != "gemm" or type(up) is not nn.ConvTranspose2d:
+        return library
+    s = up.stride[0]
+    if (up.bias is not None or tuple(up.kernel_size) != (s, s) or tuple(up.stride) != (s, s) or tuple(up.padding) != (0, 0)
+            or tuple(up.output_padding) != (0, 0) or tuple(up.dilation) != (1, 1) or up.groups != 1):
+        return library
+    K, c_up = up.in_channels, up.out_channels
+    grad = "gemm" if deconv_train_supported(K, s, c_up) else "library"
+    return ("gemm" if deconv_supported(K, s, c_up) else "library", grad, grad)
+
+
 # ------------------------------------------------------------------ the backbone
 def _route(l):
     """conv_route of a bev_backbone.BlockLayer"""
@@ -264,10 +436,12 @@ class TrainBEVBackbone:
     pointpillar.make_bev_backbone / the reference build them): their parameters receive the gradients and their BatchNorm running
     statistics are updated.  Call with the channels-last fp32 BEV map -> the concatenated deblock map (channels-last); autograd
     does the backward.  Building it is pure host (routes are decided from the modules' settings).  wgrad: who computes the weight
-    gradients of the "wino"-routed layers ("library", the default, or "wino": see wgrad_routes)."""
+    gradients of the "wino"-routed layers ("library", the default, or "wino": see wgrad_routes).  deblock: who runs the deblocks'
+    up-convolutions ("library", the default, or "gemm": see deblock_conv_routes)."""
 
-    def __init__(self, blocks, deblocks, wgrad="library"):
+    def __init__(self, blocks, deblocks, wgrad="library", deblock="library"):
         self.wgrad = _check_wgrad(wgrad, "TrainBEVBackbone")
+        self.deblock = _check_deblock(deblock, "TrainBEVBackbone")
         self.blocks, self.deblocks = list(blocks), list(deblocks)
         self.plan = []
         for blk in self.blocks:
@@ -275,6 +449,9 @@ class TrainBEVBackbone:
             self.plan.append(("stock", blk) if layers is None else ("layers", [(_route(l), l) for l in layers]))
         n = len(self.blocks)
         self.de_routes = [deblock_route(de) for de in self.deblocks[:n]]
+        # a "stock" deblock runs as the module it is: its up-convolution stays on the library whatever the option says
+        self.de_conv_routes = [deblock_conv_route(de, self.deblock) if r == "fused" else ("library",) * 3
+                               for de, r in zip(self.deblocks[:n], self.de_routes)]
         self.extra = self.deblocks[n] if len(self.deblocks) > n else None       # a final deblock on the concatenated map (stock)
         bns = [list(de)[1] for de in self.deblocks[:n]]
         self.de_merged = (len(bns) > 0 and all(r == "fused" for r in self.de_routes) and len(bns) <= _MAX_SEG
@@ -290,6 +467,18 @@ class TrainBEVBackbone:
         "wino" layer whose map does not fit the kernel's 32-bit offsets (wino.wgrad43_fits) still takes the library at run time."""
         return [[(wgrad_route(l.conv.in_channels, l.conv.out_channels, self.wgrad) if route == "wino" else None) for route, l in steps]
                 if kind == "layers" else [None] for kind, steps in self.plan]
+
+    def deblock_conv_routes(self):
+        """-> [(forward, input gradient, weight gradient) of each deblock's up-convolution], each "gemm" (csrc/deconv_gemm.hip /
+        csrc/deconv_train.hip) or "library" (deblock_conv_route; all "library" for a deblock routes() calls "stock")"""
+        return list(self.de_conv_routes)
+
+    def _up(self, i, f):
+        """deblock i's up-convolution of the block output f"""
+        up = list(self.deblocks[i])[0]
+        if "gemm" in self.de_conv_routes[i]:
+            return deconv_train(f, up.weight, up.stride[0], "gemm")
+        return _cl(up(f))
 
     def _layer(self, step, x):
         route, l = step
@@ -316,13 +505,12 @@ class TrainBEVBackbone:
         if not self.deblocks[:n]:
             out = torch.cat(feats, dim=1) if len(feats) > 1 else feats[0]
         elif self.de_merged:     # every deblock's BN + ReLU in one call, written straight into the concatenated map
-            zs = [_cl(list(de)[0](f)) for de, f in zip(self.deblocks, feats)]
+            zs = [self._up(i, f) for i, f in enumerate(feats)]
             out = bn_relu_train(zs, [list(de)[1] for de in self.deblocks[:n]])
         else:
             ups = []
-            for de, f, route in zip(self.deblocks, feats, self.de_routes):
-                up, bn = list(de)[0], list(de)[1]
-                ups.append(bn_relu_train(_cl(up(f)), bn) if route == "fused" else _cl(de(f)))
+            for i, (de, f, route) in enumerate(zip(self.deblocks, feats, self.de_routes)):
+                ups.append(bn_relu_train(self._up(i, f), list(de)[1]) if route == "fused" else _cl(de(f)))
             out = torch.cat(ups, dim=1) if len(ups) > 1 else ups[0]
         if self.extra is not None:
             out = _cl(self.extra(out))

@@ -23,7 +23,7 @@ import torch.nn as nn
 
 from . import anchor_loss, anchor_post, pillar_ops, synth
 from .bev_backbone import FoldedBEVBackbone, collect_params, params_key
-from .bev_train import TrainBEVBackbone, _check_wgrad
+from .bev_train import TrainBEVBackbone, _check_deblock, _check_wgrad
 from .ext import iou3d_nms_cuda
 from .voxelizer import BatchVoxelizer, grid_size_of
 
@@ -196,17 +196,20 @@ class PointPillarKITTI(nn.Module):
         dirs = self.conv_dir_cls(x).permute(0, 2, 3, 1).reshape(self.B, -1, self.num_dir_bins)
         return cls, box, dirs
 
-    def backbone_head_train(self, canvas, wgrad="library"):
+    def backbone_head_train(self, canvas, wgrad="library", deblock="library"):
         """backbone_head_stock() in train mode on this package's kernels (bev_train.TrainBEVBackbone: fused train-mode BatchNorm +
         ReLU, Winograd stride-1 convolutions forward and input gradient, the deblocks' BatchNorm written straight into the
         concatenated map); the heads stay stock.  Needs the channels-last model (channels_last=True) and a channels-last canvas.
-        wgrad: who computes the weight gradients of the stride-1 3x3 layers, "library" (MIOpen) or "wino" (csrc/wino43_wgrad.hip)."""
+        wgrad: who computes the weight gradients of the stride-1 3x3 layers, "library" (MIOpen) or "wino" (csrc/wino43_wgrad.hip).
+        deblock: who runs the deblocks' up-convolutions, "library" or "gemm" (csrc/deconv_gemm.hip forward, csrc/deconv_train.hip
+        gradients; bev_train.deblock_conv_route)."""
         _check_wgrad(wgrad, "PointPillarKITTI.backbone_head_train")
+        _check_deblock(deblock, "PointPillarKITTI.backbone_head_train")
         if not self.channels_last:
             raise pillar_ops._lib.LidarHipError("PointPillarKITTI.backbone_head_train needs the channels-last model (channels_last=True)")
-        key = "_bev_train" if wgrad == "library" else "_bev_train_" + wgrad
+        key = ("_bev_train" if wgrad == "library" else "_bev_train_" + wgrad) + ("" if deblock == "library" else "_" + deblock)
         if self.__dict__.get(key) is None:
-            self.__dict__[key] = TrainBEVBackbone(self.blocks, self.deblocks, wgrad=wgrad)
+            self.__dict__[key] = TrainBEVBackbone(self.blocks, self.deblocks, wgrad=wgrad, deblock=deblock)
         return self._head_maps(self.__dict__[key](canvas))
 
     def rpn_loss(self, head_out, gt_boxes):
@@ -217,18 +220,20 @@ class PointPillarKITTI(nn.Module):
         t = head.assign_targets(gt_boxes)
         return anchor_loss.anchor_head_loss(*head_out, t['box_cls_labels'], t['box_reg_targets'], head.loss_anchors(), head.loss_spec)
 
-    def train_loss(self, points, point_offsets, gt_boxes, host_offsets=None, backbone="stock", wgrad="library"):
+    def train_loss(self, points, point_offsets, gt_boxes, host_offsets=None, backbone="stock", wgrad="library", deblock="library"):
         """One training forward of PointPillar-KITTI on this package's kernels: voxelise (no gradient), the train-mode PillarVFE
         (batch statistics; pfn_norm's running statistics are updated), the differentiable scatter into a fresh canvas, the backbone
         and head (train-mode BatchNorm) and rpn_loss.  -> (cls_loss, loc_loss, dir_loss), differentiable with respect to
         every parameter.  gt_boxes (B, M, 8) [box | class id].  No host synchronisation.
         backbone: "stock" (backbone_head_stock: torch modules) or "fused" (backbone_head_train; needs channels_last).
-        wgrad ("library" or "wino"): backbone_head_train's option; it has no effect on the "stock" backbone."""
+        wgrad ("library" or "wino") and deblock ("library" or "gemm"): backbone_head_train's options; they have no effect on the
+        "stock" backbone."""
         if not self.training:
             raise pillar_ops._lib.LidarHipError("PointPillarKITTI.train_loss needs train mode (call .train() first)")
         if backbone not in ("stock", "fused"):
             raise pillar_ops._lib.LidarHipError(f"PointPillarKITTI.train_loss: backbone must be 'stock' or 'fused', got {backbone!r}")
         _check_wgrad(wgrad, "PointPillarKITTI.train_loss")
+        _check_deblock(deblock, "PointPillarKITTI.train_loss")
         if backbone == "fused" and not self.channels_last:
             raise pillar_ops._lib.LidarHipError("PointPillarKITTI.train_loss(backbone='fused') needs the channels-last model")
         with torch.no_grad():   # fresh voxel buffers: the PFN's backward reads them after the next step may have voxelised
@@ -240,7 +245,12 @@ class PointPillarKITTI(nn.Module):
                                            momentum=n.momentum, num_batches_tracked=n.num_batches_tracked, num_voxels_dev=total)
         canvas = pillar_ops.pillar_scatter_train(feat, vox["voxel_coords"], self.B, self.nx, self.ny, num_voxels_dev=total,
                                                  channels_last=self.channels_last)
-        head = self.backbone_head_train(canvas, wgrad) if backbone == "fused" else self.backbone_head_stock(canvas)
+        if backbone != "fused":
+            head = self.backbone_head_stock(canvas)
+        elif deblock == "library":
+            head = self.backbone_head_train(canvas, wgrad)
+        else:
+            head = self.backbone_head_train(canvas, wgrad, deblock)
         return self.rpn_loss(head, gt_boxes)
 
     def _loss_head(self):

@@ -1,6 +1,8 @@
 """Times the bs-16 PointPillar-KITTI training step with the stock train-mode backbone, with the fused one (bev_train.py:
-csrc/bn_train.hip BatchNorm + ReLU, Winograd stride-1 convolutions forward and input gradient, weight gradients on the library) and
-with the fused one + wgrad="wino" (csrc/wino43_wgrad.hip for the stride-1 3x3 weight gradients), alternated in one process:
+csrc/bn_train.hip BatchNorm + ReLU, Winograd stride-1 convolutions forward and input gradient, weight gradients on the library),
+with the fused one + wgrad="wino" (csrc/wino43_wgrad.hip for the stride-1 3x3 weight gradients) and with that + deblock="gemm"
+(csrc/deconv_gemm.hip / csrc/deconv_train.hip for the deblocks' up-convolutions, forward and both gradients), alternated in one
+process:
 
   step      PointPillarKITTI.train_loss(backbone=...) + backward (gradients of every parameter);
   backbone  backbone_head_stock / backbone_head_train + backward alone on a fixed channels-last canvas (no PFN, scatter or loss).
@@ -9,9 +11,9 @@ Inputs: 16 synthetic KITTI-like clouds and boxes (tests/test_gpu_pfn_train.py's 
 one call of each column back to back; medians after warm-up; peak memory from torch.cuda.max_memory_allocated above what was
 allocated before the call.  Prints one JSON line.
 
-  python tools/bev_train_bench.py [--iters 20] [--only stock|fused|fused_wino] [--rocprof OUTDIR]
+  python tools/bev_train_bench.py [--iters 20] [--only stock|fused|fused_wino|fused_wino_gemm] [--rocprof OUTDIR]
 
---rocprof OUTDIR: afterwards runs this script once more per column in child processes (--only stock, fused, fused_wino) under
+--rocprof OUTDIR: afterwards runs this script once more per column in child processes (--only stock, fused, fused_wino, fused_wino_gemm) under
 `rocprofv3 --kernel-trace --stats --output-format csv -d OUTDIR/<column>` (kernel trace only, no counters), so each column's kernel
 statistics come from a run of their own.
 """
@@ -29,9 +31,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-KINDS = ("stock", "fused", "fused_wino")
-# column -> (backbone option, wgrad option) of PointPillarKITTI.train_loss / backbone_head_train
-OPTIONS = {"stock": ("stock", "library"), "fused": ("fused", "library"), "fused_wino": ("fused", "wino")}
+KINDS = ("stock", "fused", "fused_wino", "fused_wino_gemm")
+# column -> (backbone option, wgrad option, deblock option) of PointPillarKITTI.train_loss / backbone_head_train
+OPTIONS = {"stock": ("stock", "library", "library"), "fused": ("fused", "library", "library"), "fused_wino": ("fused", "wino", "library"),
+           "fused_wino_gemm": ("fused", "wino", "gemm")}
 
 
 def load_test_module():
@@ -89,13 +92,13 @@ def main():
     heads_g = None
 
     def step(kind):
-        bb, wg = OPTIONS[kind]
-        return lambda: torch.autograd.grad(sum(pp.train_loss(pts, offs, gt, backbone=bb, wgrad=wg)), params)
+        bb, wg, de = OPTIONS[kind]
+        return lambda: torch.autograd.grad(sum(pp.train_loss(pts, offs, gt, backbone=bb, wgrad=wg, deblock=de)), params)
 
     def backbone(kind):
         def run():
             nonlocal heads_g
-            head = pp.backbone_head_stock(canvas) if kind == "stock" else pp.backbone_head_train(canvas, OPTIONS[kind][1])
+            head = pp.backbone_head_stock(canvas) if kind == "stock" else pp.backbone_head_train(canvas, *OPTIONS[kind][1:])
             if heads_g is None:
                 heads_g = [torch.randn(h.shape, generator=g).to(dev) for h in head]
             torch.autograd.grad(sum((h * hg).sum() for h, hg in zip(head, heads_g)), bev_params)
@@ -112,6 +115,7 @@ def main():
         if len(kinds) == len(KINDS):
             w["speedup"] = round(t["stock"][0] / t["fused"][0], 3)
             w["wino_wgrad_speedup"] = round(t["fused"][0] / t["fused_wino"][0], 3)        # over the fused column (wgrad="library")
+            w["gemm_deblock_speedup"] = round(t["fused_wino"][0] / t["fused_wino_gemm"][0], 3)   # over fused_wino (deblock="library")
         result[name] = w
     print(json.dumps(result), flush=True)
     if args.rocprof:
