@@ -588,6 +588,44 @@ int lidar_anchor_assign(const float *const *anchors, const long long *counts, co
                         int max_gt, int gt_cols, int code_size, int sincos, int norm_by_num_examples, int *labels, float *targets,
                         float *weights, void *ws, size_t ws_bytes, void *stream);
 
+/* ------------------------------------------------------------------ second-stage RoI target assignment (training)
+ * ProposalTargetLayer.forward (pcdet/models/roi_heads/target_assigner/proposal_target_layer.py:13-238) and the canonical transform
+ * of RoIHeadTemplate.assign_targets (pcdet/models/roi_heads/roi_head_template.py:101-131) for a whole batch in ONE launch on the
+ * caller's stream: no host read, no float atomics, bitwise reproducible, graph-capturable, no workspace (csrc/proposal_target.hip).
+ *   rois (batch, num_rois, box_dim) f32, roi_scores (batch, num_rois) f32, roi_labels (batch, num_rois) i64,
+ *   gt_boxes (batch, max_gt, box_dim + 1) f32 [box | class id]; gt_boxes_enlarged: the same shape or NULL.  Per frame the trailing
+ *   rows whose fp32 left-to-right sum (class id included) is 0 are trimmed, row 0 always stays (:94-97); trim, IoU and gt labels
+ *   come from gt_boxes_enlarged when given (:93), gt_of_rois from gt_boxes (:116-117).  3D IoU: boxes_iou3d_gpu
+ *   (pcdet/ops/iou3d_nms/iou3d_nms_utils.py:48-81) on the polygon clipper of csrc/iou3d_dev.h.
+ *   by_class: SAMPLE_ROI_BY_EACH_CLASS (:204-238: only gts whose label equals the roi's; none -> overlap 0, assignment 0).
+ *   fg_rois_per_image = int(np.round(FG_RATIO * ROI_PER_IMAGE)); hard_quota HOST (roi_per_image + 1) ints, hard_quota[n] =
+ *   int(n * HARD_BG_RATIO) in [0, n] (Python double arithmetic, :177); cls_fg_minus_bg = CLS_FG_THRESH - CLS_BG_THRESH in double,
+ *   rounded once.  cls_score_type 0: 'cls' (1 / 0 / -1), 1: 'roi_iou'.
+ *   Randomness (the kernel draws nothing): fg_keys (batch, num_rois) f32, draws (batch, roi_per_image) f32 in [0, 1).  The
+ *   without-replacement fg choice (:144-145) takes the fg candidates with the smallest (key, roi index), in that order; every
+ *   with-replacement pick for output slot s is candidates[min(floor(draws[b][s] * n), n - 1)], product in fp32, candidates in
+ *   ascending roi index.  Slot order: fg, hard bg, easy bg.
+ *   -> out_rois (batch, P, box_dim), out_gt_of_rois (batch, P, box_dim + 1) after the canonical transform, out_gt_of_rois_src (the
+ *   same rows before it), out_iou, out_scores, out_cls_labels (batch, P) f32, out_labels, out_reg_valid (batch, P) i64,
+ *   out_sampled (batch, P) i32 roi indices, P = roi_per_image; max_overlaps (batch, num_rois) f32 and gt_assignment (batch,
+ *   num_rois) i32 of every roi; frame_status (batch) i32: 0, or 1 for a frame with neither fg nor bg (NaN overlaps; the reference
+ *   raises NotImplementedError, :166-169), whose sampled outputs are zeros.
+ * Supported (lidar_proposal_target_supported, pure host; everything else is refused with LIDAR_ERR_ARG before any launch):
+ * 1 <= num_rois <= 1024, 1 <= max_gt <= 512, 1 <= roi_per_image <= 512, 7 <= box_dim <= 16; batch >= 0 (0: nothing is launched). */
+#define LIDAR_PROPOSAL_TARGET_MAX_ROIS 1024
+#define LIDAR_PROPOSAL_TARGET_MAX_GT 512
+#define LIDAR_PROPOSAL_TARGET_MAX_SAMPLES 512
+#define LIDAR_PROPOSAL_TARGET_MAX_DIM 16
+int lidar_proposal_target_supported(int num_rois, int max_gt, int roi_per_image, int box_dim);
+int lidar_proposal_target(const float *rois, const float *roi_scores, const long long *roi_labels, const float *gt_boxes,
+                          const float *gt_boxes_enlarged, int batch, int num_rois, int max_gt, int box_dim, int roi_per_image,
+                          int fg_rois_per_image, const int *hard_quota, int by_class, int cls_score_type, float reg_fg_thresh,
+                          float cls_fg_thresh, float cls_bg_thresh, float cls_bg_thresh_lo, float cls_fg_minus_bg,
+                          const float *fg_keys, const float *draws, float *out_rois, float *out_gt_of_rois,
+                          float *out_gt_of_rois_src, float *out_iou, float *out_scores, long long *out_labels,
+                          long long *out_reg_valid, float *out_cls_labels, int *out_sampled, int *frame_status,
+                          float *max_overlaps, int *gt_assignment, void *stream);
+
 /* ------------------------------------------------------------------ anchor-head RPN loss (training), forward + backward
  * AnchorHeadTemplate.get_loss / AnchorHeadMulti.get_loss for a whole batch and every head, no host synchronisation, no float atomics
  * (csrc/anchor_loss.hip).  Reference: pcdet/models/dense_heads/anchor_head_template.py:102-224 (get_cls_layer_loss,

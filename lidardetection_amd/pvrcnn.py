@@ -26,7 +26,9 @@ from .pcdet.ops.pointnet2 import _common as pn_common
 from .pcdet.ops.pointnet2.pointnet2_batch import pointnet2_utils as pn_batch
 from .pcdet.ops.pointnet2.pointnet2_stack import pointnet2_modules as pn_stack_modules
 from .pcdet.ops.pointnet2.pointnet2_stack import pointnet2_utils as pn_stack
+from .pcdet.models.roi_heads.roi_head_template import RoIHeadTemplate
 from .pcdet.utils import common_utils
+from .pcdet.utils.cfg import AttrDict
 from .second import SECONDKitti
 
 # pv_rcnn.yaml:119-144: source -> (downsample factor, radii, nsamples, MLP widths behind the input width)
@@ -36,6 +38,10 @@ VSA_SOURCES = {
     "x_conv3": (4, [1.2, 2.4], [16, 32], [[64, 64], [64, 64]], 64),
     "x_conv4": (8, [2.4, 4.8], [16, 32], [[64, 64], [64, 64]], 64),
 }
+
+# pv_rcnn.yaml:190-202: ROI_HEAD.TARGET_CONFIG
+TARGET_CONFIG = dict(ROI_PER_IMAGE=128, FG_RATIO=0.5, SAMPLE_ROI_BY_EACH_CLASS=True, CLS_SCORE_TYPE="roi_iou", CLS_FG_THRESH=0.75,
+                     CLS_BG_THRESH=0.25, CLS_BG_THRESH_LO=0.1, HARD_BG_RATIO=0.8, REG_FG_THRESH=0.55)
 
 
 def bilinear_bev(bev_nhwc, x, y):
@@ -205,6 +211,23 @@ class PVRCNNKitti(SECONDKitti):
         roi_scores = torch.gather(top_scores, 1, sel) * valid
         roi_labels = (torch.gather(labels_all, 1, torch.gather(top_idx, 1, sel)) + 1) * valid
         return rois, roi_scores, roi_labels, num, (boxes, top_scores)
+
+    def rcnn_targets(self, rois, roi_scores, roi_labels, gt_boxes, gt_boxes_enlarged=None, target_config=None, fg_keys=None,
+                     draws=None, generator=None):
+        """RoIHeadTemplate.assign_targets (roi_head_template.py:101-131) on what proposals() returns: rois (B, R, 7) zero padded,
+        roi_scores (B, R), roi_labels (B, R) 1-based (0 on the padding: those rois match no gt and land in easy bg, as in the
+        reference), gt_boxes (B, M, 8) [box | class id] -> the reference's targets_dict (rois, gt_of_rois in the roi's frame,
+        gt_of_rois_src, gt_iou_of_rois, roi_scores, roi_labels, reg_valid_mask, rcnn_cls_labels) plus sampled_inds and
+        frame_status.  One HIP launch, no host synchronisation; target_config overrides entries of pv_rcnn.yaml's TARGET_CONFIG;
+        fg_keys / draws / generator: the random numbers (pcdet/models/roi_heads/target_assigner/proposal_target_layer.py here)."""
+        cfg = AttrDict(TARGET_CONFIG, **(target_config or {}))
+        cached = self.__dict__.get("_rcnn_target_head")
+        if cached is None or cached[0] != dict(cfg):
+            cached = self.__dict__["_rcnn_target_head"] = (dict(cfg), RoIHeadTemplate(self.num_class, AttrDict(TARGET_CONFIG=cfg)))
+        batch = {"batch_size": rois.shape[0], "rois": rois, "roi_scores": roi_scores, "roi_labels": roi_labels, "gt_boxes": gt_boxes}
+        if gt_boxes_enlarged is not None:
+            batch["gt_boxes_enlarged"] = gt_boxes_enlarged
+        return cached[1].assign_targets(batch, fg_keys=fg_keys, draws=draws, generator=generator)
 
     def keypoints(self, points, point_offsets, sizes):
         """get_sampled_points (voxel_set_abstraction.py:119-157) -> (B, num_keypoints, 3): FPS per frame, starting at point 0"""

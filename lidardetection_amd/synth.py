@@ -80,3 +80,34 @@ def boxes_random(seed, n, extent=20.0):
     r = np.random.default_rng(seed)
     return np.concatenate([r.uniform(0, extent, (n, 2)), r.uniform(-1, 1, (n, 1)), r.uniform(0.5, 5, (n, 2)),
                            r.uniform(1, 2, (n, 1)), r.uniform(-np.pi, np.pi, (n, 1))], 1).astype(np.float32)
+
+
+def rcnn_target_inputs(seed=5000, batch=8, rois=512, max_gt=40, classes=3, pad_rois=32):
+    """A second-stage training batch shaped like PV-RCNN's: per frame a random number of gts of `classes` classes spread over the
+    KITTI range, zero padded to max_gt, and rois that are jittered copies of the gts (from near-exact to barely touching) or boxes
+    on empty ground, with the class of their gt, the last `pad_rois` rows zero with label 0 as a proposal layer pads them.
+    -> rois (batch, rois, 7) f32, roi_scores (batch, rois) f32, roi_labels (batch, rois) i64, gt_boxes (batch, max_gt, 8) f32"""
+    r = np.random.default_rng(seed)
+    sizes = np.array([[3.9, 1.6, 1.56], [0.8, 0.6, 1.73], [1.76, 0.6, 1.73]], np.float64)
+    gt = np.zeros((batch, max_gt, 8), np.float32)
+    boxes = np.zeros((batch, rois, 7), np.float32)
+    labels = np.zeros((batch, rois), np.int64)
+    scores = r.normal(0, 2, (batch, rois)).astype(np.float32)
+    for b in range(batch):
+        n = int(r.integers(max(1, max_gt // 4), max_gt + 1))
+        cls = r.integers(1, classes + 1, n)
+        g = np.concatenate([r.uniform(0, 70, (n, 1)), r.uniform(-40, 40, (n, 1)), r.uniform(-1.8, -0.4, (n, 1)),
+                            sizes[(cls - 1) % 3] * r.uniform(0.85, 1.15, (n, 3)), r.uniform(-np.pi, np.pi, (n, 1))], 1)
+        gt[b, :n, :7], gt[b, :n, 7] = g, cls
+        real = rois - pad_rois
+        src = r.integers(0, n, real)
+        noise = r.choice([0.02, 0.1, 0.25, 0.5, 1.0], real)[:, None]
+        jit = g[src].copy()
+        jit[:, 0:3] += r.normal(0, 1, (real, 3)) * noise * [1.0, 0.5, 0.2]
+        jit[:, 3:6] *= 1 + r.normal(0, 0.1, (real, 3)) * noise
+        jit[:, 6] += r.normal(0, 0.3, real) * noise[:, 0]
+        far = r.random(real) < 0.2
+        jit[far, 0:2] = np.stack([r.uniform(0, 70, far.sum()), r.uniform(-40, 40, far.sum())], 1)
+        boxes[b, :real], labels[b, :real] = jit, cls[src]
+        scores[b, real:] = 0
+    return boxes, scores, labels, gt

@@ -1,0 +1,351 @@
+"""Second-stage target assignment on the GPU (csrc/proposal_target.hip, lidardetection_amd/proposal_target.py, the
+pcdet.models.roi_heads mirror, PVRCNNKitti.rcnn_targets) against the reference's own ProposalTargetLayer + assign_targets
+(tests/golden/proposal_target_ref.npz, written by tests/golden/make_proposal_target_golden.py with the recorded random draws) and,
+at the sizes the fixture cannot hold, against the numpy restatement of tests/_proposal_target_np.py — which
+tests/test_proposal_target_host.py shows to reproduce the fixture — fed with the GPU's own max_overlaps, so that sampling, labels and
+the canonical transform are compared without threshold noise (the overlaps themselves are compared with the overlap oracle).
+
+Tolerances: indices, labels, masks and gathered rows bit-equal; IoU, roi_iou labels and the canonical gt_of_rois within 1e-4 of
+scale (the heading as an angle: the clamp to [-pi/2, pi/2] makes it unique)."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import _proposal_target_np as ptn
+from lidardetection_amd import _lib, proposal_target, synth
+from lidardetection_amd.pcdet.models.roi_heads.roi_head_template import RoIHeadTemplate
+from lidardetection_amd.pcdet.models.roi_heads.target_assigner.proposal_target_layer import ProposalTargetLayer
+from lidardetection_amd.pcdet.utils.cfg import AttrDict
+from oracle import c_oracle
+
+pytestmark = pytest.mark.gpu
+
+EXACT = ["sampled_inds", "roi_labels", "reg_valid_mask", "rois", "roi_scores", "gt_of_rois_src"]
+OUT_KEYS = EXACT + ["gt_of_rois", "gt_iou_of_rois", "rcnn_cls_labels", "frame_status"]
+
+
+def overlap(a, b):
+    return c_oracle.pairwise(a, b, 0)
+
+
+def head_of(cfg):
+    return RoIHeadTemplate(num_class=3, model_cfg=AttrDict(TARGET_CONFIG=AttrDict(cfg)))
+
+
+def batch_of(inp, dev):
+    t = {k: torch.from_numpy(np.ascontiguousarray(v)).to(dev) for k, v in inp.items()}
+    batch = {k: t[k] for k in ("rois", "roi_scores", "roi_labels", "gt_boxes", "gt_boxes_enlarged") if k in t}
+    batch["batch_size"] = inp["rois"].shape[0]
+    return batch, t
+
+
+def close(got, exp, tol=1e-4):
+    exp = np.asarray(exp, np.float64)
+    return bool(np.all(np.abs(np.asarray(got, np.float64) - exp) <= tol * max(1.0, float(np.abs(exp).max(initial=0.0)))))
+
+
+def assert_matches(got, exp, cfg, what):
+    got = {k: (v.cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in got.items()}
+    for k in EXACT:
+        assert got[k].shape == exp[k].shape, (what, k, got[k].shape, exp[k].shape)
+        assert np.array_equal(got[k], exp[k]), f"{what}: {k} differs in {int((got[k] != exp[k]).sum())} of {got[k].size} places"
+    if cfg["CLS_SCORE_TYPE"] == "cls":
+        assert got["rcnn_cls_labels"].dtype == np.int64 and np.array_equal(got["rcnn_cls_labels"], exp["rcnn_cls_labels"]), what
+    else:
+        assert got["rcnn_cls_labels"].dtype == np.float32 and close(got["rcnn_cls_labels"], exp["rcnn_cls_labels"]), what
+    assert got["reg_valid_mask"].dtype == np.int64 and got["roi_labels"].dtype == np.int64
+    assert close(got["gt_iou_of_rois"], exp["gt_iou_of_rois"]), what
+    g, e = got["gt_of_rois"], exp["gt_of_rois"]
+    assert g.shape == e.shape and close(np.delete(g, 6, axis=-1), np.delete(e, 6, axis=-1)), what
+    assert close(g[..., 6], e[..., 6]), f"{what}: heading differs by {np.abs(g[..., 6] - e[..., 6]).max()}"
+
+
+# ------------------------------------------------------------------------------------------------ the reference's fixture
+@pytest.mark.parametrize("name", ptn.CASES)
+def test_fixture_parity(name, dev):
+    cfg, inp, exp = ptn.load_case(name)
+    batch, t = batch_of(inp, dev)
+    got = head_of(cfg).assign_targets(batch, fg_keys=t["fg_keys"], draws=t["draws"])
+    assert not got["frame_status"].any()
+    assert close(got["max_overlaps"].cpu().numpy(), exp["max_overlaps"])
+    assert_matches(got, exp, cfg, name)
+    # the layer alone returns the reference's forward() dict: gt_of_rois before the transform
+    layer = ProposalTargetLayer(AttrDict(cfg)).forward(batch, fg_keys=t["fg_keys"], draws=t["draws"])
+    assert torch.equal(layer["gt_of_rois"], got["gt_of_rois_src"]) and set(got) - set(layer) == {"gt_of_rois_src"}
+
+
+# ------------------------------------------------------------------------------------------------ raw ABI, guard bands
+GUARD = 64          # elements of every dtype in front of and behind each output
+
+
+class Guarded:
+    def __init__(self, shape, dtype, dev):
+        n = int(np.prod(shape))
+        self.fill = float("nan") if dtype == torch.float32 else -7777
+        self.buf = torch.full((n + 2 * GUARD,), self.fill, dtype=dtype, device=dev)
+        self.view = self.buf[GUARD:GUARD + n].view(*shape)
+
+    def intact(self):
+        band = torch.cat((self.buf[:GUARD], self.buf[-GUARD:]))
+        return bool(torch.isnan(band).all()) if self.fill != self.fill else bool((band == self.fill).all())
+
+
+def raw_call(cfg, t, dev):
+    """lidar_proposal_target through ctypes with every output inside a guard band -> dict of tensors"""
+    B, R, D = t["rois"].shape
+    M, P = t["gt_boxes"].shape[1], cfg["ROI_PER_IMAGE"]
+    f32, i64, i32 = torch.float32, torch.int64, torch.int32
+    spec = [("rois", (B, P, D), f32), ("gt_of_rois", (B, P, D + 1), f32), ("gt_of_rois_src", (B, P, D + 1), f32),
+            ("gt_iou_of_rois", (B, P), f32), ("roi_scores", (B, P), f32), ("roi_labels", (B, P), i64), ("reg_valid_mask", (B, P), i64),
+            ("rcnn_cls_labels", (B, P), f32), ("sampled_inds", (B, P), i32), ("frame_status", (B,), i32),
+            ("max_overlaps", (B, R), f32), ("gt_assignment", (B, R), i32)]
+    outs = {k: Guarded(s, dt, dev) for k, s, dt in spec}
+    status = _lib.lib().lidar_proposal_target(
+        _lib.ptr(t["rois"]), _lib.ptr(t["roi_scores"]), _lib.ptr(t["roi_labels"]), _lib.ptr(t["gt_boxes"]),
+        _lib.ptr(t.get("gt_boxes_enlarged")), B, R, M, D, P, proposal_target.fg_rois_per_image(cfg["FG_RATIO"], P),
+        _lib.host_i32(proposal_target.hard_quota_table(cfg["HARD_BG_RATIO"], P)), int(cfg["SAMPLE_ROI_BY_EACH_CLASS"]),
+        proposal_target.CLS_SCORE_TYPES[cfg["CLS_SCORE_TYPE"]], cfg["REG_FG_THRESH"], cfg["CLS_FG_THRESH"], cfg["CLS_BG_THRESH"],
+        cfg["CLS_BG_THRESH_LO"], cfg["CLS_FG_THRESH"] - cfg["CLS_BG_THRESH"], _lib.ptr(t["fg_keys"]), _lib.ptr(t["draws"]),
+        *[C.c_void_p(outs[k].view.data_ptr()) for k, _, _ in spec], _lib.stream())
+    assert status == 0
+    torch.cuda.synchronize()
+    for k, g in outs.items():
+        assert g.intact(), f"the guard band around {k} was written"
+    return {k: g.view for k, g in outs.items()}
+
+
+def random_inputs(seed, B, R, M, D, P, dev, equal_keys=False, edge_draws=False):
+    boxes, scores, labels, gt = synth.rcnn_target_inputs(seed, batch=B, rois=R, max_gt=M, pad_rois=R // 16)
+    r = np.random.default_rng(seed + 1)
+    if D > 7:
+        boxes = np.concatenate([boxes, r.normal(0, 3, (B, R, D - 7)).astype(np.float32)], 2)
+        gt = np.concatenate([gt[..., :7], r.normal(0, 3, (B, M, D - 7)).astype(np.float32), gt[..., 7:]], 2)
+        gt[(gt[..., :7] == 0).all(-1)] = 0
+    keys = np.full((B, R), 0.5, np.float32) if equal_keys else r.random((B, R), dtype=np.float32)
+    draws = r.random((B, P), dtype=np.float32)
+    if edge_draws:
+        draws[:, ::2] = 0.0
+        draws[:, 1::2] = np.nextafter(np.float32(1), np.float32(0))
+    inp = dict(rois=boxes, roi_scores=scores, roi_labels=labels, gt_boxes=gt, fg_keys=keys, draws=draws)
+    return inp, {k: torch.from_numpy(np.ascontiguousarray(v)).to(dev) for k, v in inp.items()}
+
+
+def check_assignment(cfg, inp, ov, asg, own, what):
+    """max_overlaps / gt_assignment of every roi against the per-pair IoU of the overlap oracle: the overlap at the assigned gt is
+    the roi's maximum, the assigned gt has the roi's label (by class; assignment 0 and overlap 0 when no gt has it), and wherever
+    the choice is not a matter of rounding — the maximum leads by 1e-3, ten times the tolerance, or every eligible overlap is
+    exactly 0, where first-index argmax picks the first eligible gt — the assignment is the restatement's"""
+    src_all = inp.get("gt_boxes_enlarged", inp["gt_boxes"])
+    by_class = cfg.get("SAMPLE_ROI_BY_EACH_CLASS", False)
+    decided = 0
+    for b in range(ov.shape[0]):
+        k = int(own["kept"][b])
+        assert (asg[b] >= 0).all() and (asg[b] < k).all(), what
+        gts = src_all[b][:k]
+        iou = ptn.iou3d(inp["rois"][b], gts, overlap)
+        rows = np.arange(iou.shape[0])
+        eligible = np.ones(iou.shape, bool)
+        if by_class:
+            eligible = inp["roi_labels"][b][:, None] == gts[:, -1].astype(np.int64)[None, :]
+        has = eligible.any(1)
+        assert (asg[b][~has] == 0).all() and (ov[b][~has] == 0).all(), f"{what}: rois without a gt of their label"
+        assert eligible[rows, asg[b]][has].all(), f"{what}: a roi was assigned a gt of another label"
+        assert np.abs(iou[rows, asg[b]] - ov[b])[has].max(initial=0.0) <= 1e-4, f"{what}: the assigned gt does not reach max_overlaps"
+        masked = np.where(eligible, iou, -np.inf)
+        top = -np.sort(-masked, axis=1)[:, :2] if k > 1 else np.concatenate([masked, np.full_like(masked, -np.inf)], 1)
+        with np.errstate(invalid="ignore"):      # rois without an eligible gt: -inf - -inf, excluded by `has`
+            clear = has & ((top[:, 0] - top[:, 1] > 1e-3) | ((top[:, 0] == 0) & (ov[b] == 0)))
+        assert np.array_equal(asg[b][clear], own["gt_assignment"][b][clear]), \
+            f"{what}: frame {b}: {int((asg[b][clear] != own['gt_assignment'][b][clear]).sum())} assignments differ from the restatement's"
+        decided += int(clear.sum())
+    return decided
+
+
+def check_against_restatement(cfg, inp, got, what):
+    """`got` (device dict) vs the numpy restatement: max_overlaps and gt_assignment against the overlap oracle (check_assignment),
+    then sampling, labels, gathers and the canonical transform against the restatement fed with the GPU's max_overlaps /
+    gt_assignment, which takes threshold noise out of the index comparison"""
+    ov, asg = got["max_overlaps"].cpu().numpy(), got["gt_assignment"].cpu().numpy()
+    own = ptn.restate(cfg, inp["rois"], inp["roi_scores"], inp["roi_labels"], inp["gt_boxes"], inp["fg_keys"], inp["draws"],
+                      gt_boxes_enlarged=inp.get("gt_boxes_enlarged"), overlap_fn=overlap)
+    assert close(ov, own["max_overlaps"]), f"{what}: max_overlaps off by {np.abs(ov - own['max_overlaps']).max()}"
+    decided = check_assignment(cfg, inp, ov, asg, own, what)
+    assert decided >= 0.5 * ov.size, f"{what}: only {decided} of {ov.size} assignments were clear enough to compare"
+    exp = ptn.restate(cfg, inp["rois"], inp["roi_scores"], inp["roi_labels"], inp["gt_boxes"], inp["fg_keys"], inp["draws"],
+                      gt_boxes_enlarged=inp.get("gt_boxes_enlarged"), overlaps=(ov, asg))
+    assert np.array_equal(got["frame_status"].cpu().numpy(), exp["frame_status"])
+    exp["sampled_inds"] = exp["sampled_inds"].astype(np.int32)
+    g = {k: got[k] for k in OUT_KEYS}
+    if cfg["CLS_SCORE_TYPE"] == "cls":
+        g["rcnn_cls_labels"] = g["rcnn_cls_labels"].long()
+    assert_matches(g, exp, cfg, what)
+    assert np.array_equal(got["gt_iou_of_rois"].cpu().numpy(), exp["gt_iou_of_rois"])      # a gather of the same overlaps
+    return exp
+
+
+SWEEP = [  # B, R, M, D, ROI_PER_IMAGE, by class, score type
+    (1, 1, 1, 7, 1, True, "roi_iou"), (3, 63, 2, 7, 7, True, "cls"), (1, 64, 33, 9, 128, False, "roi_iou"),
+    (3, 65, 33, 7, 512, True, "roi_iou"), (1, 257, 2, 16, 7, False, "cls"), (3, 257, 33, 7, 128, True, "roi_iou"),
+    (1, 1024, 1, 7, 512, True, "cls"), (3, 1024, 512, 7, 128, True, "roi_iou"), (1, 1024, 512, 8, 512, False, "roi_iou"),
+    (3, 257, 65, 7, 7, False, "cls"),       # M = 65: one gt past the kernel's 64-gt chunk
+]
+
+
+@pytest.mark.parametrize("B,R,M,D,P,by_class,score", SWEEP)
+def test_raw_abi_sweep(B, R, M, D, P, by_class, score, dev):
+    cfg = dict(ptn.PV_RCNN_CFG, ROI_PER_IMAGE=P, SAMPLE_ROI_BY_EACH_CLASS=by_class, CLS_SCORE_TYPE=score)
+    inp, t = random_inputs(700 + R + M + P, B, R, M, D, P, dev)
+    got = raw_call(cfg, t, dev)
+    check_against_restatement(cfg, inp, got, f"B{B} R{R} M{M} D{D} P{P}")
+
+
+def test_degenerate_draws_and_equal_keys(dev):
+    cfg = dict(ptn.PV_RCNN_CFG)
+    inp, t = random_inputs(31, 3, 257, 33, 7, 128, dev, equal_keys=True, edge_draws=True)
+    got = raw_call(cfg, t, dev)
+    check_against_restatement(cfg, inp, got, "edge draws")
+    ov, idx = got["max_overlaps"].cpu().numpy(), got["sampled_inds"].cpu().numpy()
+    for b in range(3):
+        fg, hard = np.nonzero(ov[b] >= np.float32(0.55))[0], np.nonzero((ov[b] < np.float32(0.55)) & (ov[b] >= np.float32(0.1)))[0]
+        easy = np.nonzero(ov[b] < np.float32(0.1))[0]
+        assert len(fg) > 64 and len(hard) and len(easy)
+        assert np.array_equal(idx[b, :64], fg[:64])                      # equal keys: the tie breaks by ascending roi index
+        n_hard = min(int(64 * 0.8), len(hard))
+        for s in range(64, 128):                                         # draw 0 -> first candidate, draw just below 1 -> last
+            cand = hard if s < 64 + n_hard else easy
+            assert idx[b, s] == (cand[0] if s % 2 == 0 else cand[-1]), (b, s)
+    # fg only, with replacement from the draws
+    inp["gt_boxes"][:] = 0
+    inp["gt_boxes"][:, 0] = [10, 0, -1, 4, 2, 1.5, 0.3, 1]
+    inp["rois"][:] = inp["gt_boxes"][:, :1, :7]
+    inp["rois"][..., 0] += np.linspace(0, 0.3, 257, dtype=np.float32)
+    inp["roi_labels"][:] = 1
+    t = {k: torch.from_numpy(v).to(dev) for k, v in inp.items()}
+    got = raw_call(cfg, t, dev)
+    check_against_restatement(cfg, inp, got, "fg only")
+    assert (got["max_overlaps"] >= 0.55).all()
+    idx = got["sampled_inds"].cpu().numpy()
+    assert (idx[:, ::2] == 0).all() and (idx[:, 1::2] == 256).all()
+
+
+def test_deterministic(dev):
+    cfg = dict(ptn.PV_RCNN_CFG)
+    _, t = random_inputs(77, 4, 512, 40, 7, 128, dev)
+    a, b = raw_call(cfg, t, dev), raw_call(cfg, t, dev)
+    for k in a:
+        assert torch.equal(a[k].view(torch.uint8), b[k].view(torch.uint8)), k
+
+
+# ------------------------------------------------------------------------------------------------ the layer on its default RNG
+def pv_batch(dev, seed=5000):
+    boxes, scores, labels, gt = synth.rcnn_target_inputs(seed)           # bs 8, R 512, M 40, three classes
+    inp = dict(rois=boxes, roi_scores=scores, roi_labels=labels, gt_boxes=gt)
+    return batch_of(inp, dev)[0]
+
+
+def test_no_host_sync_on_the_default_rng(dev):
+    batch = pv_batch(dev)
+    head = head_of(ptn.PV_RCNN_CFG)
+    head.assign_targets(batch)
+    torch.cuda.synchronize()
+    torch.cuda.set_sync_debug_mode("error")
+    try:
+        out = head.assign_targets(batch)
+        layer = head.proposal_target_layer.forward(batch)
+    finally:
+        torch.cuda.set_sync_debug_mode(0)
+    assert out["rois"].shape == (8, 128, 7) and layer["gt_of_rois"].shape == (8, 128, 8)
+
+
+def test_same_generator_seed_gives_the_same_targets(dev):
+    batch = pv_batch(dev)
+    head = head_of(ptn.PV_RCNN_CFG)
+    runs = [head.assign_targets(batch, generator=torch.Generator(device=dev).manual_seed(s)) for s in (3, 3, 4)]
+    for k in runs[0]:
+        assert torch.equal(runs[0][k].view(torch.uint8), runs[1][k].view(torch.uint8)), k
+    assert not torch.equal(runs[0]["sampled_inds"], runs[2]["sampled_inds"])
+
+
+def test_default_rng_samples_meet_the_quotas(dev):
+    batch = pv_batch(dev)
+    out = head_of(ptn.PV_RCNN_CFG).assign_targets(batch)
+    assert not out["frame_status"].any()
+    ov, idx = out["max_overlaps"].cpu().numpy(), out["sampled_inds"].cpu().numpy()
+    for b in range(8):
+        fg = set(np.nonzero(ov[b] >= np.float32(0.55))[0])
+        hard = set(np.nonzero((ov[b] < np.float32(0.55)) & (ov[b] >= np.float32(0.1)))[0])
+        easy = set(np.nonzero(ov[b] < np.float32(0.1))[0])
+        assert len(fg) >= 64 and hard and easy
+        n_hard = min(int(64 * 0.8), len(hard))
+        picks = idx[b]
+        assert len(set(picks[:64])) == 64 and set(picks[:64]) <= fg                       # without replacement, fg >= the quota
+        assert set(picks[64:64 + n_hard]) <= hard and set(picks[64 + n_hard:]) <= easy    # the quotas, slot by slot
+    assert torch.equal(out["gt_iou_of_rois"], torch.gather(out["max_overlaps"], 1, out["sampled_inds"].long()))
+
+
+def test_nan_frame_raises_its_flag_and_leaves_the_others_alone(dev):
+    cfg = dict(ptn.PV_RCNN_CFG)
+    inp, t = random_inputs(91, 3, 65, 12, 7, 128, dev)
+    clean = raw_call(cfg, t, dev)
+    inp["rois"][1] = np.nan
+    inp["roi_labels"][1] = int(inp["gt_boxes"][1, 0, 7])                 # a label that has a gt: the overlaps are evaluated
+    t = {k: torch.from_numpy(v).to(dev) for k, v in inp.items()}
+    got = raw_call(cfg, t, dev)
+    assert got["frame_status"].tolist() == [0, 1, 0]
+    assert torch.isnan(got["max_overlaps"][1]).all()
+    for k in OUT_KEYS[:-1]:
+        assert not got[k][1].any(), f"{k} of the failed frame is not zero"
+        assert torch.equal(got[k][[0, 2]], clean[k][[0, 2]]), k
+
+
+# ------------------------------------------------------------------------------------------------ PV-RCNN
+def test_pvrcnn_rcnn_targets_on_proposals_and_in_a_graph(dev):
+    from lidardetection_amd.pvrcnn import PVRCNNKitti
+    B = 2
+    frames = [synth.cloud_ring(2000 + f)[:12000] for f in range(B)]
+    sizes = [len(f) for f in frames]
+    pts = torch.from_numpy(np.concatenate(frames, 0)).to(dev)
+    offs = torch.tensor(np.concatenate([[0], np.cumsum(sizes)]), dtype=torch.int32, device=dev)
+    torch.manual_seed(0)
+    m = PVRCNNKitti(batch_size=B, n_max=max(sizes), device=dev).randomize_for_bench(3)
+    with torch.no_grad():
+        _, _, head = m.trunk(pts, offs)
+        rois, roi_scores, roi_labels, num, _ = m.proposals(head)
+    R = rois.shape[1]
+    assert R == 100 and roi_labels.dtype == torch.int64
+    # gts: a few of the proposals themselves, nudged, with the proposal's class; zero padded to 12 rows
+    gt = torch.zeros(B, 12, 8, device=dev)
+    gt[:, :6, :7] = rois[:, 0:12:2] + 0.05
+    gt[:, :6, 7] = roi_labels[:, 0:12:2].float()
+    layer = ProposalTargetLayer(AttrDict(ptn.PV_RCNN_CFG))
+    fg_keys, draws = layer.random_inputs(rois, torch.Generator(device=dev).manual_seed(11))
+    out = m.rcnn_targets(rois, roi_scores, roi_labels, gt, fg_keys=fg_keys, draws=draws)
+    shapes = dict(rois=(B, 128, 7), gt_of_rois=(B, 128, 8), gt_of_rois_src=(B, 128, 8), gt_iou_of_rois=(B, 128), roi_scores=(B, 128),
+                  roi_labels=(B, 128), reg_valid_mask=(B, 128), rcnn_cls_labels=(B, 128), sampled_inds=(B, 128), frame_status=(B,))
+    for k, s in shapes.items():
+        assert tuple(out[k].shape) == s, (k, tuple(out[k].shape))
+    assert out["roi_labels"].dtype == out["reg_valid_mask"].dtype == torch.int64
+    assert out["rcnn_cls_labels"].dtype == torch.float32 and out["sampled_inds"].dtype == out["frame_status"].dtype == torch.int32
+    assert not out["frame_status"].any() and int(out["reg_valid_mask"].sum()) > 0
+    src = out["gt_of_rois_src"][..., :7]
+    for b in range(B):                      # every source row is a row of the frame's gt_boxes
+        assert (src[b][:, None, :] == gt[b, None, :, :7]).all(-1).any(-1).all()
+    assert torch.equal(out["rois"], torch.gather(rois, 1, out["sampled_inds"].long().unsqueeze(-1).expand(-1, -1, 7)))
+    # hipGraph: capture one call, replay it, compare with the eager result on the same random numbers
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream(dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side):
+        m.rcnn_targets(rois, roi_scores, roi_labels, gt, fg_keys=fg_keys, draws=draws)
+    torch.cuda.current_stream(dev).wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        captured = m.rcnn_targets(rois, roi_scores, roi_labels, gt, fg_keys=fg_keys, draws=draws)
+    for v in captured.values():
+        v.zero_()
+    graph.replay()
+    torch.cuda.synchronize()
+    for k in out:
+        assert torch.equal(captured[k].view(torch.uint8), out[k].view(torch.uint8)), k
