@@ -659,6 +659,40 @@ int lidar_anchor_loss_backward(const float *const *cls, const float *const *box,
                                const float *grad_losses, float *const *d_cls, float *const *d_box, float *const *d_dir, void *ws,
                                size_t ws_bytes, void *stream);
 
+/* ------------------------------------------------------------------ RoI-head loss (training), forward + backward
+ * RoIHeadTemplate.get_loss (pcdet/models/roi_heads/roi_head_template.py:133-233: get_box_cls_layer_loss with CLS_LOSS
+ * BinaryCrossEntropy, get_box_reg_layer_loss with REG_LOSS smooth-l1 and CORNER_LOSS_REGULARIZATION) on what the target layer
+ * writes, for all n = batch * roi_per_image rows: ONE forward launch on the caller's stream, no host read, no allocation, no atomics,
+ * bitwise reproducible, graph-capturable (csrc/roi_loss.hip).
+ *   rcnn_cls (n, 1) f32 logits, rcnn_reg (n, 7) f32, rois (batch, P, 7) f32, gt_of_rois (batch, P, 8) f32 in the roi's canonical
+ *   frame, gt_of_rois_src (batch, P, 8) f32 before the transform, reg_valid_mask (batch, P) i64, rcnn_cls_labels (batch, P) f32
+ *   (soft labels in [0, 1] or 1 / 0 / -1; a row is valid when its label is >= 0).  Inputs are never written.
+ *   weights HOST (3): rcnn_cls_weight, rcnn_reg_weight, rcnn_corner_weight; code_weights HOST (7); flags: 1 corner regulariser.
+ *   cls    = sum_valid bce(x, t) / max(n_valid, 1) * w_cls, bce in the stable form max(x, 0) - x t + log1p(exp(-|x|)) (equal to the
+ *            reference's binary_cross_entropy(sigmoid(x), t) for |x| < 27.6, where its clamps do not engage; continued beyond)
+ *   reg    = sum_fg sum_7 smoothL1((pred - target) * code_w, beta 1/9) / max(fg_sum, 1) * w_reg, fg = reg_valid_mask > 0, target =
+ *            ResidualCoder.encode_torch(gt_of_rois[:7], roi with centre and heading zeroed), sizes clamped at 1e-5, a NaN target
+ *            takes the prediction; non-fg rows are skipped
+ *   corner = mean_fg mean_8 smoothL1(min(|p - g|, |p - g_flip|), beta 1) * w_corner on the corners of the decoded prediction and
+ *            of gt_of_rois_src[:7] (get_corner_loss_lidar); 0 without fg rows or without the flag
+ *   forward -> out (5) DEVICE f32: cls, reg, corner, fg_sum, n_valid.  The rows' gradient pieces and the two counts stay in the
+ *       workspace; backward takes the same workspace, weights and flags.  batch 0: no kernel, out is zeroed.
+ *   backward: grad_out (3) DEVICE f32 (upstream gradients of cls, reg, corner) -> d_rcnn_cls (n, 1), d_rcnn_reg (n, 7); either may
+ *       be NULL (not written).
+ * Supported (lidar_roi_loss_supported, pure host; everything else is refused with LIDAR_ERR_ARG before any launch): roi_dim 7,
+ * gt_dim 8, reg_dim 7, cls_dim 1 (ResidualCoder without sin/cos, class-agnostic regression, no tracking info), batch >= 0,
+ * 1 <= roi_per_image <= 512, batch * roi_per_image <= 65536. */
+#define LIDAR_ROI_LOSS_MAX_SAMPLES 512
+#define LIDAR_ROI_LOSS_MAX_ROWS 65536
+int lidar_roi_loss_supported(int batch, int roi_per_image, int roi_dim, int gt_dim, int reg_dim, int cls_dim);
+size_t lidar_roi_loss_workspace_bytes(int batch, int roi_per_image);
+int lidar_roi_loss_forward(const float *rcnn_cls, const float *rcnn_reg, const float *rois, const float *gt_of_rois,
+                           const float *gt_of_rois_src, const long long *reg_valid_mask, const float *rcnn_cls_labels, int batch,
+                           int roi_per_image, const float *weights, const float *code_weights, int flags, float *out, void *ws,
+                           size_t ws_bytes, void *stream);
+int lidar_roi_loss_backward(int batch, int roi_per_image, const float *weights, const float *code_weights, int flags,
+                            const float *grad_out, float *d_rcnn_cls, float *d_rcnn_reg, void *ws, size_t ws_bytes, void *stream);
+
 /* HeightCompression in one pass (pcdet/models/backbones_2d/map_to_bev/height_compression.py:21-24): the (N, C*D, H, W) BEV
  * map of a sparse tensor written directly channels-last: out[b][h][w][c*D + d]; D <= 4, channels % 4 == 0; same workspace
  * as lidar_sparse_to_dense. */

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import anchor_post
+from . import anchor_post, roi_loss
 from .ext import iou3d_nms_cuda
 from .pcdet.ops.pointnet2 import _common as pn_common
 from .pcdet.ops.pointnet2.pointnet2_batch import pointnet2_utils as pn_batch
@@ -42,6 +42,9 @@ VSA_SOURCES = {
 # pv_rcnn.yaml:190-202: ROI_HEAD.TARGET_CONFIG
 TARGET_CONFIG = dict(ROI_PER_IMAGE=128, FG_RATIO=0.5, SAMPLE_ROI_BY_EACH_CLASS=True, CLS_SCORE_TYPE="roi_iou", CLS_FG_THRESH=0.75,
                      CLS_BG_THRESH=0.25, CLS_BG_THRESH_LO=0.1, HARD_BG_RATIO=0.8, REG_FG_THRESH=0.55)
+# pv_rcnn.yaml:204-218: ROI_HEAD.LOSS_CONFIG
+LOSS_CONFIG = dict(CLS_LOSS="BinaryCrossEntropy", REG_LOSS="smooth-l1", CORNER_LOSS_REGULARIZATION=True,
+                   LOSS_WEIGHTS=dict(rcnn_cls_weight=1.0, rcnn_reg_weight=1.0, rcnn_corner_weight=1.0, code_weights=[1.0] * 7))
 
 
 def bilinear_bev(bev_nhwc, x, y):
@@ -228,6 +231,18 @@ class PVRCNNKitti(SECONDKitti):
         if gt_boxes_enlarged is not None:
             batch["gt_boxes_enlarged"] = gt_boxes_enlarged
         return cached[1].assign_targets(batch, fg_keys=fg_keys, draws=draws, generator=generator)
+
+    def rcnn_loss(self, rcnn_cls, rcnn_reg, targets_dict, loss_config=None):
+        """RoIHeadTemplate.get_loss (roi_head_template.py:222-233) on what rcnn_targets() returns and the head's rcnn_cls (B * P, 1)
+        / rcnn_reg (B * P, 7) -> (loss, stats): loss = cls + reg + corner, a differentiable 0-dim tensor; stats the device record
+        [cls, reg, corner, fg_sum, n_valid].  One HIP launch (one more in backward), no host synchronisation; loss_config
+        overrides entries of pv_rcnn.yaml's LOSS_CONFIG."""
+        cfg = dict(LOSS_CONFIG, **(loss_config or {}))
+        cached = self.__dict__.get("_rcnn_loss_spec")
+        if cached is None or cached[0] != cfg:
+            cached = self.__dict__["_rcnn_loss_spec"] = (cfg, roi_loss.spec_from_cfg(dict(LOSS_CONFIG=cfg)))
+        cls, reg, corner, stats = roi_loss.roi_head_loss(rcnn_cls, rcnn_reg, targets_dict, cached[1])
+        return cls + reg + corner, stats
 
     def keypoints(self, points, point_offsets, sizes):
         """get_sampled_points (voxel_set_abstraction.py:119-157) -> (B, num_keypoints, 3): FPS per frame, starting at point 0"""
