@@ -693,6 +693,49 @@ int lidar_roi_loss_forward(const float *rcnn_cls, const float *rcnn_reg, const f
 int lidar_roi_loss_backward(int batch, int roi_per_image, const float *weights, const float *code_weights, int flags,
                             const float *grad_out, float *d_rcnn_cls, float *d_rcnn_reg, void *ws, size_t ws_bytes, void *stream);
 
+/* ------------------------------------------------------------------ point-head targets and loss (training)
+ * PointHeadTemplate.assign_stack_targets with set_ignore_flag=True and get_cls / box / part_layer_loss
+ * (pcdet/models/dense_heads/point_head_template.py:49-191) for a stacked point set: ONE launch for the targets, two for the loss
+ * forward, ONE for its backward, all on the caller's stream; no host read, no allocation, no atomics, bitwise reproducible
+ * (csrc/point_head.hip).
+ *   points (n, 4) f32 [bs_idx, x, y, z] in any frame order (a bs_idx outside [0, batch) keeps label 0 and zero targets);
+ *   gt_boxes (batch, m, 8) f32 [box7 | class], zero rows as padding (they take part, enlarged too, as in the reference);
+ *   extra_width HOST (3); flags: 1 box labels, 2 part labels; mean_size HOST (n_mean, 3) or NULL with n_mean 0
+ *   (PointResidualCoder use_mean_size; class id c reads row c - 1, class 0 the last row, classes beyond n_mean wrap).
+ *   targets -> point_cls_labels (n) i64: fg (inside the first containing gt row = owner) 1 if num_class == 1 else (long)class,
+ *       -1 for fg XOR inside any enlarged row, else 0; point_box_labels (n, 8) f32 PointResidualCoder.encode_torch on fg rows, 0
+ *       elsewhere; point_part_labels (n, 3) f32 rotate_z(p - centre, -rz) / dims + 0.5 on fg rows, 0 elsewhere; point_box_idx (n)
+ *       i32 owner row or -1.  Every element is written.
+ *   loss: point_cls_preds (n, num_class), point_box_preds (n, 8), point_part_preds (n, 3) f32, each may be NULL (term skipped,
+ *       record entry 0); weights HOST (3): point_cls_weight, point_box_weight, point_part_weight; code_weights HOST (8).
+ *       cls  = sum_{label >= 0} focal(x, onehot(label)) / max(npos, 1) * w_cls (alpha 0.25, gamma 2), npos = #(label > 0)
+ *       box  = sum_{label > 0} sum_8 smoothL1((pred - label) * code_w, beta 1/9) / max(npos, 1) * w_box, a NaN label takes the pred
+ *       part = sum_{label > 0} sum_3 bce_logits(x, t) / (3 max(npos, 1)) * w_part, bce in the stable logits form
+ *   forward -> out (4) DEVICE f32: cls, box, part, npos; the workspace (lidar_point_loss_ws_bytes(n)) keeps the tile partials and
+ *       the count for backward.  n 0: no kernel, out is zeroed.
+ *   backward: the same inputs and workspace, grad_out (3) DEVICE f32 -> d_cls_preds, d_box_preds, d_part_preds; any may be NULL.
+ * Supported (lidar_point_head_supported, pure host; everything else is refused with LIDAR_ERR_ARG before any launch):
+ * 0 <= n <= 2^20, 1 <= batch <= 64, 0 <= m <= 128, gt_dim 8, 1 <= num_class <= 8, 0 <= n_mean <= 8. */
+#define LIDAR_POINT_HEAD_MAX_POINTS (1 << 20)
+#define LIDAR_POINT_HEAD_MAX_BATCH 64
+#define LIDAR_POINT_HEAD_MAX_GT 128
+#define LIDAR_POINT_HEAD_MAX_CLASS 8
+#define LIDAR_POINT_HEAD_MAX_MEAN 8
+int lidar_point_head_supported(long long n, int batch, int m, int gt_dim, int num_class, int n_mean);
+int lidar_point_targets(const float *points, long long n, const float *gt_boxes, int batch, int m, int gt_dim,
+                        const float *extra_width, int num_class, int flags, const float *mean_size, int n_mean,
+                        long long *point_cls_labels, float *point_box_labels, float *point_part_labels, int *point_box_idx,
+                        void *stream);
+size_t lidar_point_loss_ws_bytes(long long n);
+int lidar_point_loss_forward(const float *point_cls_preds, const float *point_box_preds, const float *point_part_preds,
+                             const long long *point_cls_labels, const float *point_box_labels, const float *point_part_labels,
+                             long long n, int num_class, const float *weights, const float *code_weights, float *out, void *ws,
+                             size_t ws_bytes, void *stream);
+int lidar_point_loss_backward(const float *point_cls_preds, const float *point_box_preds, const float *point_part_preds,
+                              const long long *point_cls_labels, const float *point_box_labels, const float *point_part_labels,
+                              long long n, int num_class, const float *weights, const float *code_weights, const float *grad_out,
+                              float *d_cls_preds, float *d_box_preds, float *d_part_preds, void *ws, size_t ws_bytes, void *stream);
+
 /* HeightCompression in one pass (pcdet/models/backbones_2d/map_to_bev/height_compression.py:21-24): the (N, C*D, H, W) BEV
  * map of a sparse tensor written directly channels-last: out[b][h][w][c*D + d]; D <= 4, channels % 4 == 0; same workspace
  * as lidar_sparse_to_dense. */

@@ -152,6 +152,11 @@ SIGNATURES = {
     "lidar_roi_loss_workspace_bytes": (sz, [i32, i32]),
     "lidar_roi_loss_forward": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, vp, vp, sz, vp]),
     "lidar_roi_loss_backward": (i32, [i32, i32, vp, vp, i32, vp, vp, vp, vp, sz, vp]),
+    "lidar_point_head_supported": (i32, [C.c_longlong, i32, i32, i32, i32, i32]),
+    "lidar_point_targets": (i32, [vp, C.c_longlong, vp, i32, i32, i32, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp]),
+    "lidar_point_loss_ws_bytes": (sz, [C.c_longlong]),
+    "lidar_point_loss_forward": (i32, [vp, vp, vp, vp, vp, vp, C.c_longlong, i32, vp, vp, vp, vp, sz, vp]),
+    "lidar_point_loss_backward": (i32, [vp, vp, vp, vp, vp, vp, C.c_longlong, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
     "lidar_rotate_iou_eval": (i32, [vp, i32, vp, i32, i32, vp, vp]),
     "lidar_boxes_iou_bev_cpu": (i32, [vp, i32, vp, i32, vp]),
     "lidar_points_in_boxes_cpu": (i32, [vp, i32, vp, i32, vp]),

@@ -1,0 +1,245 @@
+"""Mirror of pcdet/models/dense_heads/point_head_template.py: PointHeadTemplate with the reference's constructor, build_losses,
+make_fc_layers, assign_stack_targets, get_cls_layer_loss / get_box_layer_loss / get_part_layer_loss and generate_predicted_boxes.
+
+Only the interface is the reference's (names, arguments, dict keys); the bodies are this project's.
+
+On CUDA tensors inside the kernels' declared support the targets are one HIP launch and the three loss terms one fused call
+(lidardetection_amd/point_head.py); get_loss of the subclasses evaluates the terms once and fills tb_dict from one device-to-host
+copy of the record, while each get_*_layer_loss called on its own evaluates them anew (nothing is kept between calls, so no graph
+or tensor outlives the call that made it).  Everything else (CPU tensors, use_ball_constraint, an extend_gt_boxes handed in by the
+caller, shapes or configs the kernels refuse) takes a torch formulation of the same math, written without the per-frame loop; its
+part term is the stable logits form of BCE as well, so both paths compute the same loss."""
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from .... import point_head
+
+
+def _get(cfg, key, default=None):
+    return cfg.get(key, default) if hasattr(cfg, "get") else getattr(cfg, key, default)
+
+
+def _in_boxes(pts, boxes):
+    """check_pt_in_box3d (roiaware_pool3d_kernel.cu:23-36) of every point (n, 3) against every box (n, M, 7) of its frame -> (n, M)
+    bool and the local x, y; the comparisons are promoted to float64 as in the kernel"""
+    d = pts[:, None, :] - boxes[..., 0:3]
+    ca, sa = torch.cos(-boxes[..., 6]), torch.sin(-boxes[..., 6])
+    lx, ly = d[..., 0] * ca + d[..., 1] * (-sa), d[..., 0] * sa + d[..., 1] * ca
+    h = boxes[..., 3:6].double() / 2.0
+    inside = (d[..., 2].abs().double() <= h[..., 2]) & (lx.abs().double() < h[..., 0] + 1e-5) & (ly.abs().double() < h[..., 1] + 1e-5)
+    return inside, lx, ly
+
+
+def _first(mask):
+    """index of the first True along dim 1, -1 without one"""
+    if mask.shape[1] == 0:
+        return mask.new_full((mask.shape[0],), -1, dtype=torch.long)
+    idx = torch.argmax(mask.to(torch.uint8), dim=1)
+    return torch.where(mask.any(dim=1), idx, torch.full_like(idx, -1))
+
+
+class PointHeadTemplate(nn.Module):
+    def __init__(self, model_cfg, num_class):
+        super().__init__()
+        self.model_cfg = model_cfg
+        self.num_class = num_class
+        self.build_losses(self.model_cfg.LOSS_CONFIG)
+        self.forward_ret_dict = None
+        self._spec = None           # (PointHeadSpec or None) once asked for
+
+    def build_losses(self, losses_cfg):
+        """the reference registers a focal-loss module and picks reg_loss_func; here the fused kernels carry both (alpha 0.25,
+        gamma 2; WeightedSmoothL1Loss beta 1/9) and the torch formulation below restates them, so only the choice is kept"""
+        self.reg_loss_type = _get(losses_cfg, 'LOSS_REG', None)
+
+    def fused_spec(self):
+        """-> the fused path's PointHeadSpec, or None for a config it refuses"""
+        if self._spec is None:
+            try:
+                self._spec = (point_head.spec_from_cfg(self.model_cfg, self.num_class),)
+            except NotImplementedError:
+                self._spec = (None,)
+        return self._spec[0]
+
+    @staticmethod
+    def make_fc_layers(fc_cfg, input_channels, output_channels):
+        """[Linear (no bias) -> BatchNorm1d -> ReLU] per width in fc_cfg, then a biased Linear to output_channels"""
+        widths = [input_channels, *fc_cfg]
+        stack = []
+        for c_in, c_out in zip(widths[:-1], widths[1:]):
+            stack += [nn.Linear(c_in, c_out, bias=False), nn.BatchNorm1d(c_out), nn.ReLU()]
+        return nn.Sequential(*stack, nn.Linear(widths[-1], output_channels, bias=True))
+
+    # ---------------------------------------------------------------- targets
+    def assign_stack_targets(self, points, gt_boxes, extend_gt_boxes=None, ret_box_labels=False, ret_part_labels=False,
+                             set_ignore_flag=True, use_ball_constraint=False, central_radius=2.0):
+        """points (N1 + N2 + ..., 4) [bs_idx, x, y, z], gt_boxes (B, M, 8), extend_gt_boxes (B, M, 8) or None -> targets_dict with
+        point_cls_labels (N) long (0 background, -1 ignored), point_box_labels (N, 8), point_part_labels (N, 3) and, beyond the
+        reference, point_box_idx (N) int32.
+
+        extend_gt_boxes=None (what the heads of this package pass) means gt_boxes enlarged by the config's GT_EXTRA_WIDTH; only
+        then can the fused kernel run, because it enlarges by those widths itself.  Boxes handed in by the caller may be anything
+        and could be compared with the config only by reading them back, so they take the torch formulation."""
+        if points.dim() != 2 or points.shape[1] != 4:
+            raise AssertionError(f'points must be (N, 4), got {tuple(points.shape)}')
+        for name, boxes in (('gt_boxes', gt_boxes), ('extend_gt_boxes', extend_gt_boxes)):
+            if boxes is not None and (boxes.dim() != 3 or boxes.shape[2] != 8):
+                raise AssertionError(f'{name} must be (B, M, 8), got {tuple(boxes.shape)}')
+        if set_ignore_flag == use_ball_constraint:
+            raise AssertionError('exactly one of set_ignore_flag and use_ball_constraint')
+        spec = self.fused_spec()
+        fused = (spec is not None and set_ignore_flag and extend_gt_boxes is None and points.is_cuda
+                 and points.dtype == torch.float32 and gt_boxes.dtype == torch.float32 and (spec.box_coder or not ret_box_labels)
+                 and point_head.supported(points.shape[0], gt_boxes.shape[0], gt_boxes.shape[1], 8, self.num_class, len(spec.mean_size)))
+        with torch.no_grad():
+            if fused:
+                return point_head.assign_point_targets(points, gt_boxes, spec, ret_box_labels, ret_part_labels)
+            return self._torch_targets(points, gt_boxes, extend_gt_boxes, ret_box_labels, ret_part_labels, use_ball_constraint,
+                                       central_radius)
+
+    def _torch_targets(self, points, gt_boxes, extend_gt_boxes, ret_box_labels, ret_part_labels, use_ball_constraint, central_radius):
+        N, (B, M) = points.shape[0], gt_boxes.shape[:2]
+        bs, pts = points[:, 0], points[:, 1:4]
+        frame = bs.long()
+        valid = (bs == frame.to(bs.dtype)) & (frame >= 0) & (frame < B)
+        f = torch.where(valid, frame, torch.zeros_like(frame))
+        gts = gt_boxes[f]                                                      # (N, M, 8)
+        inside, lx, ly = _in_boxes(pts, gts[..., 0:7])
+        owner = torch.where(valid, _first(inside), torch.full_like(frame, -1))
+        fg = owner >= 0
+        labels = points.new_zeros(N).long()
+        if use_ball_constraint:
+            row = gts[torch.arange(N, device=points.device), owner] if M else gts.new_zeros((N, 8))      # owner -1: the last row
+            centers = row[:, 0:3].clone()
+            centers[:, 2] += row[:, 5] / 2
+            fg = fg & ((centers - pts).norm(dim=1) < central_radius)
+        else:
+            if extend_gt_boxes is None:
+                extend_gt_boxes = gt_boxes.clone()
+                extend_gt_boxes[..., 3:6] += gt_boxes.new_tensor(self.model_cfg.TARGET_CONFIG.GT_EXTRA_WIDTH)
+            ext, _, _ = _in_boxes(pts, extend_gt_boxes[f][..., 0:7])
+            labels[(fg ^ ext.any(dim=1)) & valid] = -1
+        own = owner[fg]
+        row = gts[fg, own] if M else gts.new_zeros((0, 8))                     # (n_fg, 8)
+        labels[fg] = 1 if self.num_class == 1 else row[:, -1].long()
+        box = part = None
+        if ret_box_labels:
+            box = gt_boxes.new_zeros((N, 8))
+            if row.shape[0]:
+                box[fg] = self.box_coder.encode_torch(gt_boxes=row[:, :-1], points=pts[fg], gt_classes=row[:, -1].long())
+        if ret_part_labels:
+            part = gt_boxes.new_zeros((N, 3))
+            local = torch.stack([lx[fg, own], ly[fg, own], pts[fg, 2] - row[:, 2]], dim=1) if M else pts[fg]
+            # the reference's encode_torch clamps the rows in place, so part labels made after box labels see dims >= 1e-5
+            part[fg] = local / (torch.clamp_min(row[:, 3:6], 1e-5) if ret_box_labels else row[:, 3:6]) + 0.5
+        return {'point_cls_labels': labels, 'point_box_labels': box, 'point_part_labels': part,
+                'point_box_idx': owner.to(torch.int32)}
+
+    # ---------------------------------------------------------------- losses
+    def _terms(self):
+        """-> (cls, box, part, stats) of the current forward_ret_dict: weighted 0-dim tensors (0 for an absent term) and the record
+        [cls, box, part, pos_num].  Every call evaluates anew."""
+        d = self.forward_ret_dict
+        cls_preds = d['point_cls_preds'].view(-1, self.num_class)
+        box_preds, part_preds = d.get('point_box_preds'), d.get('point_part_preds')
+        spec = self.fused_spec()
+        if (spec is not None and cls_preds.is_cuda and cls_preds.dtype == torch.float32 and (box_preds is None or spec.box_coder)
+                and point_head.supported(cls_preds.shape[0], 1, 0, 8, self.num_class, 0)):
+            return point_head.point_head_loss(cls_preds, box_preds, part_preds, d, spec)
+        return self._torch_terms(cls_preds, box_preds, part_preds, d)
+
+    def _torch_terms(self, cls_preds, box_preds, part_preds, d):
+        lw = self.model_cfg.LOSS_CONFIG.LOSS_WEIGHTS
+        labels = d['point_cls_labels'].view(-1)
+        pos = labels > 0
+        npos = pos.sum().to(cls_preds.dtype)
+        norm = torch.clamp(npos, min=1.0)
+        # SigmoidFocalClassificationLoss(alpha 0.25, gamma 2) on the one-hot targets, rows with label -1 weighing 0
+        onehot = cls_preds.new_zeros(labels.shape[0], self.num_class + 1)
+        onehot.scatter_(-1, (labels * (labels >= 0).long()).unsqueeze(-1), 1.0)
+        t = onehot[:, 1:]
+        p = torch.sigmoid(cls_preds)
+        focal = (t * 0.25 + (1 - t) * 0.75) * torch.pow(t * (1.0 - p) + (1.0 - t) * p, 2.0)
+        bce = torch.clamp(cls_preds, min=0) - cls_preds * t + torch.log1p(torch.exp(-torch.abs(cls_preds)))
+        cls = (focal * bce * ((labels >= 0).to(cls_preds.dtype) / norm).unsqueeze(-1)).sum() * lw['point_cls_weight']
+        zero = cls.new_zeros(())
+        box = part = zero
+        if box_preds is not None:
+            if self.reg_loss_type != 'WeightedSmoothL1Loss':
+                raise TypeError(f"LOSS_REG {self.reg_loss_type!r}: the reference hands F.smooth_l1_loss / F.l1_loss a `weights=` "
+                                "argument they do not take; use WeightedSmoothL1Loss")
+            target = d['point_box_labels']
+            target = torch.where(torch.isnan(target), box_preds, target)
+            n = ((box_preds - target) * box_preds.new_tensor(lw['code_weights']).view(1, -1)).abs()
+            beta = 1.0 / 9.0
+            sl1 = torch.where(n < beta, 0.5 * n ** 2 / beta, n - 0.5 * beta)
+            box = (sl1 * (pos.to(box_preds.dtype) / norm).unsqueeze(-1)).sum() * lw['point_box_weight']
+        if part_preds is not None:
+            # stable logits form, as the kernel: max(x, 0) - x t + log1p(exp(-|x|)); the labels of the other rows carry no weight
+            # (and may be NaN), so they are replaced before the product
+            t = torch.where(pos.unsqueeze(-1), d['point_part_labels'], torch.zeros_like(part_preds))
+            e = F.binary_cross_entropy_with_logits(part_preds, t, reduction='none')      # its gradient is sigmoid(x) - t, at x == 0 too
+            part = (e.sum(dim=-1) * pos.to(part_preds.dtype)).sum() / (3 * norm) * lw['point_part_weight']
+        stats = torch.stack([cls.detach(), box.detach(), part.detach(), npos]).to(torch.float32)
+        return cls, box, part, stats
+
+    def get_cls_layer_loss(self, tb_dict=None):
+        cls, _, _, stats = self._terms()
+        tb_dict = {} if tb_dict is None else tb_dict
+        cls_v, _, _, pos = stats.tolist()
+        tb_dict.update({'point_loss_cls': cls_v, 'point_pos_num': pos})
+        return cls, tb_dict
+
+    def get_part_layer_loss(self, tb_dict=None):
+        _, _, part, stats = self._terms()
+        tb_dict = {} if tb_dict is None else tb_dict
+        tb_dict.update({'point_loss_part': stats.tolist()[2]})
+        return part, tb_dict
+
+    def get_box_layer_loss(self, tb_dict=None):
+        _, box, _, stats = self._terms()
+        tb_dict = {} if tb_dict is None else tb_dict
+        tb_dict.update({'point_loss_box': stats.tolist()[1]})
+        return box, tb_dict
+
+    def _get_loss(self, tb_dict, box, part):
+        """the heads' get_loss: the sum of the terms the head has, tb_dict filled in the reference's key order from ONE copy of
+        the record"""
+        tb_dict = {} if tb_dict is None else tb_dict
+        cls, box_t, part_t, stats = self._terms()
+        cls_v, box_v, part_v, pos = stats.tolist()
+        tb_dict.update({'point_loss_cls': cls_v, 'point_pos_num': pos})
+        loss = cls
+        if part:
+            tb_dict['point_loss_part'] = part_v
+            loss = loss + part_t
+        if box:
+            tb_dict['point_loss_box'] = box_v
+            loss = loss + box_t
+        return loss, tb_dict
+
+    def _stack_inputs(self, input_dict):
+        """the heads' assign_targets: point_coords (N1 + N2 + ..., 4) and gt_boxes (B, M, 8) of a batch dict, shape-checked"""
+        coords, boxes = input_dict['point_coords'], input_dict['gt_boxes']
+        if boxes.dim() != 3:
+            raise AssertionError(f'gt_boxes must be (B, M, 8), got {tuple(boxes.shape)}')
+        if coords.dim() != 2:
+            raise AssertionError(f'point_coords must be (N, 4), got {tuple(coords.shape)}')
+        return coords, boxes
+
+    def _decode_into(self, batch_dict, cls_preds, box_preds):
+        """what a head with box layers adds to batch_dict when it predicts boxes: decoded boxes, scores, frame index"""
+        scores, boxes = self.generate_predicted_boxes(points=batch_dict['point_coords'][:, 1:4], point_cls_preds=cls_preds,
+                                                      point_box_preds=box_preds)
+        batch_dict.update(batch_cls_preds=scores, batch_box_preds=boxes, batch_index=batch_dict['point_coords'][:, 0],
+                          cls_preds_normalized=False)
+
+    def generate_predicted_boxes(self, points, point_cls_preds, point_box_preds):
+        """points (N, 3), point_cls_preds (N, num_class), point_box_preds (N, box_code_size) -> the scores unchanged and the boxes
+        decoded against the points with the mean size of each point's best class (1-based)"""
+        best = point_cls_preds.argmax(dim=-1) + 1
+        return point_cls_preds, self.box_coder.decode_torch(point_box_preds, points, best)
+
+    def forward(self, **kwargs):
+        raise NotImplementedError

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import anchor_post, roi_loss
+from . import anchor_post, point_head, roi_loss
 from .ext import iou3d_nms_cuda
 from .pcdet.ops.pointnet2 import _common as pn_common
 from .pcdet.ops.pointnet2.pointnet2_batch import pointnet2_utils as pn_batch
@@ -45,6 +45,9 @@ TARGET_CONFIG = dict(ROI_PER_IMAGE=128, FG_RATIO=0.5, SAMPLE_ROI_BY_EACH_CLASS=T
 # pv_rcnn.yaml:204-218: ROI_HEAD.LOSS_CONFIG
 LOSS_CONFIG = dict(CLS_LOSS="BinaryCrossEntropy", REG_LOSS="smooth-l1", CORNER_LOSS_REGULARIZATION=True,
                    LOSS_WEIGHTS=dict(rcnn_cls_weight=1.0, rcnn_reg_weight=1.0, rcnn_corner_weight=1.0, code_weights=[1.0] * 7))
+# pv_rcnn.yaml:146-157: POINT_HEAD (class-agnostic: one class)
+POINT_HEAD_CONFIG = dict(TARGET_CONFIG=dict(GT_EXTRA_WIDTH=[0.2, 0.2, 0.2]),
+                         LOSS_CONFIG=dict(LOSS_REG="smooth-l1", LOSS_WEIGHTS=dict(point_cls_weight=1.0)))
 
 
 def bilinear_bev(bev_nhwc, x, y):
@@ -243,6 +246,32 @@ class PVRCNNKitti(SECONDKitti):
             cached = self.__dict__["_rcnn_loss_spec"] = (cfg, roi_loss.spec_from_cfg(dict(LOSS_CONFIG=cfg)))
         cls, reg, corner, stats = roi_loss.roi_head_loss(rcnn_cls, rcnn_reg, targets_dict, cached[1])
         return cls + reg + corner, stats
+
+    def _point_spec(self, loss_config=None, target_config=None):
+        cfg = dict(TARGET_CONFIG=dict(POINT_HEAD_CONFIG["TARGET_CONFIG"], **(target_config or {})),
+                   LOSS_CONFIG=dict(POINT_HEAD_CONFIG["LOSS_CONFIG"], **(loss_config or {})))
+        cached = self.__dict__.get("_point_head_spec")
+        if cached is None or cached[0] != cfg:
+            cached = self.__dict__["_point_head_spec"] = (cfg, point_head.spec_from_cfg(cfg, 1))
+        return cached[1]
+
+    def point_targets(self, kp, gt_boxes, target_config=None):
+        """PointHeadSimple.assign_targets (point_head_simple.py:21-51) on what keypoints() returns: kp (B, K, 3), gt_boxes (B, M, 8)
+        [box | class id] -> the reference's targets_dict (point_cls_labels (B * K) int64: 1 inside a gt, -1 in its 0.2 m shell only,
+        else 0) plus point_box_idx.  One HIP launch, no host synchronisation; target_config overrides entries of pv_rcnn.yaml's
+        POINT_HEAD.TARGET_CONFIG."""
+        B, K = kp.shape[:2]
+        bs = torch.arange(B, device=kp.device, dtype=kp.dtype).view(B, 1, 1).expand(B, K, 1)
+        points = torch.cat([bs, kp], dim=-1).view(B * K, 4)
+        return point_head.assign_point_targets(points, gt_boxes, self._point_spec(target_config=target_config))
+
+    def point_loss(self, point_cls_preds, targets, loss_config=None):
+        """PointHeadSimple.get_loss (point_head_simple.py:53-59) on what point_targets() returns and the head's point_cls_preds
+        (B * K, 1) -> (loss, stats): the focal segmentation loss as a differentiable 0-dim tensor; stats the device record [cls, box,
+        part, pos_num].  Two HIP launches (one more in backward), no host synchronisation; loss_config overrides entries of
+        pv_rcnn.yaml's POINT_HEAD.LOSS_CONFIG."""
+        cls, _box, _part, stats = point_head.point_head_loss(point_cls_preds, None, None, targets, self._point_spec(loss_config=loss_config))
+        return cls, stats
 
     def keypoints(self, points, point_offsets, sizes):
         """get_sampled_points (voxel_set_abstraction.py:119-157) -> (B, num_keypoints, 3): FPS per frame, starting at point 0"""

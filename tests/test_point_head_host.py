@@ -1,0 +1,269 @@
+"""Host tests of the point-head targets and loss: the float64 restatement tests/_point_head_np.py against the reference's own run
+(tests/golden/point_head_ref.npz), the config reader, the declared support, the mirrors' torch formulation on the CPU, the
+PointResidualCoder mirror, and the point filter of the GPU sweep."""
+import itertools
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import _point_head_np as ph
+from lidardetection_amd import _lib, point_head
+from lidardetection_amd.pcdet.models import dense_heads
+from lidardetection_amd.pcdet.utils.box_coder_utils import PointResidualCoder
+from lidardetection_amd.pcdet.utils.cfg import AttrDict
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+@pytest.fixture(scope="module")
+def fx():
+    return np.load(os.path.join(GOLDEN, "point_head_ref.npz"))
+
+
+def to_cfg(d):
+    return AttrDict({k: to_cfg(v) for k, v in d.items()}) if isinstance(d, dict) else d
+
+
+def close(a, b, tol=1e-9):
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    return np.array_equal(np.isnan(a), np.isnan(b)) and np.allclose(a, b, rtol=tol, atol=tol, equal_nan=True)
+
+
+def case_loss_inputs(fx, name, tag="64"):
+    """-> (cls, box, part predictions or None, labels, box labels with the planted NaN, part labels) of a fixture case"""
+    c = ph.CASES[name]
+    pred = lambda k: fx[f"{name}_pred_{k}"].astype(np.float64) / 64 if f"{name}_pred_{k}" in fx else None      # noqa: E731
+    box = fx[f"{name}_box{tag}"].copy() if c["box"] else None
+    if c["box"]:
+        r, q = fx[f"{name}_nan"]
+        box[r, q] = np.nan
+    return pred("cls"), pred("box"), pred("part"), fx[f"{name}_labels"], box, fx[f"{name}_part{tag}"] if c["part"] else None
+
+
+def test_the_fixture_holds_the_cases_of_this_module(fx):
+    assert json.loads(str(fx["cases"])) == ph.CASES
+
+
+@pytest.mark.parametrize("name", list(ph.CASES))
+def test_restatement_reproduces_the_reference(fx, name):
+    c = ph.CASES[name]
+    extra, nc, mean, weights, cw = ph.case_spec_args(name)
+    t = ph.targets(fx[f"{name}_points"], fx[f"{name}_gt"], extra, nc, mean, c["box"], c["part"])
+    assert np.array_equal(t["labels"], fx[f"{name}_labels"]) and np.array_equal(t["owner"], fx[f"{name}_owner"])
+    if c["box"]:
+        assert close(t["box"], fx[f"{name}_box64"])
+    if c["part"]:
+        assert close(t["part"], fx[f"{name}_part64"])
+    losses, npos, grads = ph.loss(*case_loss_inputs(fx, name), nc, weights, cw)
+    assert npos == int(fx[f"{name}_pos"]) and close(losses, fx[f"{name}_loss64"])
+    for k, g in zip(("cls", "box", "part"), grads):
+        if g is None:
+            assert f"{name}_g{k}64" not in fx
+        else:
+            assert close(g, fx[f"{name}_g{k}64"]), k
+            assert np.array_equal(g == 0, fx[f"{name}_g{k}64"] == 0), k      # exact zeros in the same places
+    # what the fixture was built to hold
+    lab, own, pts, gt = fx[f"{name}_labels"], fx[f"{name}_owner"], fx[f"{name}_points"], fx[f"{name}_gt"]
+    origin = np.nonzero((pts[:, 0] == 0) & (pts[:, 1:4] == 0).all(axis=1))[0][0]
+    assert own[origin] == 6 and not gt[0, 6].any() and lab[origin] == (1 if nc == 1 else 0)
+    assert lab[pts[:, 0] == 4].tolist() == [0] and (lab[pts[:, 0] == 2] != 0).any() and (np.abs(gt[..., 6]) > np.pi).any()
+    assert (np.diff(pts[:, 0]) < 0).any() and ((pts[:, 0] == 3).sum() == (1 if name == "pointrcnn" else 0))
+    if c["box"] and mean is not None:      # class 0 reads the LAST mean size
+        assert close(t["box"][origin, 3:6], np.log(1e-5 / np.asarray(mean[-1])))
+
+
+YAML = {      # POINT_HEAD of tools/cfgs/kitti_models/{pv_rcnn,pointrcnn,PartA2}.yaml
+    "pv_rcnn": (1, dict(NAME="PointHeadSimple", CLS_FC=[256, 256], CLASS_AGNOSTIC=True, USE_POINT_FEATURES_BEFORE_FUSION=True,
+                        TARGET_CONFIG=dict(GT_EXTRA_WIDTH=[0.2, 0.2, 0.2]),
+                        LOSS_CONFIG=dict(LOSS_REG="smooth-l1", LOSS_WEIGHTS={"point_cls_weight": 1.0}))),
+    "pointrcnn": (3, dict(NAME="PointHeadBox", CLS_FC=[256, 256], REG_FC=[256, 256], CLASS_AGNOSTIC=False,
+                          USE_POINT_FEATURES_BEFORE_FUSION=False,
+                          TARGET_CONFIG=dict(GT_EXTRA_WIDTH=[0.2, 0.2, 0.2], BOX_CODER="PointResidualCoder",
+                                             BOX_CODER_CONFIG={"use_mean_size": True, "mean_size": ph.MEAN_SIZE}),
+                          LOSS_CONFIG=dict(LOSS_REG="WeightedSmoothL1Loss",
+                                           LOSS_WEIGHTS={"point_cls_weight": 1.0, "point_box_weight": 1.0, "code_weights": [1.0] * 8}))),
+    "PartA2": (1, dict(NAME="PointIntraPartOffsetHead", CLS_FC=[], PART_FC=[], CLASS_AGNOSTIC=True,
+                       TARGET_CONFIG=dict(GT_EXTRA_WIDTH=[0.2, 0.2, 0.2]),
+                       LOSS_CONFIG=dict(LOSS_REG="smooth-l1", LOSS_WEIGHTS={"point_cls_weight": 1.0, "point_part_weight": 1.0}))),
+}
+
+
+def test_spec_from_cfg_accepts_the_yaml_configs_and_refuses_the_rest():
+    for name, (nc, cfg) in YAML.items():
+        for wrap in (lambda d: d, to_cfg):
+            s = point_head.spec_from_cfg(wrap(cfg), nc)
+            assert s.num_class == nc and s.extra_width == (0.2, 0.2, 0.2) and s.cls_weight == 1.0
+            assert s.box_coder == (name == "pointrcnn") and len(s.mean_size) == (3 if name == "pointrcnn" else 0) and len(s.code_weights) == 8
+    nc, base = YAML["pointrcnn"]
+
+    def edit(**kw):
+        cfg = json.loads(json.dumps(base))
+        for path, v in kw.items():
+            d, keys = cfg, path.split("__")
+            for k in keys[:-1]:
+                d = d[k]
+            if v is None:
+                d.pop(keys[-1])
+            else:
+                d[keys[-1]] = v
+        return cfg
+    for reg in ("smooth-l1", "l1", None):      # with a box term the reference raises on these
+        with pytest.raises(NotImplementedError, match="weights="):
+            point_head.spec_from_cfg(edit(LOSS_CONFIG__LOSS_REG=reg), nc)
+    for bad in (edit(TARGET_CONFIG__BOX_CODER="ResidualCoder"), edit(TARGET_CONFIG__BOX_CODER_CONFIG__code_size=9),
+                edit(LOSS_CONFIG__LOSS_WEIGHTS__code_weights=[1.0] * 7), edit(LOSS_CONFIG__LOSS_WEIGHTS__code_weights=None),
+                edit(TARGET_CONFIG__BOX_CODER_CONFIG__mean_size=[[1.0, 1.0, 1.0]] * 9)):
+        with pytest.raises(NotImplementedError):
+            point_head.spec_from_cfg(bad, nc)
+    for n in (0, 9):
+        with pytest.raises(NotImplementedError):
+            point_head.spec_from_cfg(base, n)
+    with pytest.raises(ValueError):
+        point_head.spec_from_cfg(dict(LOSS_CONFIG=base["LOSS_CONFIG"]), nc)
+    s = point_head.spec_from_cfg(edit(TARGET_CONFIG__BOX_CODER_CONFIG={"use_mean_size": False}), nc)
+    assert s.box_coder and s.mean_size == ()
+
+
+def test_supported_predicate_at_each_bound():
+    ok = dict(n=1000, batch=4, m=10, gt_dim=8, num_class=3, n_mean=3)
+    assert point_head.supported(**ok)
+    for k, good, bad in (("n", (0, 1 << 20), (-1, (1 << 20) + 1)), ("batch", (1, 64), (0, 65)), ("m", (0, 128), (-1, 129)),
+                         ("gt_dim", (8,), (7, 9)), ("num_class", (1, 8), (0, 9)), ("n_mean", (0, 8), (-1, 9))):
+        for v in good:
+            assert point_head.supported(**dict(ok, **{k: v})), (k, v)
+        for v in bad:
+            assert not point_head.supported(**dict(ok, **{k: v})), (k, v)
+    assert (point_head.MAX_POINTS, point_head.MAX_BATCH, point_head.MAX_GT, point_head.MAX_CLASS, point_head.MAX_MEAN) == (1 << 20, 64, 128, 8, 8)
+    L = _lib.lib()
+    assert L.lidar_point_loss_ws_bytes(-1) == 0 and L.lidar_point_loss_ws_bytes(0) > 0      # N = 0 still holds the count
+    assert L.lidar_point_loss_ws_bytes(257) > 0 and L.lidar_point_loss_ws_bytes((1 << 20) + 1) == 0
+
+
+def make_head(name):
+    c = ph.CASES[name]
+    return getattr(dense_heads, c["head"])(num_class=c["num_class"], input_channels=4, model_cfg=to_cfg(c["cfg"]))
+
+
+@pytest.mark.parametrize("name", ["pv", "parta2_box"])
+def test_mirror_torch_formulation_on_cpu_tensors(fx, name):
+    c = ph.CASES[name]
+    head = make_head(name)
+    t = head.assign_targets({"point_coords": torch.from_numpy(fx[f"{name}_points"]), "gt_boxes": torch.from_numpy(fx[f"{name}_gt"])})
+    assert t["point_cls_labels"].dtype == torch.int64 and np.array_equal(t["point_cls_labels"].numpy(), fx[f"{name}_labels"])
+    assert np.array_equal(t["point_box_idx"].numpy(), fx[f"{name}_owner"])
+    if c["box"]:
+        assert close(t["point_box_labels"].numpy(), fx[f"{name}_box64"], 1e-4)
+    if c["part"]:
+        assert close(t["point_part_labels"].numpy(), fx[f"{name}_part64"], 1e-4)
+    cls, box, part, lab, box_l, part_l = case_loss_inputs(fx, name, "32")
+    leaf = lambda a: None if a is None else torch.from_numpy(a).float().requires_grad_(True)      # noqa: E731
+    ret = {"point_cls_preds": leaf(cls), "point_cls_labels": torch.from_numpy(lab)}
+    if c["box"]:
+        ret.update(point_box_preds=leaf(box), point_box_labels=torch.from_numpy(box_l))
+    if c["part"]:
+        ret.update(point_part_preds=leaf(part), point_part_labels=torch.from_numpy(part_l))
+    head.forward_ret_dict = ret
+    loss, tb = head.get_loss()
+    ref = json.loads(str(fx[f"{name}_tb64"]))
+    assert list(tb) == list(ref)
+    for k in ref:
+        assert abs(tb[k] - ref[k]) <= 1e-5 * abs(ref[k]), (k, tb[k], ref[k])
+    loss.backward()
+    for k in ("cls", "box", "part"):
+        if f"{name}_g{k}64" in fx:
+            g, e = ret[f"point_{k}_preds"].grad.numpy(), fx[f"{name}_g{k}64"]
+            assert np.abs(g - e).max() <= 1e-5 * np.abs(e).max(), k
+    cls_loss, cls_tb = head.get_cls_layer_loss()
+    assert list(cls_tb) == ["point_loss_cls", "point_pos_num"] and float(cls_loss) == tb["point_loss_cls"]
+
+
+def test_mirror_get_loss_twice_and_part_labels_beyond_the_unit_interval(fx):
+    """nothing of one get_loss outlives it: a second call on the same dict builds its own graph.  A positive row whose part label
+    lies a little outside [0, 1] (a point accepted through the 1e-5 margin) gets the same loss as in the restatement."""
+    name = "parta2"
+    head = make_head(name)
+    cls, _, part, lab, _, part_l = case_loss_inputs(fx, name, "32")
+    part_l = part_l.copy()
+    rows = np.nonzero(lab > 0)[0][:2]
+    part_l[rows[0], 0], part_l[rows[1], 2] = 1.0 + 2e-5, -3e-5
+    x, p = torch.from_numpy(cls).float().requires_grad_(True), torch.from_numpy(part).float().requires_grad_(True)
+    head.forward_ret_dict = {"point_cls_preds": x, "point_part_preds": p, "point_cls_labels": torch.from_numpy(lab),
+                             "point_part_labels": torch.from_numpy(part_l)}
+    first, _ = head.get_loss()
+    first.backward()
+    g1 = p.grad.clone()
+    second, tb = head.get_loss()
+    second.backward()
+    assert float(first) == float(second) and torch.equal(p.grad, 2 * g1)
+    _, nc, _, weights, cw = ph.case_spec_args(name)
+    e_loss, _, e_grads = ph.loss(cls, None, part, lab, None, part_l, nc, weights, cw)
+    assert abs(tb["point_loss_part"] - e_loss[2]) <= 1e-5 * e_loss[2] and np.abs(g1.numpy() - e_grads[2]).max() <= 1e-5 * np.abs(e_grads[2]).max()
+
+
+def test_ball_constraint_takes_the_torch_formulation(fx):
+    head = make_head("pv")
+    pts, gt = torch.from_numpy(fx["pv_points"]), torch.from_numpy(fx["pv_gt"])
+    t = head.assign_stack_targets(pts, gt, set_ignore_flag=False, use_ball_constraint=True, central_radius=1.0)
+    lab = t["point_cls_labels"].numpy()
+    assert set(np.unique(lab)) == {0, 1} and 0 < (lab == 1).sum() < (fx["pv_labels"] == 1).sum()
+    with pytest.raises(AssertionError):
+        head.assign_stack_targets(pts, gt, set_ignore_flag=True, use_ball_constraint=True)
+
+
+@pytest.mark.parametrize("use_mean", [True, False])
+def test_point_residual_coder_round_trip(use_mean):
+    r = np.random.default_rng(3)
+    coder = PointResidualCoder(use_mean_size=use_mean, mean_size=ph.MEAN_SIZE) if use_mean else PointResidualCoder(use_mean_size=False)
+    n = 50
+    boxes = torch.from_numpy(np.concatenate([r.uniform(-20, 20, (n, 3)), r.uniform(0.5, 4, (n, 3)), r.uniform(-3.1, 3.1, (n, 1))], 1))
+    pts = boxes[:, 0:3] + torch.from_numpy(r.normal(0, 1, (n, 3)))
+    cls = torch.from_numpy(r.integers(1, 4, n))
+    keep = boxes.clone()
+    code = coder.encode_torch(boxes, pts, cls)
+    assert code.shape == (n, 8) and coder.code_size == 8 and torch.equal(boxes, keep)
+    assert torch.allclose(coder.decode_torch(code, pts, cls), boxes, rtol=1e-12, atol=1e-12)
+
+
+def test_sweep_covers_every_pair_of_axis_values():
+    cases = list(ph.sweep_cases())
+    axes = (ph.SWEEP_N, ph.SWEEP_M, ph.SWEEP_B, ph.SWEEP_C, ph.SWEEP_POS)
+    assert len({c[5] for c in cases}) == len(cases) and len({c[:5] for c in cases}) == len(cases)
+    assert {(c[0], c[1]) for c in cases if c[4] == "mixed"} >= {(n, m) for n in ph.SWEEP_N for m in ph.SWEEP_M if m}
+    for m in (7, 65):      # the mixed mode meets both batch sizes and both class counts at the sizes where it decides most
+        big = [c for c in cases if c[4] == "mixed" and c[1] == m and c[0] >= 255]
+        assert {c[2] for c in big} == set(ph.SWEEP_B) and {c[3] for c in big} == set(ph.SWEEP_C)
+
+
+def test_sweep_filter_drops_at_most_two_per_cent_and_the_mixed_cases_are_decisive():
+    seen = dict(deep=0, ignored=0, pad_owner=0, pad_shell=0, near=0)
+    for N, M, B, C, pos, seed in ph.sweep_cases():
+        pts, gt, frac = ph.sweep_inputs(seed, N, M, B, C, pos)
+        assert frac <= 0.02, (N, M, frac)
+        assert pts.shape == (N, 4) and gt.shape == (B, M, 8)
+        mg = ph.margins(pts, gt, ph.EXTRA)
+        origin = (pts[:, 1:4] == 0).all(axis=1)
+        assert mg[~origin].min() >= 1e-4 and origin.sum() <= 1
+        t = ph.targets(pts, gt, ph.EXTRA, C)
+        npos = int((t["labels"] > 0).sum())
+        if pos == "none" or M == 0:
+            assert npos == 0
+        elif pos == "one":
+            assert npos == 1
+        elif pos == "all":
+            assert npos == N
+        elif M >= 7 and N >= 255:
+            # what makes the sweep able to fail: rows behind row 0 decide, shells ignore, padding rows own and ignore
+            own, lab = t["owner"], t["labels"]
+            frame = pts[:, 0].astype(int)
+            pad_own = (own >= 0) & (gt[frame, np.maximum(own, 0), 3] == 0)
+            near_origin = (np.abs(pts[:, 1:4]) < 0.1).all(axis=1) & ~origin
+            case = dict(deep=int((own > 0).sum()), ignored=int((lab == -1).sum()), pad_owner=int(pad_own.sum()),
+                        pad_shell=int(((lab == -1) & near_origin).sum()), near=int((mg < 0.05).sum()))
+            assert case["deep"] >= 10 and case["ignored"] >= 5 and case["near"] >= 10, (N, M, case)
+            assert (own >= M // 2).any() and len(np.unique(own)) > min(M // 2, 5), (N, M)
+            for k, v in case.items():
+                seen[k] += v
+    assert all(v > 0 for v in seen.values()), seen

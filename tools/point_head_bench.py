@@ -1,0 +1,160 @@
+"""Times the point-head targets + loss at PV-RCNN's shape (bs 8 x 2048 keypoints, PointHeadSimple, pv_rcnn.yaml) and at PointRCNN's
+(bs 4 x 16384 points, PointHeadBox, pointrcnn.yaml), about 20 gts per frame: the fused targets + loss forward + backward
+(lidardetection_amd/point_head.py) against `ported_step` below, a torch port of the reference's formulation
+(point_head_template.py:49-191: the Python loop over frames with its boolean masks, two points_in_boxes_gpu calls per frame - this
+project's HIP kernel -, the [fg_flag] gathers and scatters, the one-hot focal loss and one .item() per logged value), on the same
+tensors in the same process.  The port exists only for this comparison.
+
+Reports per column: wall time per call (device events, median after warm-up), host time to enqueue without a final synchronisation
+(the port synchronises inside), the number of device kernels, of device-to-host copies and of .item() calls (torch.profiler).
+Prints one JSON line per shape.
+
+  python tools/point_head_bench.py [--iters 200] [--ref-iters 30]
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+from roi_loss_bench import enqueue_ms, kernel_count, wall_ms  # noqa: E402
+from lidardetection_amd import point_head  # noqa: E402
+from lidardetection_amd.pcdet.ops.roiaware_pool3d import roiaware_pool3d_utils  # noqa: E402
+from lidardetection_amd.pcdet.utils.box_coder_utils import PointResidualCoder  # noqa: E402
+
+MEAN_SIZE = [[3.9, 1.6, 1.56], [0.8, 0.6, 1.73], [1.76, 0.6, 1.73]]
+SHAPES = {
+    "pv_rcnn": dict(B=8, K=2048, num_class=1, box=False,
+                    cfg=dict(TARGET_CONFIG=dict(GT_EXTRA_WIDTH=[0.2, 0.2, 0.2]),
+                             LOSS_CONFIG=dict(LOSS_REG="smooth-l1", LOSS_WEIGHTS=dict(point_cls_weight=1.0)))),
+    "pointrcnn": dict(B=4, K=16384, num_class=3, box=True,
+                      cfg=dict(TARGET_CONFIG=dict(GT_EXTRA_WIDTH=[0.2, 0.2, 0.2], BOX_CODER="PointResidualCoder",
+                                                  BOX_CODER_CONFIG=dict(use_mean_size=True, mean_size=MEAN_SIZE)),
+                               LOSS_CONFIG=dict(LOSS_REG="WeightedSmoothL1Loss",
+                                                LOSS_WEIGHTS=dict(point_cls_weight=1.0, point_box_weight=1.0, code_weights=[1.0] * 8)))),
+}
+
+
+def ported_step(points, gt_boxes, cls_preds, box_preds, cfg, num_class, coder):
+    """assign_stack_targets + get_cls_layer_loss (+ get_box_layer_loss) as the reference writes them"""
+    tb = {}
+    extend = gt_boxes.clone()
+    extend[..., 3:6] += gt_boxes.new_tensor(cfg["TARGET_CONFIG"]["GT_EXTRA_WIDTH"])
+    bs_idx = points[:, 0]
+    labels = points.new_zeros(points.shape[0]).long()
+    box_labels = gt_boxes.new_zeros((points.shape[0], 8)) if box_preds is not None else None
+    for k in range(gt_boxes.shape[0]):
+        bs_mask = bs_idx == k
+        single = points[bs_mask][:, 1:4]
+        lab = labels.new_zeros(bs_mask.sum())
+        idx = roiaware_pool3d_utils.points_in_boxes_gpu(single.unsqueeze(0), gt_boxes[k:k + 1, :, 0:7].contiguous()).long().squeeze(0)
+        fg = idx >= 0
+        ext = roiaware_pool3d_utils.points_in_boxes_gpu(single.unsqueeze(0), extend[k:k + 1, :, 0:7].contiguous()).long().squeeze(0)
+        lab[fg ^ (ext >= 0)] = -1
+        row = gt_boxes[k][idx[fg]]
+        lab[fg] = 1 if num_class == 1 else row[:, -1].long()
+        labels[bs_mask] = lab
+        if box_labels is not None:
+            one = box_labels.new_zeros((bs_mask.sum(), 8))
+            one[fg] = coder.encode_torch(gt_boxes=row[:, :-1], points=single[fg], gt_classes=row[:, -1].long())
+            box_labels[bs_mask] = one
+    lw = cfg["LOSS_CONFIG"]["LOSS_WEIGHTS"]
+    positives = labels > 0
+    w = ((labels == 0) * 1.0 + 1.0 * positives).float()
+    pos_normalizer = positives.sum(dim=0).float()
+    w /= torch.clamp(pos_normalizer, min=1.0)
+    one_hot = cls_preds.new_zeros(labels.shape[0], num_class + 1)
+    one_hot.scatter_(-1, (labels * (labels >= 0).long()).unsqueeze(-1), 1.0)
+    t = one_hot[..., 1:]
+    p = torch.sigmoid(cls_preds)
+    focal = (t * 0.25 + (1 - t) * 0.75) * torch.pow(t * (1.0 - p) + (1.0 - t) * p, 2.0)
+    bce = torch.clamp(cls_preds, min=0) - cls_preds * t + torch.log1p(torch.exp(-torch.abs(cls_preds)))
+    loss = (focal * bce * w.unsqueeze(-1)).sum() * lw["point_cls_weight"]
+    tb["point_loss_cls"], tb["point_pos_num"] = loss.item(), pos_normalizer.item()
+    if box_preds is not None:
+        rw = positives.float()
+        rw /= torch.clamp(positives.sum().float(), min=1.0)
+        tg = torch.where(torch.isnan(box_labels), box_preds, box_labels)
+        n = ((box_preds - tg) * box_preds.new_tensor(lw["code_weights"]).view(1, -1)).abs()
+        sl1 = torch.where(n < 1.0 / 9.0, 0.5 * n ** 2 / (1.0 / 9.0), n - 0.5 / 9.0)
+        box = (sl1 * rw.unsqueeze(-1)).sum() * lw["point_box_weight"]
+        tb["point_loss_box"] = box.item()
+        loss = loss + box
+    return loss, tb
+
+
+def scene(B, K, M, seed):
+    r = np.random.default_rng(seed)
+    gt = np.zeros((B, M + 8, 8), np.float32)                  # M real rows, zero padding behind them
+    gt[:, :M, 0] = r.uniform(5, 65, (B, M))
+    gt[:, :M, 1] = r.uniform(-35, 35, (B, M))
+    gt[:, :M, 2] = r.uniform(-1.5, -0.5, (B, M))
+    k = r.integers(0, 3, (B, M))
+    gt[:, :M, 3:6] = np.asarray(MEAN_SIZE, np.float32)[k]
+    gt[:, :M, 6] = r.uniform(-3.14, 3.14, (B, M))
+    gt[:, :M, 7] = k + 1
+    pts = np.concatenate([np.repeat(np.arange(B), K)[:, None], r.uniform(0, 70, (B * K, 1)), r.uniform(-40, 40, (B * K, 1)),
+                          r.uniform(-3, 1, (B * K, 1))], 1).astype(np.float32)
+    near = r.uniform(size=B * K) < 0.3                       # 30 % of the points near a gt, as keypoints on objects are
+    g = gt[pts[:, 0].astype(int), r.integers(0, M, B * K)]
+    pts[near, 1:4] = (g[:, 0:3] + r.normal(0, 0.6, (B * K, 3)) * g[:, 3:6])[near]
+    return pts, gt
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=200)
+    ap.add_argument("--ref-iters", type=int, default=30)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("point_head_bench: no GPU")
+    dev = torch.device("cuda:0")
+    for name, s in SHAPES.items():
+        pts, gt = (torch.from_numpy(a).to(dev) for a in scene(s["B"], s["K"], 20, 5))
+        n = pts.shape[0]
+        spec = point_head.spec_from_cfg(s["cfg"], s["num_class"])
+        coder = PointResidualCoder(use_mean_size=True, mean_size=MEAN_SIZE) if s["box"] else None
+        x = torch.randn((n, s["num_class"]), device=dev).requires_grad_(True)
+        b = (torch.randn((n, 8), device=dev) * 0.2).requires_grad_(True) if s["box"] else None
+
+        def fused():
+            x.grad = None
+            if b is not None:
+                b.grad = None
+            t = point_head.assign_point_targets(pts, gt, spec, s["box"], False)
+            cls, box, _part, _ = point_head.point_head_loss(x, b, None, t, spec)
+            (cls + box).backward()
+
+        def fused_targets():
+            point_head.assign_point_targets(pts, gt, spec, s["box"], False)
+
+        def port():
+            x.grad = None
+            if b is not None:
+                b.grad = None
+            loss, _ = ported_step(pts, gt, x, b, s["cfg"], s["num_class"], coder)
+            loss.backward()
+
+        t = point_head.assign_point_targets(pts, gt, spec, s["box"], False)
+        result = {"tool": "point_head_bench", "shape": name, "device": torch.cuda.get_device_name(0), "batch": s["B"], "points": n,
+                  "gts_per_frame": 20, "positives": int((t["point_cls_labels"] > 0).sum()), "ignored": int((t["point_cls_labels"] < 0).sum())}
+        for col, fn, iters in [("fused_targets_fwd_bwd", fused, args.iters), ("fused_targets", fused_targets, args.iters),
+                               ("torch_port_targets_fwd_bwd", port, args.ref_iters)]:
+            med, lo = wall_ms(fn, iters, 10)
+            n_kernels, n_d2h, n_items, names = kernel_count(fn)
+            result[col] = {"wall_ms_median": round(med, 4), "wall_ms_min": round(lo, 4), "enqueue_ms": round(enqueue_ms(fn, iters), 4),
+                           "device_kernels": n_kernels, "device_to_host_copies": n_d2h, "item_calls": n_items}
+            if col != "torch_port_targets_fwd_bwd":
+                result[col]["kernel_names"] = names
+        result["speedup_wall"] = round(result["torch_port_targets_fwd_bwd"]["wall_ms_median"] / result["fused_targets_fwd_bwd"]["wall_ms_median"], 1)
+        print(json.dumps(result), flush=True)
+
+
+if __name__ == "__main__":
+    main()
