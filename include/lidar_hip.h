@@ -248,8 +248,11 @@ int lidar_group_rows_affine_stack(int B, int M, int H, int nsample, const float 
                                   const float *empty_row, const int *features_batch_cnt, const int *idx, const int *idx_batch_cnt,
                                   float *out, void *stream);
 /* A two-layer scale in one kernel: the gather above, the second layer on the matrix cores (W2 (H1, H2) row-major, b2) and the max
- * over the samples — out (M, H2) = max_s relu(relu(table[idx] - query_term[m]) @ W2 + b2).  H1 in {16, 32, 64}, H2 <= 128,
- * nsample in {8, 16, 32} (lidar_sa_layer2_max_supported). */
+ * over the samples — out (M, H2) = max_s relu(relu(table[idx] - query_term[m]) @ W2 + b2).  H1 in {16, 32, 64}, 1 <= H2 <= 128,
+ * nsample in {8, 16, 32} (lidar_sa_layer2_max_supported); query_term may be null; an empty ball (idx[m][0] < 0) gives
+ * relu(empty_row @ W2 + b2).  Dynamic LDS per launch: (H1 * NT * 32 + 4 * 32 * (H1 + 1)) * 4 bytes with NT = ceil(H2 / 32), from
+ * 4 224 (H1 16, NT 1) to 66 048 bytes (H1 64, NT 4: 96 < H2 <= 128); the launch requests what exceeds 64 KiB itself
+ * (hipFuncAttributeMaxDynamicSharedMemorySize), so every declared shape runs. */
 int lidar_sa_layer2_max_supported(int H1, int H2, int nsample);
 int lidar_sa_layer2_max_stack(int B, int M, int H1, int H2, int nsample, const float *table, const float *query_term,
                               const float *empty_row, const float *W2, const float *b2, const int *features_batch_cnt,
@@ -291,7 +294,8 @@ int lidar_three_interpolate_grad_batch(int b, int c, int n, int m, const float *
 /* ------------------------------------------------------------------ roiaware_pool3d / roipoint_pool3d
  * roiaware_pool3d_gpu (pcdet/ops/roiaware_pool3d/src/roiaware_pool3d.cpp:29-66): argmax (R,x,y,z,C) i32,
  * pts_idx_of_voxels (R,x,y,z,max_pts) i32 (slot 0 = count) and pooled (R,x,y,z,C) f32 zero-filled by the
- * caller; pool_method 0 = max, 1 = avg; out_x/y/z < 256.  No (boxes x points) scratch matrix is needed. */
+ * caller; pool_method 0 = max, 1 = avg; 1 <= out_x/y/z <= 255, max_pts >= 2, channels >= 1.  No (boxes x points) scratch matrix
+ * is needed. */
 int lidar_roiaware_pool3d_forward(int boxes_num, int pts_num, int channels, int max_pts_each_voxel, int out_x, int out_y,
                                   int out_z, const float *rois, const float *pts, const float *pts_feature, int *argmax,
                                   int *pts_idx_of_voxels, float *pooled_features, int pool_method, void *stream);

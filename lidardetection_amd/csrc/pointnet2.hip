@@ -687,6 +687,10 @@ LIDAR_EXPORT int lidar_sa_layer2_max_supported(int H1, int H2, int nsample) {
 
 // table (N, H1), query_term (M, H1) or null, empty_row (H1), W2 (H1, H2) row-major, b2 (H2), idx = RAW ball-query result
 // (M, nsample); out (M, H2).  See lidar_group_rows_affine_stack for the first layer's algebra.
+// Dynamic LDS per instance: (H1 * NT * 32 + 4 * 32 * (H1 + 1)) * 4 bytes with NT = ceil(H2 / 32) -- W2 padded to NT * 32 columns plus
+// one 32 x (H1 + 1) tile per wave: 4 224 bytes (H1 = 16, NT = 1) up to 66 048 (H1 = 64, NT = 4, i.e. 96 < H2 <= 128).  That one size is
+// past 64 KiB, so the launch asks for it first (hipFuncAttributeMaxDynamicSharedMemorySize, once per instance and device); every
+// declared shape is launched with the LDS it needs, none is narrowed.
 LIDAR_EXPORT int lidar_sa_layer2_max_stack(int B, int M, int H1, int H2, int nsample, const float *table, const float *query_term,
                                            const float *empty_row, const float *W2, const float *b2,
                                            const int *features_batch_cnt, const int *idx, const int *idx_batch_cnt, float *out,
@@ -699,7 +703,22 @@ LIDAR_EXPORT int lidar_sa_layer2_max_stack(int B, int M, int H1, int H2, int nsa
     const int qw = 32 / nsample, ngroups = divup(M, qw);
     const int blocks = (int)std::min<long long>(divup(ngroups, 4), 256 * 3);
     hipStream_t s = (hipStream_t)stream;
-#define SAL(NT, C4, NS) hipLaunchKernelGGL((sa_layer2_max_kernel<NT, C4, NS>), dim3(blocks), dim3(256), lds, s, B, M, H2, (const float4 *)table, (const float4 *)query_term, (const float4 *)empty_row, W2, b2, features_batch_cnt, idx, idx_batch_cnt, out)
+    int dev_id = 0;                                       // the LDS opt-in is a per-device function attribute: one flag per device
+    (void)hipGetDevice(&dev_id);
+    dev_id &= 63;
+#define SAL(NT, C4, NS) do {                                                                                                       \
+        if (lds > 65536) {                                /* H1 = 64, NT = 4: 66 048 bytes, past the 64 KiB a launch gets unasked */ \
+            static bool attr_set[64] = {};                                                                                        \
+            if (!attr_set[dev_id]) {                                                                                              \
+                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&sa_layer2_max_kernel<NT, C4, NS>),                      \
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                  \
+                attr_set[dev_id] = true;                                                                                          \
+            }                                                                                                                     \
+        }                                                                                                                         \
+        hipLaunchKernelGGL((sa_layer2_max_kernel<NT, C4, NS>), dim3(blocks), dim3(256), lds, s, B, M, H2, (const float4 *)table,   \
+                           (const float4 *)query_term, (const float4 *)empty_row, W2, b2, features_batch_cnt, idx, idx_batch_cnt,  \
+                           out);                                                                                                  \
+    } while (0)
 #define SAL_NS(NT, C4) do { if (nsample == 8) SAL(NT, C4, 8); else if (nsample == 16) SAL(NT, C4, 16); else SAL(NT, C4, 32); } while (0)
 #define SAL_C4(NT) do { if (c4 == 4) SAL_NS(NT, 4); else if (c4 == 8) SAL_NS(NT, 8); else SAL_NS(NT, 16); } while (0)
     switch (nt) { case 1: SAL_C4(1); break; case 2: SAL_C4(2); break; case 3: SAL_C4(3); break; default: SAL_C4(4); break; }
