@@ -475,6 +475,16 @@ int lidar_wino43_supported(int Cin, int Cout);
 int lidar_wino43_pack_weights(const float *w, int Cin, int Cout, float *packed, void *stream);
 int lidar_wino43_conv3x3_nhwc(const float *in, int B, int H, int W, int Cin, int in_C, const float *packed, const float *bias, int relu,
                               int Cout, float *out, int out_C, int out_off, void *stream);
+/* The same kernel in its shared-transform workgroup shape (one tile group x four blocks of 32 output channels: the input transform
+ * and the region DMA of a tile group run once per 128 output channels instead of once per 64).  Bit-identical results; supported:
+ * Cin % 16 == 0, Cin >= 32, Cout % 128 == 0.  The waves walk the 36 positions in another order, so the filters have their OWN packed
+ * layout: `packed` of lidar_wino43s_conv3x3_nhwc comes from lidar_wino43s_pack_weights (lidar_wino43s_packed_floats = 36 Cin Cout
+ * floats, 0 = unsupported), never from lidar_wino43_pack_weights, and the other way round.  Everything else as above. */
+size_t lidar_wino43s_packed_floats(int Cin, int Cout);
+int lidar_wino43s_supported(int Cin, int Cout);
+int lidar_wino43s_pack_weights(const float *w, int Cin, int Cout, float *packed, void *stream);
+int lidar_wino43s_conv3x3_nhwc(const float *in, int B, int H, int W, int Cin, int in_C, const float *packed, const float *bias, int relu,
+                               int Cout, float *out, int out_C, int out_off, void *stream);
 
 /* The WEIGHT GRADIENT of the same layers (training; torch hands it to MIOpen) as Winograd F(3x3, 4x4) on the fp32 matrix cores
  * (csrc/wino43_wgrad.hip): dw[co][ci][a][b] = sum_{n,h,w} g[n][h][w][co] x[n][h + a - 1][w + b - 1][ci] with zero padding, 36

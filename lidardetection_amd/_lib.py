@@ -117,6 +117,10 @@ SIGNATURES = {
     "lidar_wino43_supported": (i32, [i32, i32]),
     "lidar_wino43_pack_weights": (i32, [vp, i32, i32, vp, vp]),
     "lidar_wino43_conv3x3_nhwc": (i32, [vp, i32, i32, i32, i32, i32, vp, vp, i32, i32, vp, i32, i32, vp]),
+    "lidar_wino43s_packed_floats": (sz, [i32, i32]),
+    "lidar_wino43s_supported": (i32, [i32, i32]),
+    "lidar_wino43s_pack_weights": (i32, [vp, i32, i32, vp, vp]),
+    "lidar_wino43s_conv3x3_nhwc": (i32, [vp, i32, i32, i32, i32, i32, vp, vp, i32, i32, vp, i32, i32, vp]),
     "lidar_wino43_wgrad_supported": (i32, [i32, i32]),
     "lidar_wino43_wgrad_workspace_bytes": (sz, [i32, i32, i32, i32, i32]),
     "lidar_wino43_wgrad_nhwc": (i32, [vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp]),

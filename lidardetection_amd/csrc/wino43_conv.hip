@@ -601,3 +601,488 @@ LIDAR_EXPORT int lidar_wino43_conv3x3_nhwc(const float *in, int B, int H, int W,
 #undef W43_LAUNCH
     return lidar_check_launch("lidar_wino43_conv3x3_nhwc");
 }
+
+// ================================================================== the shared-transform shape (Cout % 128 == 0)
+// Same arithmetic, second workgroup shape: ONE tile group x FOUR blocks of 32 output channels (wave wv <-> block 4 ng + wv).  In the
+// shape above the input transform and the region DMA of a tile group are redone by every workgroup that covers another 64 output
+// channels of it; here they are done once per 128.  Per output element nothing changes — K order of the accumulation, transform
+// expressions, epilogue — so the result is bit-identical to wino_f43_kernel (tests/test_gpu_wino43_share.py requires it).
+//   Transform split: V = B^T d B is cut into four 3 x 3 quadrants of positions; wave (nw = wv & 1, h = wv >> 1) computes rows
+//   xy = 3 nw + r and columns x = 3 h + c.  First stage as above (rows nw .. nw + 4 of the patch, wave-uniform coefficients) but only
+//   over the five patch columns h .. h + 4 its second stage needs (B^T rows 0..2 ignore column 5, rows 3..5 column 0): 25 patch reads
+//   and 75 packed instructions instead of 30 / 90; second stage: the three outputs of its half (13 or 9 instructions per row instead
+//   of 22), 9 V writes instead of 18.  Still two bursts per chunk.
+//   Position order of a wave (time index t = 0..35): quadrant (da, db) = (t / 18, (t / 9) & 1) RELATIVE to its own, i.e. rows
+//   3 (nw ^ da) + r, columns 3 (h ^ db) + c with r = (t % 9) / 3, c = t % 3.  t = 0..8 are the positions the wave wrote itself: the
+//   first R A operands of a chunk are read before the chunk barrier, as above; t = 9..35 (the three other waves' quadrants) are read
+//   after it and rely on it.  The accumulator of time index t sits at acc index 6 (3 da + r) + 3 db + c: rows rotated by 3 nw (as
+//   above), columns by 3 h — one epilogue copy per (nw, h).
+//   Filters: own pack routine (wino43s_pack_kernel), the same [chunk][cout / 32][t][lane][2 s + cout parity] with t in THIS order.
+//   LDS: region image and V ring of one tile group: 87 KB for 4 x 4 tiles instead of 141 KB.  (A second workgroup per CU does not
+//   follow from it: a wave holds all 512 registers of its SIMD.)
+__global__ __launch_bounds__(256) void wino43s_pack_kernel(const float *__restrict__ w, int Cin, int Cout, float *__restrict__ upk) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= Cin * Cout) return;
+    const int cout = idx / Cin, cin = idx - cout * Cin;
+    const float *g = w + ((size_t)cout * Cin + cin) * 9;
+    const double G[6][3] = {{0.5, 0., 0.}, {1. / 6, 1. / 6, 1. / 6}, {1. / 6, -1. / 6, 1. / 6},
+                            {16. / 15, 8. / 15, 4. / 15}, {1. / 30, -2. / 30, 4. / 30}, {0., 0., 0.5}};
+    double t[6][3];                      // G g
+#pragma unroll
+    for (int y = 0; y < 6; ++y)
+#pragma unroll
+        for (int x = 0; x < 3; ++x) t[y][x] = G[y][0] * (double)g[x] + G[y][1] * (double)g[3 + x] + G[y][2] * (double)g[6 + x];
+    const int C = cin >> 3, kq = (cin >> 1) & 3, sk = cin & 1, nb = cout >> 5, hf = cout & 1, n = (cout >> 1) & 15, NB = Cout >> 5;
+    const int lane = kq * 16 + n, nw = nb & 1, h = (nb >> 1) & 1;
+#pragma unroll
+    for (int y = 0; y < 6; ++y)
+#pragma unroll
+        for (int x = 0; x < 6; ++x) {
+            const double u = t[y][0] * G[x][0] + t[y][1] * G[x][1] + t[y][2] * G[x][2];
+            const int da = (y / 3) ^ nw, db = (x / 3) ^ h, q = 18 * da + 9 * db + 3 * (y % 3) + x % 3;
+            upk[(((((size_t)C * NB + nb) * 36 + q) * 64 + lane) << 2) + (sk << 1) + hf] = (float)u;
+        }
+}
+
+static constexpr int w43s_nt(int TY, int TX) { return (TY + 1) * (TX + 1); }
+static constexpr int w43s_rp(int TY, int TX) { return ((32 * w43s_nt(TY, TX) + 255) / 256) * 256; }
+static constexpr size_t w43s_lds_bytes(int TY, int TX) {
+    return (size_t)2 * w43s_rp(TY, TX) * 16 + (size_t)2 * 36 * 64 * 8 + (size_t)4 * 32 * W43_STG_PITCH * 4;
+}
+// time index t of a wave's position order -> its accumulator index (see above)
+static constexpr int w43s_qi(int t) { return 6 * (3 * (t / 18) + (t % 9) / 3) + 3 * ((t / 9) & 1) + t % 3; }
+// ... -> float2 offset inside its quadrant of a V buffer
+static constexpr int w43s_vo(int t) { return (6 * ((t % 9) / 3) + t % 3) * 64; }
+
+template <int TY, int TX>
+__global__ __launch_bounds__(256) void wino_f43s_kernel(const Wino43Args a) {      // a.n_groups = Cout / 128
+    static_assert(TY * TX == 16, "a wave owns 16 tiles");
+    constexpr int TR = TY + 1, TC = TX + 1, NT = TR * TC;
+    constexpr int RH = 4 * TY + 2, RW = 4 * TX + 2;
+    constexpr int RP = w43s_rp(TY, TX);
+    constexpr int QW = RP / 256;
+    constexpr int VB = 36 * 64;                                 // f32x2 per V buffer
+    constexpr int R = W43_R;
+    static_assert(R <= 9 && 36 % R == 0, "the A operands read before the chunk barrier must be the wave's own positions");
+    extern __shared__ float4 s_mem4[];
+    float4 *s_raw = s_mem4;                                                   // [2][RP]
+    f32x2 *s_v = reinterpret_cast<f32x2 *>(s_mem4 + 2 * RP);                  // [2][36 positions][64 lanes]{K-step 0, 1}
+    float *s_stg = reinterpret_cast<float *>(s_v + 2 * VB);                   // [4 waves][32 pixels][W43_STG_PITCH]
+
+    const int t = threadIdx.x, l = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int nw = wv & 1, h = wv >> 1;
+    const int m = l & 15, kq = l >> 4;
+    const int ty = m / TX, tx = m % TX;
+    const int H = a.H, W = a.W;
+    const int NB = a.Cout >> 5;
+    const int bstride = NB * 36 * 64;
+
+    const int nb8 = (a.n_blocks + 7) >> 3;
+    const int xcd = (int)(blockIdx.x & 7), slot = (int)(blockIdx.x >> 3), nslots = (int)(gridDim.x >> 3);
+    const int blk_end = min((xcd + 1) * nb8, a.n_blocks);
+    int blk = xcd * nb8 + slot;
+    if (blk >= blk_end) return;
+
+    struct Tile {
+        unsigned off[QW];
+        int b;
+        int bidx, by, bx, nb;
+    };
+    auto make_tile = [&](int blk_) {
+        Tile tl;
+        const int ng = blk_ % a.n_groups;
+        blk_ /= a.n_groups;
+        tl.bx = blk_ % a.blocks_x;
+        blk_ /= a.blocks_x;
+        tl.by = blk_ % a.blocks_y;
+        tl.bidx = blk_ / a.blocks_y;
+        tl.nb = ng * 4 + wv;
+        tl.b = tl.nb * 36 * 64;
+        const int R0 = 4 * TY * tl.by - 1, C0 = 4 * TX * tl.bx - 1;
+        int lq = l;
+        asm volatile("" : "+v"(lq));
+#pragma unroll
+        for (int k = 0; k < QW; ++k) {
+            const int sl = (wv + 4 * k) * 64 + lq;
+            const int ps = sl >> 1;
+            const int c0 = ps / NT, tidx = ps - c0 * NT;
+            const int tyy = tidx / TC, txx = tidx - tyy * TC;
+            const int ry = 4 * tyy + (c0 >> 2), rx = 4 * txx + (c0 & 3);
+            const int gy = R0 + ry, gx = C0 + rx;
+            const bool ok = ps < 16 * NT && ry < RH && rx < RW && gy >= 0 && gy < H && gx >= 0 && gx < W;
+            tl.off[k] = ok ? (unsigned)(((tl.bidx * H + gy) * W + gx) * a.in_C) * 4u + 16u * (unsigned)(sl & 1) : W43_OOB;
+        }
+        return tl;
+    };
+    typedef int i32x4 __attribute__((ext_vector_type(4)));
+    i32x4 rsrc;
+    {
+        const unsigned long long base = (unsigned long long)a.in;
+        rsrc[0] = (int)(unsigned)base;
+        rsrc[1] = (int)((unsigned)(base >> 32) & 0xffffu);
+        rsrc[2] = (int)((unsigned)a.B * (unsigned)H * (unsigned)W * (unsigned)a.in_C * 4u);
+        rsrc[3] = 0x00020000;
+    }
+    const __amdgpu_buffer_rsrc_t frsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.upk), (short)0, (int)(36u * (unsigned)a.Cin * (unsigned)a.Cout * 4u), 0x00020000);
+    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+    const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(a.out, (short)0, (int)((unsigned)a.B * (unsigned)H * (unsigned)W * (unsigned)a.out_C * 4u), 0x00020000);
+    const int l16 = l * 16;
+    auto ldf = [&](int f4_index) {
+        return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(frsrc, l16, f4_index * 16, 0));
+    };
+    const unsigned raw_lds = (unsigned)(size_t)((__attribute__((address_space(3))) char *)s_raw);
+    unsigned doff[QW];
+    auto dma = [&](int buf) {
+#pragma unroll
+        for (int k = 0; k < QW; ++k) {
+            const unsigned dst = raw_lds + (unsigned)((buf * RP + (wv + 4 * k) * 64) * 16);
+            asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds" : : "v"(doff[k]), "s"(rsrc), "s"(dst) : "memory", "m0");
+        }
+    };
+
+    // ---- input transform, this wave's quadrant.  Patch rows nw .. nw + 4 (rrow, as above) x patch columns h .. h + 4.  Relative to
+    // the base shifted by h * NT pixels the columns jx = 0, 1, 2, 4 sit at the same compile-time offsets {0, NT, 2 NT, 1} * 8 floats
+    // for both h; only jx = 3 (patch column 3 or 4) differs: its own five addresses (rrow3).
+    const int rbase = (ty * TC + tx) * 8 + 2 * kq;
+    int rrow[5], rrow3[5];
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+        const int dy = nw + j;
+        const int rr = rbase + ((dy & 3) * 4 * NT + (dy >> 2) * TC) * 8;
+        rrow[j] = rr + h * NT * 8;
+        rrow3[j] = rr + (h ? 1 : 3 * NT) * 8;
+    }
+    float cf[3][5];
+    {
+        const float c0[3][5] = {{2.f, -3.f, -4.f, 3.f, 2.f}, {0.f, -2.f, 1.f, 5.f, 2.f}, {0.f, -2.f, 5.f, -1.f, -2.f}};
+        const float c1[3][5] = {{2.f, 1.f, -2.f, -1.f, 0.f}, {1.f, -2.f, -1.f, 2.f, 0.f}, {2.f, -3.f, -4.f, 3.f, 2.f}};
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int j = 0; j < 5; ++j) cf[r][j] = nw ? c1[r][j] : c0[r][j];
+    }
+#define W43S_COL(jx) ((jx) == 4 ? 8 : (jx) * NT * 8)                       /* float offset of patch column h + jx from rrow (jx != 3) */
+#define W43S_RD(raw_, j, jx) (*reinterpret_cast<const f32x2 *>((jx) == 3 ? (raw_) + rrow3[j] : (raw_) + rrow[j] + W43S_COL(jx)))
+    // second stage of one row for this wave's column half: ws_[x] = first-stage value of patch column x (h = 0: 0..4, h = 1: 1..5)
+#define W43S_S2(wr_, o_)                                                                                                           \
+    if (h == 0) {                                                                                                                  \
+        const f32x2 ws_[6] = {wr_[0], wr_[1], wr_[2], wr_[3], wr_[4], wr_[4]};                                                     \
+        W43_S2_0(ws_, o_) W43_S2_1(ws_, o_) W43_S2_2(ws_, o_)                                                                      \
+    } else {                                                                                                                       \
+        const f32x2 ws_[6] = {wr_[0], wr_[0], wr_[1], wr_[2], wr_[3], wr_[4]};                                                     \
+        f32x2 ot_[6];                                                                                                              \
+        W43_S2_34(ws_, ot_) W43_S2_5(ws_, ot_)                                                                                     \
+        o_[0] = ot_[3]; o_[1] = ot_[4]; o_[2] = ot_[5];                                                                            \
+    }
+    // V pointers of the four quadrants relative to this wave's: v_q[2 da + db], + buffer * VB + w43s_vo(t)
+    const f32x2 *v_q[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v_q[e] = s_v + (size_t)(18 * (nw ^ (e >> 1)) + 3 * (h ^ (e & 1))) * 64 + l;
+    f32x2 *const v_own = s_v + (size_t)(18 * nw + 3 * h) * 64 + l;
+    auto transform = [&](int rbuf, int vbuf) {            // (pipeline fill only)
+        const float *raw = reinterpret_cast<const float *>(s_raw + rbuf * RP);
+        f32x2 *vd = v_own + vbuf * VB;
+        f32x2 w_[3][5];
+#pragma unroll
+        for (int jx = 0; jx < 5; ++jx) {
+            f32x2 d[5];
+#pragma unroll
+            for (int j = 0; j < 5; ++j) d[j] = W43S_RD(raw, j, jx);
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                f32x2 sacc = W43_PK(cf[r][0]) * d[0];
+#pragma unroll
+                for (int j = 1; j < 5; ++j) sacc = W43_FMA(W43_PK(cf[r][j]), d[j], sacc);
+                w_[r][jx] = sacc;
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            f32x2 o[3];
+            W43S_S2(w_[r], o)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) vd[(r * 6 + c) * 64] = o[c];
+        }
+    };
+
+    f32x4 acc[72];                        // acc[2 w43s_qi(t) + hf]
+    f32x4 bb[18];                         // filters, a rolling window of 18 time indices
+    f32x2 va[R];
+    const int NC = a.Cin >> 3;
+    Tile cur = make_tile(blk), nxt = cur;
+#pragma unroll
+    for (int k = 0; k < QW; ++k) doff[k] = cur.off[k];
+    auto dma_advance = [&](bool cross, bool to_next, const Tile &tn) {
+#pragma unroll
+        for (int k = 0; k < QW; ++k) doff[k] = cross ? (to_next ? tn.off[k] : W43_OOB) : doff[k] + 32u;
+    };
+
+    dma(0);
+    dma_advance(false, false, cur);
+    dma(1);
+    dma_advance(false, false, cur);
+#pragma unroll
+    for (int e = 0; e < 18; ++e) bb[e] = ldf(cur.b + e * 64);
+    __builtin_amdgcn_s_waitcnt(0x0F70);
+    asm volatile("" ::: "memory");
+    __syncthreads();
+    transform(0, 0);
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < R; ++e) va[e] = v_own[w43s_vo(e)];
+
+    // chunk C as above; slot k <-> MFMA (time index tq = k >> 2, K-step (k >> 1) & 1, output channel k & 1).  The A ring slot of time
+    // index tq takes tq + R: of V[P] (tq + R >= 9: another wave's rows — valid because of THIS chunk's barrier), then (tq + R >= 36)
+    // the first time indices of chunk C + 1 in V[!P]: the wave's own quadrant, written by itself at slot W43_B2, no barrier needed.
+    // Transform of chunk C + 1: the 25 patch reads at slots 0..14 (columns jx 0..2) and W43_B1 .. W43_B1 + 9 (jx 3, 4); first stage of
+    // jx 0..2 at slot W43_B1; first stage of jx 3, 4 + second stage + the 9 V writes at slot W43_B2.
+#define W43S_CHUNK(C, P, FIRST)                                                                                                    \
+    {                                                                                                                              \
+        if (!(WINO43_PROBE & 16)) {                                                                                                \
+            if ((C) > 0) asm volatile("s_waitcnt vmcnt(36) lgkmcnt(0)\n\ts_barrier" ::: "memory");                                 \
+            else if (!first_block) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");                                 \
+        }                                                                                                                          \
+        if (!(WINO43_PROBE & 1)) {                                                                                                 \
+            dma(P);                                                                                                                \
+            dma_advance((C) + 3 == NC, has_next, nxt);                                                                             \
+        }                                                                                                                          \
+        const int bc_ = cur.b + (C) * bstride;                                                                                     \
+        const int bn_ = ((C) + 1 < NC) ? cur.b + ((C) + 1) * bstride : (has_next ? nxt.b : cur.b);                                 \
+        const float *raw_ = reinterpret_cast<const float *>(s_raw + (1 - (P)) * RP);                                               \
+        f32x2 *vd_ = v_own + (1 - (P)) * VB;                                                                                       \
+        f32x2 d_[5][5], w_[3][5];                                                                                                  \
+        __builtin_amdgcn_sched_barrier(0);                                                                                         \
+        _Pragma("unroll") for (int k = 0; k < 144; ++k) {                                                                          \
+            const int tq = k >> 2, sk = (k >> 1) & 1, hf = k & 1, q = w43s_qi(tq);                                                 \
+            const float av_ = va[tq % R][sk];                                                                                      \
+            const float bv_ = bb[tq % 18][(sk << 1) + hf];                                                                         \
+            if (FIRST && sk == 0) {                                                                                                \
+                if (q < 32) W43_MFMA_A0(acc[2 * q + hf], av_, bv_); else W43_MFMA_V0(acc[2 * q + hf], av_, bv_);                   \
+            } else {                                                                                                               \
+                if (q < 32) W43_MFMA_A(acc[2 * q + hf], av_, bv_); else W43_MFMA_V(acc[2 * q + hf], av_, bv_);                     \
+            }                                                                                                                      \
+            if ((k & 3) == 3) {                                                                                                    \
+                if (!(WINO43_PROBE & 2)) bb[tq % 18] = tq < 18 ? ldf(bc_ + (tq + 18) * 64) : ldf(bn_ + (tq - 18 < 0 ? 0 : tq - 18) * 64); \
+                const int ta = tq + R;                                                                                             \
+                va[tq % R] = ta < 36 ? (v_q[(ta < 36 ? ta : 0) / 9] + (P) * VB)[w43s_vo(ta < 36 ? ta : 0)]                         \
+                                     : vd_[w43s_vo(ta >= 36 ? ta - 36 : 0)];                                                       \
+            }                                                                                                                      \
+            if (!(WINO43_PROBE & 4)) {                                                                                             \
+                if (k < 15 || (k >= W43_B1 && k < W43_B1 + 10)) {                                                                  \
+                    const int rk = k < 15 ? k : k - W43_B1 + 15;                                                                   \
+                    if (WINO43_PROBE & 128) d_[rk / 5][rk % 5] = va[0];                                                            \
+                    else d_[rk / 5][rk % 5] = W43S_RD(raw_, rk % 5, rk / 5);                                                       \
+                }                                                                                                                  \
+                if ((k == W43_B1 || k == W43_B2) && (WINO43_PROBE & 32)) {     /* keep the reads alive */                          \
+                    _Pragma("unroll") for (int x = (k == W43_B1 ? 0 : 3); x < (k == W43_B1 ? 3 : 5); ++x)                          \
+                        _Pragma("unroll") for (int j = 0; j < 5; ++j) asm volatile("" : : "v"(d_[x][j]));                          \
+                }                                                                                                                  \
+                if ((k == W43_B1 || k == W43_B2) && !(WINO43_PROBE & 32)) {                                                        \
+                    _Pragma("unroll") for (int x = (k == W43_B1 ? 0 : 3); x < (k == W43_B1 ? 3 : 5); ++x)                          \
+                        _Pragma("unroll") for (int r = 0; r < 3; ++r) {                                                            \
+                            f32x2 s_ = W43_PK(cf[r][0]) * d_[x][0];                                                                \
+                            _Pragma("unroll") for (int j = 1; j < 5; ++j) s_ = W43_FMA(W43_PK(cf[r][j]), d_[x][j], s_);            \
+                            w_[r][x] = s_;                                                                                         \
+                        }                                                                                                          \
+                }                                                                                                                  \
+                if (k == W43_B2 && !(WINO43_PROBE & 32)) {                                                                         \
+                    _Pragma("unroll") for (int r = 0; r < 3; ++r) {                                                                \
+                        f32x2 o_[3];                                                                                               \
+                        W43S_S2(w_[r], o_)                                                                                         \
+                        _Pragma("unroll") for (int c = 0; c < 3; ++c) vd_[(r * 6 + c) * 64] = o_[c];                               \
+                    }                                                                                                              \
+                }                                                                                                                  \
+            }                                                                                                                      \
+            __builtin_amdgcn_sched_barrier(0);                                                                                     \
+        }                                                                                                                          \
+    }
+
+    // ---- epilogue: as above.  Stored row qr holds transform row (qr + 3 nw) % 6, stored column xs transform column (xs + 3 h) % 6:
+    // one copy of the code per (nw, h).
+#define W43S_EPILOGUE(NWV, HV)                                                                                                     \
+        {                                                                                                                          \
+            asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");                                                                     \
+            int lo = l;                                                                                                            \
+            asm volatile("" : "+v"(lo));                                                                                           \
+            const int ch0 = 32 * cur.nb;                                                                                           \
+            const bool relu = a.relu != 0;                                                                                         \
+            float *stg = s_stg + (size_t)wv * 32 * W43_STG_PITCH;                                                                  \
+            const f32x2 bv = bias2;                                                                                                \
+            const int gy0 = 4 * TY * cur.by, gx0 = 4 * TX * cur.bx;                                                                \
+            const bool inside = gy0 + 4 * TY <= H && gx0 + 4 * TX <= W;                                                            \
+            int lane_ry[4], lane_cx[4];                                                                                            \
+            unsigned lane_off[4];                                                                                                  \
+_Pragma("unroll")                                                                                                                  \
+            for (int i = 0; i < 4; ++i) {                                                                                          \
+                const int mt = 4 * ((lo >> 3) & 3) + i;                                                                            \
+                lane_ry[i] = gy0 + 4 * (mt / TX);                                                                                  \
+                lane_cx[i] = gx0 + 4 * (mt % TX) + (lo >> 5);                                                                      \
+                lane_off[i] = (unsigned)(((cur.bidx * H + lane_ry[i]) * W + lane_cx[i]) * a.out_C + a.out_off + ch0 + 4 * (lo & 7)) * 4u; \
+            }                                                                                                                      \
+            const float at[6][4] = {{1.f, 0.f, 0.f, 0.f}, {1.f, 1.f, 1.f, 1.f}, {1.f, -1.f, 1.f, -1.f},                            \
+                                    {1.f, 0.5f, 0.25f, 0.125f}, {1.f, -2.f, 4.f, -8.f}, {0.f, 0.f, 0.f, 1.f}};                     \
+_Pragma("unroll")                                                                                                                  \
+            for (int i = 0; i < 4; ++i) {                                                                                          \
+                f32x2 y[4][4];                                                                                                     \
+_Pragma("unroll")                                                                                                                  \
+                for (int ii = 0; ii < 4; ++ii)                                                                                     \
+_Pragma("unroll")                                                                                                                  \
+                    for (int j = 0; j < 4; ++j) y[ii][j] = bv;                                                                     \
+_Pragma("unroll")                                                                                                                  \
+                for (int qr = 0; qr < 6; ++qr) {                                                                                   \
+                    f32x2 mm[6];                                                                                                   \
+_Pragma("unroll")                                                                                                                  \
+                    for (int x = 0; x < 6; ++x) {                                                                                  \
+                        const int q = 6 * qr + (x + 3 * (HV)) % 6;                                                                 \
+                        if (q < 32) {                                                                                              \
+                            asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(mm[x][0]) : "a"(acc[2 * q][i]));                       \
+                            asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(mm[x][1]) : "a"(acc[2 * q + 1][i]));                   \
+                        } else {                                                                                                   \
+                            mm[x] = (f32x2){acc[2 * q][i], acc[2 * q + 1][i]};                                                     \
+                        }                                                                                                          \
+                    }                                                                                                              \
+                    const f32x2 s = mm[1] + mm[2], d = mm[1] - mm[2];                                                              \
+                    f32x2 tt[4];                                                                                                   \
+                    tt[0] = (mm[0] + s) + (mm[3] + mm[4]);                                                                         \
+                    tt[1] = W43_FMA(W43_PK(0.5f), mm[3], W43_FMA(W43_PK(-2.f), mm[4], d));                                         \
+                    tt[2] = W43_FMA(W43_PK(0.25f), mm[3], W43_FMA(W43_PK(4.f), mm[4], s));                                         \
+                    tt[3] = W43_FMA(W43_PK(0.125f), mm[3], W43_FMA(W43_PK(-8.f), mm[4], d)) + mm[5];                               \
+_Pragma("unroll")                                                                                                                  \
+                    for (int ii = 0; ii < 4; ++ii) {                                                                               \
+                        const float c_own = at[qr][ii], c_oth = at[(qr + 3) % 6][ii];                                              \
+                        if ((NWV ? c_oth : c_own) == 0.f) continue;                                                                \
+                        const float cfa = NWV ? c_oth : c_own;                                                                     \
+_Pragma("unroll")                                                                                                                  \
+                        for (int j = 0; j < 4; ++j) {                                                                              \
+                            if (cfa == 1.f) y[ii][j] += tt[j];                                                                     \
+                            else if (cfa == -1.f) y[ii][j] -= tt[j];                                                               \
+                            else y[ii][j] = W43_FMA(W43_PK(cfa), tt[j], y[ii][j]);                                                 \
+                        }                                                                                                          \
+                    }                                                                                                              \
+                    __builtin_amdgcn_sched_barrier(0);                                                                             \
+                }                                                                                                                  \
+_Pragma("unroll")                                                                                                                  \
+                for (int hh = 0; hh < 2; ++hh) {                                                                                   \
+_Pragma("unroll")                                                                                                                  \
+                    for (int ii = 0; ii < 2; ++ii)                                                                                 \
+_Pragma("unroll")                                                                                                                  \
+                        for (int j = 0; j < 4; ++j) {                                                                              \
+                            const f32x2 yv = y[2 * hh + ii][j];                                                                    \
+                            const f32x2 v = relu ? (f32x2){fmaxf(yv[0], 0.f), fmaxf(yv[1], 0.f)} : yv;                             \
+                            *reinterpret_cast<f32x2 *>(stg + ((ii * 4 + j) * 4 + (lo >> 4)) * W43_STG_PITCH + 2 * (lo & 15)) = v;  \
+                        }                                                                                                          \
+                    if (i == 0 && hh == 0 && !(WINO43_PROBE & 512)) __builtin_amdgcn_s_waitcnt(0x0F70);                            \
+                    float4 sv_[4];                                                                                                 \
+_Pragma("unroll")                                                                                                                  \
+                    for (int k = 0; k < 4; ++k) sv_[k] = *reinterpret_cast<const float4 *>(stg + (k * 8 + (lo >> 3)) * W43_STG_PITCH + 4 * (lo & 7)); \
+_Pragma("unroll")                                                                                                                  \
+                    for (int k = 0; k < 4; ++k) {                                                                                  \
+                        const int dyk = 2 * hh + (k >> 1), dxk = 2 * (k & 1);                                                      \
+                        unsigned vo_ = lane_off[i];                                                                                \
+                        if (!inside) vo_ = (lane_ry[i] + dyk < H && lane_cx[i] + dxk < W) ? vo_ : W43_OOB;                         \
+                        if (!(WINO43_PROBE & 256))                                                                                 \
+                            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, sv_[k]), orsrc, (int)vo_, (dyk * W + dxk) * a.out_C * 4, W43_STORE_AUX); \
+                    }                                                                                                              \
+                    __builtin_amdgcn_sched_barrier(0);                                                                             \
+                }                                                                                                                  \
+            }                                                                                                                      \
+        }                                                                                                                          \
+
+    bool first_block = true;
+    for (;;) {
+        const int blk_next = blk + nslots;
+        const bool has_next = blk_next < blk_end;
+        if (has_next) nxt = make_tile(blk_next);
+        const f32x2 bias2 = a.bias ? *reinterpret_cast<const f32x2 *>(a.bias + 32 * cur.nb + 2 * (l & 15)) : (f32x2){0.f, 0.f};
+        __builtin_amdgcn_s_waitcnt(0x8F71);                // vmcnt(33), see above
+        W43S_CHUNK(0, 0, true)
+        W43S_CHUNK(1, 1, false)
+        for (int c = 2; c < NC; c += 2) {
+            W43S_CHUNK(c, 0, false)
+            W43S_CHUNK(c + 1, 1, false)
+        }
+#if !(WINO43_PROBE & 8)
+        if (wv == 0) W43S_EPILOGUE(0, 0) else if (wv == 1) W43S_EPILOGUE(1, 0) else if (wv == 2) W43S_EPILOGUE(0, 1) else W43S_EPILOGUE(1, 1)
+#else
+        {
+            float sum = 0.f;
+#pragma unroll
+            for (int q = 32; q < 36; ++q) sum += acc[2 * q][0] + acc[2 * q + 1][1];
+            if (sum == 12345.678f) a.out[0] = sum;
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+#endif
+        if (!has_next) break;
+        cur = nxt;
+        blk = blk_next;
+        first_block = false;
+    }
+#undef W43S_CHUNK
+#undef W43S_EPILOGUE
+}
+
+// Supported: Cin % 16 == 0, Cin >= 32 (as above), Cout % 128 == 0 (four blocks of 32 output channels per workgroup)
+LIDAR_EXPORT size_t lidar_wino43s_packed_floats(int Cin, int Cout) {
+    if (Cin < 32 || Cout <= 0 || (Cin & 15) || (Cout & 127)) return 0;
+    return (size_t)36 * Cin * Cout;
+}
+
+LIDAR_EXPORT int lidar_wino43s_supported(int Cin, int Cout) { return lidar_wino43s_packed_floats(Cin, Cout) != 0; }
+
+LIDAR_EXPORT int lidar_wino43s_pack_weights(const float *w, int Cin, int Cout, float *packed, void *stream) {
+    if (!w || !packed || !lidar_wino43s_supported(Cin, Cout)) return LIDAR_ERR_ARG;
+    hipLaunchKernelGGL(wino43s_pack_kernel, dim3(divup((long long)Cin * Cout, 256)), dim3(256), 0, (hipStream_t)stream, w, Cin, Cout, packed);
+    return lidar_check_launch("lidar_wino43s_pack_weights");
+}
+
+// lidar_wino43_conv3x3_nhwc on the shared-transform shape: same arguments and limits, `packed` from lidar_wino43s_pack_weights
+LIDAR_EXPORT int lidar_wino43s_conv3x3_nhwc(const float *in, int B, int H, int W, int Cin, int in_C, const float *packed, const float *bias, int relu,
+                                            int Cout, float *out, int out_C, int out_off, void *stream) {
+    if (!in || !packed || !out || B <= 0 || H <= 0 || W <= 0 || !lidar_wino43s_supported(Cin, Cout) || out_off < 0 || out_off + Cout > out_C ||
+        in_C < Cin)
+        return LIDAR_ERR_ARG;
+    if ((reinterpret_cast<uintptr_t>(in) & 15) || (reinterpret_cast<uintptr_t>(packed) & 15) || (in_C & 3)) return LIDAR_ERR_ARG;
+    if ((reinterpret_cast<uintptr_t>(out) & 15) || (out_C & 3) || (out_off & 3)) return LIDAR_ERR_ARG;
+    if ((long long)B * H * W * in_C * 4 >= 0x7fffffffll) return LIDAR_ERR_ARG;
+    if ((long long)B * H * W * out_C * 4 >= 0x7fffffffll) return LIDAR_ERR_ARG;
+    Wino43Args a;
+    a.in = in; a.upk = packed; a.bias = bias; a.out = out;
+    a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.in_C = in_C; a.out_C = out_C; a.out_off = out_off; a.relu = relu;
+    // tile group shape: whichever of 4 x 4, 2 x 8, 8 x 2 tiles covers the map with the fewest groups (one group per workgroup block)
+    const int tiles_y = (H + 3) / 4, tiles_x = (W + 3) / 4;
+    const int shapes[3][2] = {{4, 4}, {2, 8}, {8, 2}};
+    int best = 0;
+    long long best_n = -1;
+    for (int s = 0; s < 3; ++s) {
+        const long long n = (long long)divup(tiles_y, shapes[s][0]) * divup(tiles_x, shapes[s][1]);
+        if (best_n < 0 || n < best_n) { best_n = n; best = s; }
+    }
+    a.blocks_y = divup(tiles_y, shapes[best][0]);
+    a.blocks_x = divup(tiles_x, shapes[best][1]);
+    a.n_groups = Cout / 128;
+    const long long nblk = (long long)B * a.blocks_y * a.blocks_x * a.n_groups;
+    if (nblk > 0x7ffffff0ll) return LIDAR_ERR_ARG;
+    a.n_blocks = (int)nblk;
+    long long want = ((nblk + 7) / 8) * 8;
+    const long long cap = ((long long)w43_cu_count() / 8) * 8;
+    if (cap >= 8 && want > cap) want = cap;
+    const dim3 grid((unsigned)want), blk(256);
+    hipStream_t s = (hipStream_t)stream;
+    int dev_id = 0;
+    (void)hipGetDevice(&dev_id);
+    dev_id &= 63;
+#define W43S_LAUNCH(TYV, TXV) do {                                                                                                 \
+        static bool attr_set[64] = {};                                                                                            \
+        if (!attr_set[dev_id]) {                                                                                                  \
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&wino_f43s_kernel<TYV, TXV>), hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                      (int)w43s_lds_bytes(TYV, TXV));                                                              \
+            attr_set[dev_id] = true;                                                                                              \
+        }                                                                                                                         \
+        hipLaunchKernelGGL((wino_f43s_kernel<TYV, TXV>), grid, blk, w43s_lds_bytes(TYV, TXV), s, a);                              \
+    } while (0)
+    if (best == 0) W43S_LAUNCH(4, 4);
+    else if (best == 1) W43S_LAUNCH(2, 8);
+    else W43S_LAUNCH(8, 2);
+#undef W43S_LAUNCH
+    return lidar_check_launch("lidar_wino43s_conv3x3_nhwc");
+}

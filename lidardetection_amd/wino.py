@@ -10,6 +10,10 @@ from . import _lib
 # which Winograd kernel the model code gets for a layer both support: 1 (default) = F(4x4, 3x3) (csrc/wino43_conv.hip: fewer MFMA
 # cycles, |error| ~ 1e-5 of the output scale), 0 = F(2x2, 3x3) everywhere (csrc/wino_conv.hip: ~ 2e-6).  A/B switch.
 _F43 = [os.environ.get("LIDAR_WINO_F43", "1") != "0"]
+# the F(4x4, 3x3) kernel's workgroup shape for layers with Cout % 128 == 0: 1 (default) = one tile group x four blocks of 32 output
+# channels (input transform and region DMA once per 128 output channels; own packed filter layout), 0 = two tile groups x two blocks
+# everywhere.  Bit-identical results.  A/B switch, read when the filters are packed (pack_auto).
+_F43_SHARE = [os.environ.get("LIDAR_WINO43_SHARE", "1") != "0"]
 
 
 def supported(cin, cout):
@@ -66,20 +70,46 @@ def pack_weights43(w):
     return packed
 
 
-def conv3x3_f43(x, packed, cout, bias=None, relu=True, out=None, out_offset=0, cin=None):
-    """conv3x3 through the F(4x4, 3x3) kernel.  cin: the layer reads channels [0, cin) of x (default: all of them)."""
+def supported43_share(cin, cout):
+    """the shared-transform shape of the F(4x4, 3x3) kernel takes this layer: Cin % 16 == 0, Cin >= 32, Cout % 128 == 0"""
+    return bool(_lib.lib().lidar_wino43s_supported(int(cin), int(cout)))
+
+
+def pack_weights43_share(w):
+    """pack_weights43 in the filter order of the shared-transform shape (conv3x3_f43(..., share=True)); the tensor carries the
+    mark `w43_share` by which conv3x3_auto tells the two layouts apart"""
+    _lib.require_cuda(w.contiguous())
+    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or w.dtype != torch.float32 or not supported43_share(w.shape[1], w.shape[0]):
+        raise _lib.LidarHipError(f"wino.pack_weights43_share: expected a float32 (Cout % 128 == 0, Cin % 16 == 0, 3, 3) weight, got {tuple(w.shape)}")
+    wc = w.detach().contiguous()
+    if wc.stride() != (wc.shape[1] * 9, 9, 3, 1):
+        wc = wc.clone(memory_format=torch.contiguous_format)
+    L = _lib.lib()
+    packed = torch.empty(L.lidar_wino43s_packed_floats(w.shape[1], w.shape[0]), dtype=torch.float32, device=w.device)
+    _lib.check(L.lidar_wino43s_pack_weights(_lib.ptr(wc), w.shape[1], w.shape[0], _lib.ptr(packed), _lib.stream()), "lidar_wino43s_pack_weights")
+    packed.w43_share = True
+    return packed
+
+
+def conv3x3_f43(x, packed, cout, bias=None, relu=True, out=None, out_offset=0, cin=None, share=False):
+    """conv3x3 through the F(4x4, 3x3) kernel.  cin: the layer reads channels [0, cin) of x (default: all of them).  share: the
+    shared-transform workgroup shape, `packed` from pack_weights43_share (bit-identical results)."""
     _lib.require_cuda(packed, bias)
     _lib.require_nhwc(x, "wino.conv3x3_f43")
     B, in_c, H, W = x.shape
     cin = in_c if cin is None else int(cin)
     L = _lib.lib()
-    if cin > in_c or packed.numel() != L.lidar_wino43_packed_floats(cin, cout) or packed.numel() == 0:
+    if bool(share) != bool(getattr(packed, "w43_share", False)):
+        raise _lib.LidarHipError("wino.conv3x3_f43: filters packed for the other workgroup shape (pack_weights43 / pack_weights43_share)")
+    size, run, name = ((L.lidar_wino43s_packed_floats, L.lidar_wino43s_conv3x3_nhwc, "lidar_wino43s_conv3x3_nhwc") if share else
+                       (L.lidar_wino43_packed_floats, L.lidar_wino43_conv3x3_nhwc, "lidar_wino43_conv3x3_nhwc"))
+    if cin > in_c or packed.numel() != size(cin, cout) or packed.numel() == 0:
         raise _lib.LidarHipError("wino.conv3x3_f43: packed filters do not match (Cin, Cout)")
     if bias is not None and bias.numel() != cout:
         raise _lib.LidarHipError("wino.conv3x3_f43: bias must hold Cout values")
     out, out_offset = _lib.nhwc_out("wino.conv3x3_f43", B, (H, W), cout, x.device, out, out_offset)
-    _lib.check(L.lidar_wino43_conv3x3_nhwc(_lib.ptr(x), B, H, W, cin, in_c, _lib.ptr(packed), _lib.ptr(bias), int(bool(relu)), int(cout),
-                                           _lib.ptr(out), out.shape[1], int(out_offset), _lib.stream()), "lidar_wino43_conv3x3_nhwc")
+    _lib.check(run(_lib.ptr(x), B, H, W, cin, in_c, _lib.ptr(packed), _lib.ptr(bias), int(bool(relu)), int(cout),
+                   _lib.ptr(out), out.shape[1], int(out_offset), _lib.stream()), name)
     return out
 
 
@@ -108,16 +138,18 @@ def pack_auto(w):
     """-> [kind, packed filters, weight, F(2x2) filters]: the filters of kernel_for(Cin, Cout).  An "f43" entry carries the
     F(2x2, 3x3) filters too (16 Cin Cout more floats), packed here on the caller's stream: a map too large for the F(4x4) kernel's
     32-bit byte offsets (f43_fits) is served by F(2x2), and filters packed on first need would be written on whichever stream met
-    that map first while another stream may already read them."""
+    that map first while another stream may already read them.  The F(4x4) filters are in the layout of the shared-transform
+    workgroup shape (pack_weights43_share) where LIDAR_WINO43_SHARE != 0 and Cout % 128 == 0; conv3x3_auto reads the mark."""
     if kernel_for(w.shape[1], w.shape[0]) == "f43":
-        return ["f43", pack_weights43(w), w.detach(), pack_weights(w)]
+        share = _F43_SHARE[0] and supported43_share(w.shape[1], w.shape[0])
+        return ["f43", pack_weights43_share(w) if share else pack_weights43(w), w.detach(), pack_weights(w)]
     return ["f23", pack_weights(w), None]
 
 
 def conv3x3_auto(x, packed, cout, bias=None, relu=True, out=None, out_offset=0):
     """conv3x3 with the filters of pack_auto: the kernel kernel_for names for this map, among those the filters were packed for"""
     if packed[0] == "f43" and kernel_for(x.shape[1], cout, x.shape, out) == "f43":
-        return conv3x3_f43(x, packed[1], cout, bias, relu, out, out_offset)
+        return conv3x3_f43(x, packed[1], cout, bias, relu, out, out_offset, share=getattr(packed[1], "w43_share", False))
     return conv3x3(x, packed[3 if packed[0] == "f43" else 1], cout, bias, relu, out, out_offset)   # ("f43" entry, oversize map: its F(2x2) filters)
 
 

@@ -18,7 +18,7 @@ for tok in sys.argv[1].split():                 # "bits" or "bits:EXTRA_DEFINE=v
     what = " + ".join(n for b, n in names.items() if v & b) or "product kernel"
     print(f"== probe {tok}: {what}")
     for ln in r.stdout.splitlines():
-        if "F(4x4)" in ln:
+        if "F(4x4)" in ln:               # "F(4x4) ..." the two-group shape, "F(4x4) shared ..." the shared-transform shape (Cout % 128 == 0)
             print("   ", ln.split("|")[0])
     if r.returncode:
         print(r.stderr[-400:])

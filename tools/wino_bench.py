@@ -40,6 +40,14 @@ for B, C, H, W in shapes:
                 e43 = float((wino.conv3x3_f43(x, p43, C, bias, True) - wino.conv3x3(x, packed, C, bias, True)).abs().max())
                 print(f"B{B} C{C} {H}x{W}: F(4x4) {t_4:.3f} ms, MFMA {2.0 * 9 * C * C * B * H * W / 1e9 / 4 / t_4 / 157.3:.3f} of peak, "
                       f"{t_w / t_4:.2f}x over F(2x2), max |diff| to it {e43:.2e} |", flush=True)
+                if wino.supported43_share(C, C):            # the shared-transform shape (Cout % 128 == 0), WINO_BENCH_REPEAT timings of each
+                    p4s = wino.pack_weights43_share(w)
+                    same = torch.equal(wino.conv3x3_f43(x, p4s, C, bias, True, share=True), wino.conv3x3_f43(x, p43, C, bias, True))
+                    rep = int(os.environ.get("WINO_BENCH_REPEAT", "3"))
+                    ts = [(ev(lambda: wino.conv3x3_f43(x, p43, C, bias, True)), ev(lambda: wino.conv3x3_f43(x, p4s, C, bias, True, share=True)))
+                          for _ in range(rep)]
+                    print(f"B{B} C{C} {H}x{W}: F(4x4) shared {min(t[1] for t in ts):.3f} ms (two-group {min(t[0] for t in ts):.3f}), repeats two-group "
+                          + " ".join(f"{t[0]:.4f}" for t in ts) + " shared " + " ".join(f"{t[1]:.4f}" for t in ts) + f", equal bits {same} |", flush=True)
             print(f"B{B} C{C} {H}x{W}: wino {t_w:.3f} ms, MFMA {2.0 * 9 * C * C * B * H * W / 1e9 * 16 / 36 / t_w / 157.3:.3f} of peak |", flush=True)
             continue
         t_m = ev(lambda: bias_act_(F.conv2d(x, wl, None, 1, 1), bias))
