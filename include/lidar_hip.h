@@ -750,6 +750,40 @@ int lidar_point_loss_backward(const float *point_cls_preds, const float *point_b
                               long long n, int num_class, const float *weights, const float *code_weights, const float *grad_out,
                               float *d_cls_preds, float *d_box_preds, float *d_part_preds, void *ws, size_t ws_bytes, void *stream);
 
+/* ------------------------------------------------------------------ fused optimiser step (training)
+ * What follows loss.backward() in the reference's loop (tools/train_utils/train_utils.py:36-42) for OPTIMIZER: adam_onecycle:
+ * clip_grad_norm_(model.parameters(), GRAD_NORM_CLIP), then OptimWrapper.step (tools/train_utils/optimization/fastai_optim.py:
+ * 132-149, built by tools/train_utils/optimization/__init__.py:19-32): p.data.mul_(1 - wd * lr) over every parameter with
+ * requires_grad, then torch.optim.Adam with betas (mom, 0.99).  Here: three launches over all tensors at once, on the caller's
+ * stream; no host read, no allocation, no float atomics, bitwise reproducible; fp32 only (csrc/optim_step.hip).
+ *   table DEVICE (n_tensors, LIDAR_OPTIM_ENTRY) 64-bit words per tensor: param, grad, exp_avg, exp_avg_sq addresses (contiguous
+ *       f32, 4-byte aligned; 16-byte aligned tensors move as 16-byte vectors), numel, step lag (steps of the optimiser this tensor
+ *       sat out: its bias corrections use t - lag).  A NULL grad is a parameter without a gradient this step: it takes no part
+ *       in the norm and gets the decay only, its state is not touched.  Parameters that do not require a gradient are not listed.
+ *   chunk map DEVICE: chunk c covers elements [chunk_index[c] * LIDAR_OPTIM_CHUNK, + LIDAR_OPTIM_CHUNK) of tensor chunk_tensor[c].
+ *       lidar_optim_plan (pure HOST, host pointers) writes the map of a list of numel values, tensor by tensor, and returns the
+ *       number of chunks (at most `capacity` are written; chunk_tensor / chunk_index may be NULL to count only; < 0: error).
+ *   lidar_optim_grad_norm -> norm_out DEVICE (2) f32: total_norm = sqrt(sum g^2) (squares and sums in fp64, one rounding to fp32)
+ *       and the clip coefficient min(1, max_norm / (total_norm + 1e-6)), torch.nn.utils.clip_grad_norm_'s with norm_type 2.
+ *       ws: lidar_optim_workspace_bytes(n_chunks) bytes, 8-byte aligned.  n_chunks 0: total_norm 0.
+ *   lidar_optim_adam_step: per element, g = norm_out[1] * grad, p *= (float)decay (the caller passes the double 1 - wd * lr),
+ *       m += (1 - beta1) * (g - m), v = beta2 * v + (1 - beta2) * g * g, denom = sqrt(v) / sqrt(1 - beta2^t) + eps,
+ *       p -= lr / (1 - beta1^t) * m / denom: torch's single-tensor Adam, the CURRENT beta1 in the bias correction as torch has it
+ *       when betas change between steps.  t >= 1: the optimiser's step count after this step.
+ *       flags: LIDAR_OPTIM_WRITE_CLIPPED stores g back (what clip_grad_norm_ leaves), LIDAR_OPTIM_ZERO_GRAD stores zeros, 0 leaves
+ *       the gradient as it is.  Non-finite norms propagate as in the reference. */
+#define LIDAR_OPTIM_CHUNK 1024
+#define LIDAR_OPTIM_ENTRY 6
+#define LIDAR_OPTIM_WRITE_CLIPPED 1
+#define LIDAR_OPTIM_ZERO_GRAD 2
+long long lidar_optim_plan(const long long *numel, int n_tensors, int *chunk_tensor, int *chunk_index, long long capacity);
+size_t lidar_optim_workspace_bytes(long long n_chunks);
+int lidar_optim_grad_norm(const long long *table, int n_tensors, const int *chunk_tensor, const int *chunk_index,
+                          long long n_chunks, float max_norm, float *norm_out, void *ws, size_t ws_bytes, void *stream);
+int lidar_optim_adam_step(const long long *table, int n_tensors, const int *chunk_tensor, const int *chunk_index,
+                          long long n_chunks, const float *norm_out, double lr, double beta1, double beta2, double eps,
+                          double decay, long long t, int flags, void *stream);
+
 /* HeightCompression in one pass (pcdet/models/backbones_2d/map_to_bev/height_compression.py:21-24): the (N, C*D, H, W) BEV
  * map of a sparse tensor written directly channels-last: out[b][h][w][c*D + d]; D <= 4, channels % 4 == 0; same workspace
  * as lidar_sparse_to_dense. */

@@ -161,6 +161,11 @@ SIGNATURES = {
     "lidar_point_loss_ws_bytes": (sz, [C.c_longlong]),
     "lidar_point_loss_forward": (i32, [vp, vp, vp, vp, vp, vp, C.c_longlong, i32, vp, vp, vp, vp, sz, vp]),
     "lidar_point_loss_backward": (i32, [vp, vp, vp, vp, vp, vp, C.c_longlong, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "lidar_optim_plan": (C.c_longlong, [vp, i32, vp, vp, C.c_longlong]),
+    "lidar_optim_workspace_bytes": (sz, [C.c_longlong]),
+    "lidar_optim_grad_norm": (i32, [vp, i32, vp, vp, C.c_longlong, f32, vp, vp, sz, vp]),
+    "lidar_optim_adam_step": (i32, [vp, i32, vp, vp, C.c_longlong, vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
+                                    C.c_longlong, i32, vp]),
     "lidar_rotate_iou_eval": (i32, [vp, i32, vp, i32, i32, vp, vp]),
     "lidar_boxes_iou_bev_cpu": (i32, [vp, i32, vp, i32, vp]),
     "lidar_points_in_boxes_cpu": (i32, [vp, i32, vp, i32, vp]),

@@ -253,6 +253,17 @@ class PointPillarKITTI(nn.Module):
             head = self.backbone_head_train(canvas, wgrad, deblock)
         return self.rpn_loss(head, gt_boxes)
 
+    def train_step(self, points, point_offsets, gt_boxes, optimizer, **train_loss_kwargs):
+        """One training iteration as the reference's loop runs it (tools/train_utils/train_utils.py:36-42) with
+        optimizer = optim.AdamOneCycle(self, ...): zero_grad, train_loss, backward of the sum of its three terms, optimizer.step()
+        (gradient-norm clip, weight decay and Adam in one fused step).  -> (cls_loss, loc_loss, dir_loss, total_norm), detached
+        device tensors; total_norm is the gradient norm before clipping.  No host synchronisation."""
+        optimizer.zero_grad()
+        cls_loss, loc_loss, dir_loss = self.train_loss(points, point_offsets, gt_boxes, **train_loss_kwargs)
+        (cls_loss + loc_loss + dir_loss).backward()
+        total_norm = optimizer.step()
+        return cls_loss.detach(), loc_loss.detach(), dir_loss.detach(), total_norm
+
     def _loss_head(self):
         if self.__dict__.get("_rpn_loss_head") is None:
             from .pcdet.models.dense_heads.anchor_head_template import AnchorHeadTemplate
