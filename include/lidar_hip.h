@@ -640,6 +640,62 @@ int lidar_proposal_target(const float *rois, const float *roi_scores, const long
                           long long *out_reg_valid, float *out_cls_labels, int *out_sampled, int *frame_status,
                           float *max_overlaps, int *gt_assignment, void *stream);
 
+/* ------------------------------------------------------------------ train-time augmentation (GT sampling, world transforms, range)
+ * Everything the reference does per frame in DataLoader workers between "raw cloud + annotations" and "points the voxeliser sees",
+ * for a whole batch in ONE call on the caller's stream (csrc/augment.hip, five launches): no host read, no float atomics, bitwise
+ * reproducible, graph-capturable.  The kernels draw nothing: which database objects are candidates, the flips, angles and scales
+ * come from the caller.  Reference: pcdet/datasets/augmentor/database_sampler.py (__call__ :181-232, add_sampled_boxes_to_scene
+ * :118-179), augmentor_utils.py :6-109, data_augmentor.py:108-134, pcdet/datasets/processor/data_processor.py:19-34.
+ *   points (n_points, C) f32, point_offsets (batch + 1) i32 DEVICE; gt_boxes (batch, max_gt, 8) f32 [box | class id], gt_counts
+ *   (batch) i32: real rows per frame.  A row inside the count with class id 0 is an annotated object of a class that is not trained:
+ *   it takes part in the collision test and is dropped from the output (gt_boxes_mask + keep_arrays_by_name of the reference).
+ *   Database: db_points (db_rows, C) f32 object-local points (relative to the box centre), db_offsets (n_obj + 1) i32, db_boxes
+ *   (n_obj, 7) f32, db_cls (n_obj) i32 1-based class ids.  cand (batch, groups, per_group) i32 database indices in SAMPLE_GROUPS
+ *   order, -1 = no candidate (an index outside [0, n_obj) counts as -1).
+ *   Per frame, DEVICE: flip_x, flip_y (batch) i32 0/1; rot (batch) f32 and rot_cs (batch, 2) f32 = [cos, sin] of it, taken in double on
+ *   the host and rounded once; scale (batch) f32 or NULL (scaling skipped: the reference's `< 1e-3` range test is a host decision);
+ *   sample_rot (batch, groups, per_group) f32 or NULL (SAMPLE_ROT_ANGLE); plane (batch, 4) f32 or NULL (USE_ROAD_PLANE): the lidar
+ *   height of the road under (x, y, z) is plane . [x, y, z, 1] (put_boxes_on_road_planes is affine in the box centre).
+ *   HOST: remove_extra_width[3] (REMOVE_EXTRA_WIDTH), collide_extra_width[3] or NULL (REMOVE_SAMPLE_BOXES_EXTRA_WIDTH), pc_range[6],
+ *   remove_outside_boxes, min_num_corners (0..8).
+ * Per frame, in the reference's order:
+ *   1. collision test (:194-227): groups in order; a candidate is valid iff its rotated BEV IoU (boxes_iou_bev_cpu's expression on the
+ *      clipper of csrc/iou3d_dev.h) is exactly 0 against every existing box (all real input rows + the valid samples of earlier
+ *      groups) and against every OTHER candidate of its group, valid or not; both boxes' dims + collide_extra_width when given;
+ *   2. road plane: mv = z - dz / 2 - plane . [x, y, z, 1], z -= mv; heading += sample_rot (both after the collision test);
+ *   3. paste and carve: a scene point inside any valid sample's box enlarged by remove_extra_width is removed, with the semantics of
+ *      points_in_boxes_cpu (xy margin 1e-2, fabsf(z - cz) > dz / 2 is outside); object points are rotated by sample_rot about the
+ *      object's origin, translated to the database box centre, z -= mv;
+ *   4. world flip x (y, heading negated), flip y (x negated, heading = -(heading + pi)), rotation about z (rotate_points_along_z's
+ *      matrix; heading += rot), scaling of columns 0..5 / points 0..2, then limit_period(heading, 0.5, 2 pi);
+ *   5. range mask: points kept iff x and y lie in [min, max], both ends closed (z is not tested); with remove_outside_boxes a box is
+ *      kept iff at least min_num_corners of its 8 corners lie inside the closed 3-D range;
+ *   6. stable compaction.
+ * -> out_points (cap, C): per frame the valid pasted objects' points in (group, candidate) order, then the surviving scene points in
+ *    input order (rows at and past out_offsets[batch] are not written); out_offsets (batch + 1) i32; out_gt_boxes (batch, max_gt +
+ *    groups * per_group, 8) zero-padded, the trained input rows first in input order, then the valid samples; out_gt_counts (batch);
+ *    sample_valid (batch, groups, per_group) i32.
+ * cap: rows of out_points.  obj_rows_bound: the caller's sum of the point counts of every candidate's object; a call with
+ * cap < n_points + obj_rows_bound is refused on the host, and no row at or past cap is ever written.
+ * Supported (lidar_augment_supported, pure host; everything else is refused with LIDAR_ERR_ARG before any launch): 3 <= C <= 8,
+ * 1 <= groups <= 8, 0 <= per_group <= 64, max_gt + groups * per_group <= 512; batch >= 0 (0 launches nothing); frames of 0 points
+ * and frames with gt_counts 0 are valid.  With C == 4 the point arrays, and always out_gt_boxes, must be 16-byte aligned.
+ * NOT built: the `locations` / `rotations_y` multi-frame extras of the reference, and velocity columns (boxes are 7 wide). */
+#define LIDAR_AUGMENT_MAX_FEATURES 8
+#define LIDAR_AUGMENT_MAX_GROUPS 8
+#define LIDAR_AUGMENT_MAX_PER_GROUP 64
+#define LIDAR_AUGMENT_MAX_BOXES 512
+int lidar_augment_supported(int num_features, int max_gt, int groups, int per_group);
+size_t lidar_augment_workspace_bytes(int batch, int groups, int per_group, int cap);
+int lidar_augment(const float *points, const int *point_offsets, int n_points, int num_features, const float *gt_boxes,
+                  const int *gt_counts, int batch, int max_gt, const float *db_points, const int *db_offsets, const float *db_boxes,
+                  const int *db_cls, int n_obj, int db_rows, const int *cand, int groups, int per_group, const int *flip_x,
+                  const int *flip_y, const float *rot, const float *rot_cs, const float *scale, const float *sample_rot,
+                  const float *plane, const float *remove_extra_width, const float *collide_extra_width, const float *pc_range,
+                  int remove_outside_boxes, int min_num_corners, long long obj_rows_bound, int cap, float *out_points,
+                  int *out_offsets, float *out_gt_boxes, int *out_gt_counts, int *sample_valid, void *ws, size_t ws_bytes,
+                  void *stream);
+
 /* ------------------------------------------------------------------ anchor-head RPN loss (training), forward + backward
  * AnchorHeadTemplate.get_loss / AnchorHeadMulti.get_loss for a whole batch and every head, no host synchronisation, no float atomics
  * (csrc/anchor_loss.hip).  Reference: pcdet/models/dense_heads/anchor_head_template.py:102-224 (get_cls_layer_loss,

@@ -147,6 +147,10 @@ SIGNATURES = {
     "lidar_proposal_target_supported": (i32, [i32, i32, i32, i32]),
     "lidar_proposal_target": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, f32, f32, f32, f32, f32, vp, vp,
                                     vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "lidar_augment_supported": (i32, [i32, i32, i32, i32]),
+    "lidar_augment_workspace_bytes": (sz, [i32, i32, i32, i32]),
+    "lidar_augment": (i32, [vp, vp, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp,
+                            vp, vp, vp, i32, i32, C.c_longlong, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
     "lidar_anchor_loss_workspace_bytes": (sz, [i32, vp, i32]),
     "lidar_anchor_loss_forward": (i32, [vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, C.c_longlong, i32, i32, i32, vp, vp, i32,
                                         vp, vp, sz, vp]),
