@@ -325,7 +325,14 @@ int lidar_spconv_subm_table(const int *indices, int n, int D, int H, int W, int 
                             size_t capacity, int *nbr, void *stream);
 /* SparseConv3d rulebook in two phases (the caller reads *num_out in between to size nbr):
  *   phase 1 -> out_indices (out_cap >= n*prod ceil(k/s) rows, 4), *num_out; output rows in first-touch order
- *   phase 2 -> nbr (num_out, K) and nbr_t (n, K) = transposed table (inverse conv / input gradient) */
+ *   phase 2 -> nbr (num_out, K) and nbr_t (n, K) = transposed table (inverse conv / input gradient)
+ * Refused with LIDAR_ERR_ARG before any launch, by phase 1 (lidar_spconv_conv_outputs) and by the grid builder's entry points
+ * below alike: a kernel size, stride, batch or extent <= 0, and a padded input thinner than the kernel along an axis (D + 2 pD <
+ * kD, ...: such a level has no output site; even kernels, mixed strides, stride > kernel and an extent of 1 with padding are all
+ * fine).  Phase 2 (lidar_spconv_conv_tables) takes no extents: it checks kernel, stride and counts only and relies on the
+ * workspace phase 1 filled.  lidar_spconv_build_hash refuses a capacity that is not a power of two or is below 2 n.
+ * Duplicated input coordinates: the LOWEST row is the one the forward tables (nbr, SubM table) name; in nbr_t every row of the
+ * coordinate, the losing ones included, holds the output rows its coordinate reaches (both builders). */
 size_t lidar_spconv_conv_table_workspace_bytes(int n, int kD, int kH, int kW, int sD, int sH, int sW);
 int lidar_spconv_conv_outputs(const int *indices, int n, int batch, int D, int H, int W, int kD, int kH, int kW, int sD,
                               int sH, int sW, int pD, int pH, int pW, int *out_indices, int out_cap, int *num_out,
@@ -363,7 +370,17 @@ int lidar_spconv_grid_outputs(const int *indices, int n, int batch, int D, int H
                               int pH, int pW, int *grid_out, int *out_indices, int *num_out, void *ws, size_t ws_bytes,
                               void *stream);
 /* indice_conv forward (and input gradient with the transposed table + transposed weights):
- * out (n_out, Cout) = sum_k in[nbr[., k]] @ weight[k] (+ bias); weight (K, Cin, Cout); fp32 MFMA; Cin, Cout <= 128 */
+ * out (n_out, Cout) = sum_k in[nbr[., k]] @ weight[k] (+ bias); weight (K, Cin, Cout); fp32 MFMA; 1 <= Cin, Cout <= 128, any K > 0,
+ * n_out >= 0 (0: nothing is launched); everything else is LIDAR_ERR_ARG before any launch.
+ *
+ * Limits on K of the mask-ordered route, in one place:
+ *   lidar_spconv_row_masks                  K <= 32   one bit per offset in an int32; offset 31 is the SIGN bit of the mask
+ *   lidar_spconv_sorted_gemm_supported      K <= 32   and Cin in {16, 32, 64, 128}, Cout % 4 == 0, 1 <= Cout <= 128; the sorted entry points
+ *   lidar_spconv_packed_floats (!= 0)                 take both row_mask and order or (n_out == 0) neither, and refuse any other shape
+ *   lidar_spconv_mask_group                 K <= 31   its bin key holds K - popcount(mask) in 5 bits
+ *   spconv/ops.py sorted_gemm_supported     K <= 31   (it orders rows with lidar_spconv_mask_group)
+ * K = 32 on the mask-ordered route is therefore reached with lidar_spconv_row_masks + any sort of the (signed) masks, not through
+ * ops.mask_order; tests/test_gpu_spconv_kernel_support.py runs it. */
 int lidar_spconv_implicit_gemm(const float *in_features, const int *nbr, int n_out, int K, int Cin, int Cout,
                                const float *weight, const float *bias, float *out_features, void *stream);
 /* the same GEMM with the inference epilogue of the reference's SubMConv3d/SparseConv3d + BatchNorm1d + ReLU triplets

@@ -196,6 +196,9 @@ __global__ __launch_bounds__(RG_TPB) void rg_assign_kernel(const int *__restrict
 // ------------------------------------------------------------------ C ABI
 static bool rg_geom(RgGeom &g, int B, int D, int H, int W, int kD, int kH, int kW, int sD, int sH, int sW, int pD, int pH, int pW) {
     if (B <= 0 || D <= 0 || H <= 0 || W <= 0 || kD <= 0 || kH <= 0 || kW <= 0 || sD <= 0 || sH <= 0 || sW <= 0) return false;
+    // a padded input thinner than the kernel has no output site: (D + 2 p - k) / s TRUNCATES a negative numerator towards zero and
+    // would report one output plane for k - s < D + 2 p < k (2 planes, kernel 3, stride 2, no padding)
+    if (D + 2 * pD < kD || H + 2 * pH < kH || W + 2 * pW < kW) return false;
     g.B = B; g.D = D; g.H = H; g.W = W; g.kD = kD; g.kH = kH; g.kW = kW; g.K = kD * kH * kW;
     g.sD = sD; g.sH = sH; g.sW = sW; g.pD = pD; g.pH = pH; g.pW = pW;
     g.oD = (D + 2 * pD - kD) / sD + 1; g.oH = (H + 2 * pH - kH) / sH + 1; g.oW = (W + 2 * pW - kW) / sW + 1;

@@ -278,8 +278,10 @@ LIDAR_EXPORT size_t lidar_spconv_conv_table_workspace_bytes(int n, int kD, int k
 LIDAR_EXPORT int lidar_spconv_conv_outputs(const int *indices, int n, int batch, int D, int H, int W, int kD, int kH, int kW,
                                            int sD, int sH, int sW, int pD, int pH, int pW, int *out_indices, int out_cap,
                                            int *num_out, void *ws, size_t ws_bytes, void *stream) {
-    if (n < 0 || batch <= 0 || kD <= 0 || kH <= 0 || kW <= 0 || sD <= 0 || sH <= 0 || sW <= 0) return LIDAR_ERR_ARG;
+    if (n < 0 || batch <= 0 || D <= 0 || H <= 0 || W <= 0 || kD <= 0 || kH <= 0 || kW <= 0 || sD <= 0 || sH <= 0 || sW <= 0) return LIDAR_ERR_ARG;
     if (!num_out) return LIDAR_ERR_ARG;
+    // a padded input thinner than the kernel has no output site ((D + 2 p - k) / s truncates a negative numerator towards zero)
+    if (D + 2 * pD < kD || H + 2 * pH < kH || W + 2 * pW < kW) return LIDAR_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     if (n == 0) return hipMemsetAsync(num_out, 0, 4, s) == hipSuccess ? LIDAR_OK : LIDAR_ERR_LAUNCH;
     if (!indices || !out_indices || !ws) return LIDAR_ERR_ARG;
