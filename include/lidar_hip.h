@@ -619,6 +619,35 @@ int lidar_anchor_assign(const float *const *anchors, const long long *counts, co
                         int max_gt, int gt_cols, int code_size, int sincos, int norm_by_num_examples, int *labels, float *targets,
                         float *weights, void *ws, size_t ws_bytes, void *stream);
 
+/* ------------------------------------------------------------------ ATSS anchor target assignment (training)
+ * ATSSTargetAssigner.assign_targets (pcdet/models/dense_heads/target_assigner/atss_target_assigner.py:16-141) for a whole batch and
+ * every anchor set in one call on the caller's stream: no host read, no float atomics, bitwise reproducible, graph-capturable (three
+ * kernels in a line; csrc/atss_assign.hip).
+ *   anchors, counts   HOST arrays of num_sets entries: DEVICE pointer to the set's contiguous (counts[k], anchor_dim) anchors in
+ *                     output order (use_multihead: already permuted (3, 4, 0, 1, 2, 5)), and its anchor count
+ *   gt (batch, max_gt, gt_cols) f32 [box (gt_cols - 1) | class id].  Per frame the rows after the last one whose box columns do
+ *   not sum to 0 (fp32, left to right) are trimmed, row 0 always stays (:41-44); every kept gt meets every set (no class mask).
+ *   Per (frame, set, gt): the topk anchors by ascending (centre distance, anchor index) are candidates; threshold = mean + unbiased
+ *   std of their IoUs + 1e-6 (rotated BEV IoU, or 3D IoU with match_height; csrc/iou3d_dev.h); a candidate is positive when
+ *   iou >= threshold and its centre, rotated by -heading, has |x| <= dy / 2 and |y| <= dx / 2 (the reference's column swap, :109).
+ *   An anchor positive for several gts takes the largest IoU (then the lowest gt).  Each gt then forces the anchor of largest IoU
+ *   over the set (lowest index; anchor 0 when nothing overlaps) to itself; of several gts forcing one anchor the highest wins.
+ *   code_size == 6 + (sincos ? 2 : 1) + min(anchor_dim, gt_cols - 1) - 7
+ *   -> labels (batch, n_total) i32 = matched gt's class id (may be <= 0) or 0, targets (batch, n_total, code_size) f32 =
+ *   ResidualCoder.encode_torch where label > 0 else 0, weights (batch, n_total) f32 = 1 where label > 0 else 0; n_total = sum
+ *   counts, the sets one after the other.  Every output element is written by the call.
+ *   ws: lidar_atss_assign_workspace_bytes(batch, max_gt, num_sets, topk) bytes, 256-byte aligned: (batch, num_sets, max_gt,
+ *   topk + 1) i32 anchor indices, then the same shape of u64 priorities.
+ * Supported (lidar_atss_assign_supported, pure host; everything else is refused with LIDAR_ERR_ARG before any launch):
+ * 1 <= num_sets <= 16, anchor_dim >= 7, gt_cols >= 8, code_size <= 16, sincos and match_height in {0, 1}, 2 <= topk <= 32,
+ * topk <= counts[k] <= 2^30 for every set, 1 <= max_gt <= 256; batch >= 0 (0: nothing is launched), batch * num_sets * max_gt < 2^31. */
+int lidar_atss_assign_supported(const long long *counts, int num_sets, int anchor_dim, int gt_cols, int code_size, int sincos,
+                                int topk, int max_gt, int match_height);
+size_t lidar_atss_assign_workspace_bytes(int batch, int max_gt, int num_sets, int topk);
+int lidar_atss_assign(const float *const *anchors, const long long *counts, int num_sets, int anchor_dim, const float *gt, int batch,
+                      int max_gt, int gt_cols, int code_size, int sincos, int topk, int match_height, int *labels, float *targets,
+                      float *weights, void *ws, size_t ws_bytes, void *stream);
+
 /* ------------------------------------------------------------------ second-stage RoI target assignment (training)
  * ProposalTargetLayer.forward (pcdet/models/roi_heads/target_assigner/proposal_target_layer.py:13-238) and the canonical transform
  * of RoIHeadTemplate.assign_targets (pcdet/models/roi_heads/roi_head_template.py:101-131) for a whole batch in ONE launch on the

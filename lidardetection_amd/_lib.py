@@ -144,6 +144,9 @@ SIGNATURES = {
     "lidar_anchor_assign_workspace_bytes": (sz, [i32, i32, i32]),
     "lidar_anchor_assign": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, C.c_longlong, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp,
                                   vp, vp, vp, sz, vp]),
+    "lidar_atss_assign_supported": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32]),
+    "lidar_atss_assign_workspace_bytes": (sz, [i32, i32, i32, i32]),
+    "lidar_atss_assign": (i32, [vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
     "lidar_proposal_target_supported": (i32, [i32, i32, i32, i32]),
     "lidar_proposal_target": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, f32, f32, f32, f32, f32, vp, vp,
                                     vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),

@@ -17,6 +17,7 @@
 // fp32 expressions keep the reference's op order (the library builds with -ffp-contract=off); the reference's Python scalars
 // (pi, pi/4, the thresholds, 1e-6, 1e-5) are fp32 constants, as torch casts them before comparing or dividing.
 #include "common.h"
+#include "box_encode_dev.h"
 #include <math.h>
 
 #define AA_MAX_CLASSES 16
@@ -214,28 +215,9 @@ __global__ __launch_bounds__(AA_TILE) void anchor_assign_gtmax_kernel(AAParams p
     }
 }
 
-// ResidualCoder.encode_torch (box_coder_utils.py:13-42) of one (gt, anchor) pair.  log / sin / cos are evaluated in double and
-// rounded once; every other column is the reference's fp32 expression.
+// ResidualCoder.encode_torch (box_coder_utils.py:13-42) of one (gt, anchor) pair: csrc/box_encode_dev.h
 __device__ __forceinline__ void aa_encode(const AAParams &p, const float *g, const float *a, float *out) {
-    const float xa = a[0], ya = a[1], za = a[2], ra = a[6];
-    const float dxa = fmaxf(a[3], 1e-5f), dya = fmaxf(a[4], 1e-5f), dza = fmaxf(a[5], 1e-5f);
-    const float dxg = fmaxf(g[3], 1e-5f), dyg = fmaxf(g[4], 1e-5f), dzg = fmaxf(g[5], 1e-5f);
-    const float diagonal = sqrtf(dxa * dxa + dya * dya);
-    out[0] = (g[0] - xa) / diagonal;
-    out[1] = (g[1] - ya) / diagonal;
-    out[2] = (g[2] - za) / dza;
-    out[3] = (float)log((double)(dxg / dxa));
-    out[4] = (float)log((double)(dyg / dya));
-    out[5] = (float)log((double)(dzg / dza));
-    const float rg = g[6];
-    int q = 6;
-    if (p.sincos) {
-        out[q++] = (float)cos((double)rg) - (float)cos((double)ra);
-        out[q++] = (float)sin((double)rg) - (float)sin((double)ra);
-    } else {
-        out[q++] = rg - ra;
-    }
-    for (int e = 7; q < p.code_size; ++e) out[q++] = g[e] - a[e];   // zip(cgs, cas): code_size was checked on the host
+    residual_encode(g, a, out, p.sincos, p.code_size);   // zip(cgs, cas): code_size was checked on the host
 }
 
 // ---------------------------------------------------------------- assign: labels, targets, weights

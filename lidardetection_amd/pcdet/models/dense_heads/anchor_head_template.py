@@ -5,7 +5,7 @@ methods.  The static add_sin_difference and get_direction_target are small torch
 path does not call them).
 
 Construction makes the anchors (AnchorGenerator mirror, padded with zero columns up to the coder's code size) and the target assigner
-(AxisAlignedTargetAssigner mirror).  `box_coder` stands in for ResidualCoder with the two attributes the assigner and the loss read,
+(AxisAlignedTargetAssigner mirror, or the ATSSTargetAssigner mirror for TARGET_ASSIGNER_CONFIG.NAME 'ATSS').  `box_coder` stands in for ResidualCoder with the two attributes the assigner and the loss read,
 code_size and encode_angle_by_sincos.  Head convolutions, forward() and generate_predicted_boxes are not part of this mirror.
 
 get_loss returns (rpn_loss, tb_dict) with the reference's keys; each float in tb_dict is a host synchronisation, as it is in the
@@ -20,6 +20,7 @@ import torch.nn.functional as F
 
 from .... import anchor_loss
 from .target_assigner.anchor_generator import AnchorGenerator
+from .target_assigner.atss_target_assigner import ATSSTargetAssigner
 from .target_assigner.axis_aligned_target_assigner import AxisAlignedTargetAssigner
 
 
@@ -62,6 +63,9 @@ class AnchorHeadTemplate(nn.Module):
         return sets, per_loc
 
     def get_target_assigner(self, anchor_target_cfg):
+        if anchor_target_cfg.NAME == 'ATSS':   # the reference's own call form (anchor_head_template.py:56-62)
+            return ATSSTargetAssigner(topk=anchor_target_cfg.TOPK, box_coder=self.box_coder, use_multihead=self.use_multihead,
+                                      match_height=anchor_target_cfg.MATCH_HEIGHT)
         if anchor_target_cfg.NAME != 'AxisAlignedTargetAssigner':
             raise NotImplementedError(f"AnchorHeadTemplate: target assigner {anchor_target_cfg.NAME} is not mirrored")
         return AxisAlignedTargetAssigner(self.model_cfg, self.class_names, self.box_coder,
