@@ -220,6 +220,16 @@ def check(status, what):
         raise LidarHipError(f"{what} failed with status {status}")
 
 
+def fail(what, msg):
+    """refuse an argument of the wrapper `what`"""
+    raise LidarHipError(f"{what}: {msg}")
+
+
+def cfg_get(cfg, key, default=None):
+    """an entry of a model config, which is a dict (EasyDict) in the reference and may be a plain namespace in tests"""
+    return cfg.get(key, default) if hasattr(cfg, "get") else getattr(cfg, key, default)
+
+
 def ptr(t):
     """device (or host) address of a torch tensor / None."""
     return None if t is None else C.c_void_p(t.data_ptr())

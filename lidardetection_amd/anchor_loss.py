@@ -12,6 +12,7 @@ from dataclasses import dataclass
 import torch
 
 from . import _lib
+from ._lib import cfg_get
 
 MAX_HEADS = 16    # csrc/anchor_loss.hip: AL_MAX_HEADS
 MAX_CODE = 16     # AL_MAX_CODE
@@ -41,18 +42,14 @@ class LossSpec:
     num_dir_bins: int
 
 
-def _get(cfg, key, default=None):
-    return cfg.get(key, default) if hasattr(cfg, "get") else getattr(cfg, key, default)
-
-
 def spec_from_cfg(model_cfg, num_class, head_num_classes=None):
     """model_cfg: a DENSE_HEAD config (LOSS_CONFIG, DIR_OFFSET, NUM_DIR_BINS, USE_DIRECTION_CLASSIFIER, USE_MULTIHEAD,
     SEPARATE_MULTIHEAD).  head_num_classes: AnchorHeadMulti's per-head class counts (rpn_heads[i].num_class); None for
     AnchorHeadTemplate.  Multi with SEPARATE_MULTIHEAD: head i compares its columns with one-hot columns sum(c[<i]) ..; without
     it every head predicts all num_class columns."""
-    loss_cfg = _get(model_cfg, "LOSS_CONFIG")
-    lw = _get(loss_cfg, "LOSS_WEIGHTS")
-    reg = _get(loss_cfg, "REG_LOSS_TYPE", None) or "WeightedSmoothL1Loss"
+    loss_cfg = cfg_get(model_cfg, "LOSS_CONFIG")
+    lw = cfg_get(loss_cfg, "LOSS_WEIGHTS")
+    reg = cfg_get(loss_cfg, "REG_LOSS_TYPE", None) or "WeightedSmoothL1Loss"
     if reg not in REG_LOSSES:
         raise NotImplementedError(f"anchor_head_loss: REG_LOSS_TYPE {reg!r} is not supported ({sorted(REG_LOSSES)})")
     if lw.get("code_weights") is None:
@@ -62,7 +59,7 @@ def spec_from_cfg(model_cfg, num_class, head_num_classes=None):
         raise NotImplementedError(f"anchor_head_loss: code size {len(code_weights)} outside 7..{MAX_CODE}")
     num_class = int(num_class)
     multihead = head_num_classes is not None
-    separate = bool(_get(model_cfg, "SEPARATE_MULTIHEAD", False)) if multihead else False
+    separate = bool(cfg_get(model_cfg, "SEPARATE_MULTIHEAD", False)) if multihead else False
     if multihead:
         heads = [int(c) for c in head_num_classes]
         if separate:
@@ -79,15 +76,15 @@ def spec_from_cfg(model_cfg, num_class, head_num_classes=None):
         raise NotImplementedError(f"anchor_head_loss: 1..{MAX_HEADS} heads, got {len(heads)}")
     if any(not 0 < c <= MAX_COLS for c in heads):
         raise NotImplementedError(f"anchor_head_loss: 1..{MAX_COLS} class columns per head, got {heads}")
-    use_dir = bool(_get(model_cfg, "USE_DIRECTION_CLASSIFIER", False))
-    bins = int(_get(model_cfg, "NUM_DIR_BINS", 2) or 0)
+    use_dir = bool(cfg_get(model_cfg, "USE_DIRECTION_CLASSIFIER", False))
+    bins = int(cfg_get(model_cfg, "NUM_DIR_BINS", 2) or 0)
     if use_dir and not 0 < bins <= MAX_BINS:
         raise NotImplementedError(f"anchor_head_loss: NUM_DIR_BINS {bins} outside 1..{MAX_BINS}")
     return LossSpec(num_class=num_class, multihead=multihead, separate=separate, head_classes=tuple(heads),
                     head_class_offsets=tuple(offs), cls_weight=float(lw["cls_weight"]), loc_weight=float(lw["loc_weight"]),
                     dir_weight=float(lw.get("dir_weight", 0.0)) if use_dir else 0.0, pos_cls_weight=pos_w,
                     neg_cls_weight=neg_w, code_weights=code_weights, reg_loss=reg, use_dir=use_dir,
-                    dir_offset=float(_get(model_cfg, "DIR_OFFSET", 0.0) or 0.0), num_dir_bins=bins)
+                    dir_offset=float(cfg_get(model_cfg, "DIR_OFFSET", 0.0) or 0.0), num_dir_bins=bins)
 
 
 def _heads(x, name, B, n_heads, last):

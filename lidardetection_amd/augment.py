@@ -18,10 +18,6 @@ from . import _lib
 MAX_FEATURES, MAX_GROUPS, MAX_PER_GROUP, MAX_BOXES = 8, 8, 64, 512      # include/lidar_hip.h: LIDAR_AUGMENT_*
 
 
-def _fail(msg):
-    raise _lib.LidarHipError("augment: " + msg)
-
-
 def fakelidar_to_lidar(boxes):
     """box_utils.boxes3d_kitti_fakelidar_to_lidar: [x, y, z bottom, w, l, h, r] -> [x, y, z centre, dx, dy, dz, heading]"""
     b = np.asarray(boxes, np.float32).copy()
@@ -43,13 +39,13 @@ class GtDatabase:
         cls = np.ascontiguousarray(cls, np.int32)
         n = len(cls)
         if points.ndim != 2 or not 3 <= points.shape[1] <= MAX_FEATURES:
-            _fail(f"database points must be (P, C) with 3 <= C <= {MAX_FEATURES}, got {points.shape}")
+            _lib.fail("augment", f"database points must be (P, C) with 3 <= C <= {MAX_FEATURES}, got {points.shape}")
         if boxes.shape != (n, 7) or offsets.shape != (n + 1,):
-            _fail(f"database boxes must be ({n}, 7) and offsets ({n + 1},), got {boxes.shape} and {offsets.shape}")
+            _lib.fail("augment", f"database boxes must be ({n}, 7) and offsets ({n + 1},), got {boxes.shape} and {offsets.shape}")
         if n and (offsets[0] != 0 or offsets[-1] != len(points) or np.any(np.diff(offsets) < 0)):
-            _fail("database offsets must ascend from 0 to the number of points")
+            _lib.fail("augment", "database offsets must ascend from 0 to the number of points")
         if np.any(cls < 1):
-            _fail("database class ids are 1-based")
+            _lib.fail("augment", "database class ids are 1-based")
         if fakelidar:
             points = points.copy()
             points[:, 2] -= np.repeat(boxes[:, 5] / 2, np.diff(offsets))
@@ -86,12 +82,12 @@ class DbSampler:
 
     def __init__(self, db, sample_groups, removed_difficulty=(), min_points=None, limit_whole_scene=False):
         if not 1 <= len(sample_groups) <= MAX_GROUPS:
-            _fail(f"1 <= number of sample groups <= {MAX_GROUPS}, got {len(sample_groups)}")
+            _lib.fail("augment", f"1 <= number of sample groups <= {MAX_GROUPS}, got {len(sample_groups)}")
         self.db = db
         self.groups = [(int(c), int(n)) for c, n in sample_groups]
         self.S = max(0, max(n for _, n in self.groups))
         if self.S > MAX_PER_GROUP:
-            _fail(f"sample number <= {MAX_PER_GROUP}, got {self.S}")
+            _lib.fail("augment", f"sample number <= {MAX_PER_GROUP}, got {self.S}")
         self.limit_whole_scene = bool(limit_whole_scene)
         min_points = min_points or {}
         self.pool = [db.indices_of_class(c, removed_difficulty, min_points.get(c, 0)) for c, _ in self.groups]
@@ -162,7 +158,7 @@ class TrainAugmentor:
         self.scale_range = tuple(float(v) for v in world_scale_range)
         self.apply_scale = not (self.scale_range[1] - self.scale_range[0] < 1e-3)           # augmentor_utils.py:99
         if any(a not in "xy" for a in flip_axes):
-            _fail(f"flip_axes must be a subset of 'xy', got {flip_axes!r}")
+            _lib.fail("augment", f"flip_axes must be a subset of 'xy', got {flip_axes!r}")
         self.flip_axes = "".join(flip_axes)
         self.sample_rot_range = None if sample_rot_range is None else tuple(float(v) for v in sample_rot_range)
         self.pc_range = [float(v) for v in pc_range]
@@ -196,27 +192,27 @@ class TrainAugmentor:
         point_offsets, gt_boxes) with host_offsets=None.  Rows of `points` at and past point_offsets[B] are unspecified."""
         db = self.db
         if points.dim() != 2 or points.dtype != torch.float32:
-            _fail(f"points must be float32 (sum N, C), got {points.dtype} {tuple(points.shape)}")
+            _lib.fail("augment", f"points must be float32 (sum N, C), got {points.dtype} {tuple(points.shape)}")
         n_points, C = (int(v) for v in points.shape)
         if C != db.C:
-            _fail(f"points have {C} columns, the database {db.C}")
+            _lib.fail("augment", f"points have {C} columns, the database {db.C}")
         if point_offsets.dim() != 1 or point_offsets.dtype != torch.int32 or point_offsets.shape[0] < 1:
-            _fail(f"point_offsets must be int32 (B + 1,), got {point_offsets.dtype} {tuple(point_offsets.shape)}")
+            _lib.fail("augment", f"point_offsets must be int32 (B + 1,), got {point_offsets.dtype} {tuple(point_offsets.shape)}")
         B = int(point_offsets.shape[0]) - 1
         if gt_boxes.dim() != 3 or gt_boxes.dtype != torch.float32 or gt_boxes.shape[0] != B or gt_boxes.shape[2] != 8:
-            _fail(f"gt_boxes must be float32 ({B}, M, 8), got {gt_boxes.dtype} {tuple(gt_boxes.shape)}")
+            _lib.fail("augment", f"gt_boxes must be float32 ({B}, M, 8), got {gt_boxes.dtype} {tuple(gt_boxes.shape)}")
         M = int(gt_boxes.shape[1])
         if tuple(gt_counts.shape) != (B,) or gt_counts.dtype != torch.int32:
-            _fail(f"gt_counts must be int32 ({B},), got {gt_counts.dtype} {tuple(gt_counts.shape)}")
+            _lib.fail("augment", f"gt_counts must be int32 ({B},), got {gt_counts.dtype} {tuple(gt_counts.shape)}")
         cand = np.asarray(cand)
         if cand.ndim != 3 or cand.shape[0] != B or cand.shape[1] != self.G or not np.issubdtype(cand.dtype, np.integer):
-            _fail(f"cand must be an integer ({B}, {self.G}, S) host array, got {cand.dtype} {cand.shape}")
+            _lib.fail("augment", f"cand must be an integer ({B}, {self.G}, S) host array, got {cand.dtype} {cand.shape}")
         S = int(cand.shape[2])
         if not (3 <= C <= MAX_FEATURES and 1 <= self.G <= MAX_GROUPS and 0 <= S <= MAX_PER_GROUP and M + self.G * S <= MAX_BOXES):
-            _fail(f"supported: 3 <= C <= {MAX_FEATURES}, 1 <= G <= {MAX_GROUPS}, 0 <= S <= {MAX_PER_GROUP}, M + G * S <= {MAX_BOXES}; "
-                  f"got C {C}, G {self.G}, S {S}, M {M}")
+            _lib.fail("augment", f"supported: 3 <= C <= {MAX_FEATURES}, 1 <= G <= {MAX_GROUPS}, 0 <= S <= {MAX_PER_GROUP}, M + G * S <= {MAX_BOXES}; "
+                      f"got C {C}, G {self.G}, S {S}, M {M}")
         if cand.size and (cand.max() >= db.n_obj or cand.min() < -1):
-            _fail(f"cand holds an index outside [-1, {db.n_obj})")
+            _lib.fail("augment", f"cand holds an index outside [-1, {db.n_obj})")
         dev = points.device
         # host bounds: every candidate's object counts, valid or not
         per_frame = np.where(cand >= 0, db.sizes[np.maximum(cand, 0)], 0).reshape(B, -1).sum(axis=1) if cand.size else np.zeros(B, np.int64)
@@ -225,9 +221,9 @@ class TrainAugmentor:
         if cap is None:
             cap = need
         if cap < need:
-            _fail(f"cap {cap} is smaller than the bound {need} (input points + the points of every candidate's object)")
+            _lib.fail("augment", f"cap {cap} is smaller than the bound {need} (input points + the points of every candidate's object)")
         if cap >= 2 ** 31 - 256 * (B + 2):
-            _fail(f"cap {cap} does not fit the kernels' int32 row indices")
+            _lib.fail("augment", f"cap {cap} does not fit the kernels' int32 row indices")
         if host_offsets is not None:
             n_in = np.diff(np.asarray(host_offsets, np.int64))
             n_max = int((n_in + per_frame).max()) if B else 0
@@ -243,10 +239,10 @@ class TrainAugmentor:
             if v is None:
                 if optional:
                     return None
-                _fail(f"{name} is neither given nor drawn (pass rng= or {name}=)")
+                _lib.fail("augment", f"{name} is neither given nor drawn (pass rng= or {name}=)")
             v = np.ascontiguousarray(v, dtype)
             if v.shape != shape:
-                _fail(f"{name} must have shape {shape}, got {v.shape}")
+                _lib.fail("augment", f"{name} must have shape {shape}, got {v.shape}")
             return v
 
         fx = pick("flip_x", flip_x, (B,), np.int32)
@@ -256,7 +252,7 @@ class TrainAugmentor:
         sr = pick("sample_rot", sample_rot, (B, self.G, S), np.float32, optional=self.sample_rot_range is None)
         pl = None if planes is None else np.ascontiguousarray(planes, np.float32)
         if pl is not None and pl.shape != (B, 4):
-            _fail(f"planes must be ({B}, 4), got {pl.shape}")
+            _lib.fail("augment", f"planes must be ({B}, 4), got {pl.shape}")
         rt64 = rt.astype(np.float64)
         rot_cs = np.stack([np.cos(rt64), np.sin(rt64)], axis=1).astype(np.float32)          # in double, rounded once
 
@@ -291,7 +287,7 @@ class TrainAugmentor:
         if shuffle:
             if shuffle_keys is None:
                 if rng is None:
-                    _fail("shuffle=True needs shuffle_keys (cap,) in [0, 1) or rng=")
+                    _lib.fail("augment", "shuffle=True needs shuffle_keys (cap,) in [0, 1) or rng=")
                 shuffle_keys = np.asarray(rng.random(cap), np.float32)
             keys = shuffle_keys if torch.is_tensor(shuffle_keys) else up(np.ascontiguousarray(shuffle_keys, np.float32))
             out["points"] = shuffle_points(out["points"], out["point_offsets"], keys)
@@ -303,7 +299,7 @@ def shuffle_points(points, point_offsets, keys):
     keys (rows,) f32 in [0, 1).  One device sort, no host read; rows past point_offsets[-1] stay where they are."""
     n = int(points.shape[0])
     if tuple(keys.shape) != (n,) or keys.dtype != torch.float32:
-        _fail(f"shuffle keys must be float32 ({n},), got {keys.dtype} {tuple(keys.shape)}")
+        _lib.fail("augment", f"shuffle keys must be float32 ({n},), got {keys.dtype} {tuple(keys.shape)}")
     rows = torch.arange(n, device=points.device, dtype=torch.int32)
     frame = torch.searchsorted(point_offsets[1:].contiguous(), rows, right=True)            # rows past the end: frame B
     last = int(point_offsets.shape[0]) - 1

@@ -56,17 +56,16 @@ struct AAWs {
 };
 
 static inline size_t aa_ws_layout(int B, int M, int ncls, AAWs *w, char *base) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return base ? base + o : nullptr; };
+    WsCarve c{base};
     char *p;
-    p = take(sizeof(int) * (size_t)B * (ncls + 1)); if (w) w->cls_start = (int *)p;
-    p = take(sizeof(int) * (size_t)B * ncls);       if (w) w->num_examples = (int *)p;
-    p = take(sizeof(float4) * (size_t)B * M);       if (w) w->bev = (float4 *)p;
-    p = take(sizeof(float) * (size_t)B * M);        if (w) w->area = (float *)p;
-    p = take(sizeof(int) * (size_t)B * M);          if (w) w->gt_row = (int *)p;
-    p = take(sizeof(int) * (size_t)B * M);          if (w) w->label = (int *)p;
-    p = take(sizeof(unsigned) * (size_t)B * M);     if (w) w->gtmax = (unsigned *)p;
-    return off;
+    p = c.take(sizeof(int) * (size_t)B * (ncls + 1)); if (w) w->cls_start = (int *)p;
+    p = c.take(sizeof(int) * (size_t)B * ncls);       if (w) w->num_examples = (int *)p;
+    p = c.take(sizeof(float4) * (size_t)B * M);       if (w) w->bev = (float4 *)p;
+    p = c.take(sizeof(float) * (size_t)B * M);        if (w) w->area = (float *)p;
+    p = c.take(sizeof(int) * (size_t)B * M);          if (w) w->gt_row = (int *)p;
+    p = c.take(sizeof(int) * (size_t)B * M);          if (w) w->label = (int *)p;
+    p = c.take(sizeof(unsigned) * (size_t)B * M);     if (w) w->gtmax = (unsigned *)p;
+    return c.off;
 }
 
 // boxes3d_lidar_to_aligned_bev_boxes (box_utils.py:261-272): |limit_period(h, 0.5, pi)| < pi/4 keeps (dx, dy), else swaps

@@ -15,11 +15,11 @@
 //   backward (same tiles)  d cls for every element, d box / d dir for the positives (zeros elsewhere), each scaled by its
 //            grad_output scalar read from device memory; staged through LDS so the stores run along the rows.
 //
-// Element math follows the reference's torch expressions op by op in fp32 (the library builds with -ffp-contract=off): expf /
-// log1pf / sinf / cosf are the device library's correctly-rounded-within-an-ulp fp32 functions, as torch's kernels call them.
-// The gradients are those of torch autograd on the reference expression: clamp(min=0) passes the gradient at 0, abs has derivative
-// 0 at 0, the focal weight is not detached, torch.where(n < β, ...) picks the branch at n == β.
+// The focal element and the conventions of the element math and its gradients are loss_dev.h's; the box term (al_box: sin
+// difference, L1 option, upstream factor folded into the gradient) and the direction term (al_dir) follow them in this file.
+// The ordered sums are common.h's block_sum / wave_sum.
 #include "common.h"
+#include "loss_dev.h"
 #include <math.h>
 
 #define AL_MAX_HEADS 16
@@ -52,12 +52,11 @@ struct ALWs {
 };
 
 static inline size_t al_ws_layout(int B, int tiles, ALWs *w, char *base) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return base ? base + o : nullptr; };
+    WsCarve c{base};
     char *p;
-    p = take(sizeof(float4) * (size_t)B * tiles); if (w) w->part = (float4 *)p;
-    p = take(sizeof(int) * (size_t)B);            if (w) w->npos = (int *)p;
-    return off;
+    p = c.take(sizeof(float4) * (size_t)B * tiles); if (w) w->part = (float4 *)p;
+    p = c.take(sizeof(int) * (size_t)B);            if (w) w->npos = (int *)p;
+    return c.off;
 }
 
 __device__ __forceinline__ int al_tile_head(const ALParams &p, int t) {
@@ -72,27 +71,6 @@ __device__ __forceinline__ int al_tile_head(const ALParams &p, int t) {
 __device__ __forceinline__ float al_onehot(const ALParams &p, const ALHead &H, int lab, int j) {
     const int le = (p.num_class == 1 && lab > 0) ? 1 : lab;
     return (lab >= 0 && le == H.c_idx + j + 1) ? 1.0f : 0.0f;
-}
-
-// SigmoidFocalClassificationLoss.forward of one element before the anchor weight; *dx: d(element)/dx as autograd forms it
-__device__ __forceinline__ float al_focal(float x, float tg, float *dx) {
-    const float p = 1.0f / (1.0f + expf(-x));                                // torch.sigmoid
-    const float aw = tg * 0.25f + (1.0f - tg) * 0.75f;                       // alpha_weight
-    const float pt = tg * (1.0f - p) + (1.0f - tg) * p;
-    const float fw = aw * (pt * pt);                                         // torch.pow(pt, 2.0) == pt * pt
-    const float e = expf(-fabsf(x));
-    const float bce = (fmaxf(x, 0.0f) - x * tg) + log1pf(e);
-    if (dx) {
-        // fw = aw * pt^2, pt(p), p = sigmoid(x): pow backward 2 * pt, sigmoid backward (1 - p) * p
-        const float dpt = aw * (2.0f * pt);
-        const float dp = dpt * (-tg) + dpt * (1.0f - tg);
-        const float dfw = dp * (1.0f - p) * p;
-        // bce: clamp(min=0) passes at x == 0, -x * t, log1p(exp(-|x|)) with sgn(0) == 0
-        const float sgn = x > 0.0f ? 1.0f : (x < 0.0f ? -1.0f : 0.0f);
-        const float dbce = (x >= 0.0f ? 1.0f : 0.0f) - tg - (e / (1.0f + e)) * sgn;
-        *dx = dfw * bce + fw * dbce;
-    }
-    return fw * bce;
 }
 
 // the anchor's direction bin (get_direction_target :148-161): floor(limit_period(t6 + a6 - off, 0, 2 pi) / (2 pi / bins)), clamped
@@ -125,9 +103,8 @@ __device__ __forceinline__ float al_box(const ALParams &p, const float *bx, cons
         const bool quad = !p.l1 && n < BETA;
         loss += p.l1 ? n : (quad ? 0.5f * (n * n) / BETA : n - HALF_BETA);
         if (dbox) {
-            const float sgn = d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f);
             const float dn = quad ? (g * 0.5f / BETA) * (2.0f * n) : g;       // d loss / d n
-            const float dd = (dn * sgn) * p.code_w[q];                         // d loss / d (in - t)
+            const float dd = (dn * sign0(d)) * p.code_w[q];                    // d loss / d (in - t)
             const float din = nan_t ? 0.0f : dd;                                // a NaN target: in - in, exactly 0
             const float dt = nan_t ? 0.0f : -dd;
             dbox[q] = ang ? din * ct * c6 + dt * st * (-s6) : din;
@@ -153,7 +130,7 @@ __global__ __launch_bounds__(AL_TILE) void anchor_loss_fwd_kernel(ALParams p, co
                                                                   const float *__restrict__ targets,
                                                                   const float *__restrict__ anchors, ALWs w) {
     __shared__ float s_buf[AL_TILE * AL_MAX_COLS];
-    __shared__ float4 s_red[AL_TILE / 64];
+    __shared__ BlockSumLds<AL_TILE / 64, 3, 1> s_red;
     const int tile = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
     const ALHead &H = p.h[al_tile_head(p, tile)];
     const long long i0 = (long long)(tile - H.tile_start) * AL_TILE;
@@ -164,43 +141,25 @@ __global__ __launch_bounds__(AL_TILE) void anchor_loss_fwd_kernel(ALParams p, co
     const float *src = H.cls + ((size_t)b * H.n + i0) * H.c;
     for (int e = t; e < nt * H.c; e += AL_TILE) s_buf[e] = src[e];
     __syncthreads();
-    float cls = 0.0f, loc = 0.0f, dir = 0.0f;
+    float sum[3] = {0.0f, 0.0f, 0.0f};      // cls, loc, dir
     if (lab >= 0) {
         const float cw = (lab > 0 ? p.pos_w : 0.0f) + (lab == 0 ? p.neg_w : 0.0f);
         float a = 0.0f;
-        for (int j = 0; j < H.c; ++j) a += al_focal(s_buf[t * H.c + j], al_onehot(p, H, lab, j), nullptr);
-        cls = a * cw;
+        for (int j = 0; j < H.c; ++j) a += sigmoid_focal(s_buf[t * H.c + j], al_onehot(p, H, lab, j), nullptr);
+        sum[0] = a * cw;
     }
     if (lab > 0) {
         const size_t row = (size_t)b * H.n + i0 + t;
         const float *tg = targets + ((size_t)b * p.n_total + g) * p.code;
-        loc = al_box(p, H.box + row * p.code, tg, 0.0f, nullptr);
+        sum[1] = al_box(p, H.box + row * p.code, tg, 0.0f, nullptr);
         if (H.dir) {
             const int k = al_dir_bin(p, tg[6], anchors[(size_t)g * p.anchor_dim + 6]);
-            dir = al_dir(p, H.dir + row * p.bins, k, 0.0f, nullptr);
+            sum[2] = al_dir(p, H.dir + row * p.bins, k, 0.0f, nullptr);
         }
     }
-    // fixed-order reduction: waves by shuffle, then the four waves in order
-    int np = lab > 0 ? 1 : 0;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        cls += __shfl_xor(cls, d, 64);
-        loc += __shfl_xor(loc, d, 64);
-        dir += __shfl_xor(dir, d, 64);
-        np += __shfl_xor(np, d, 64);
-    }
-    if (lane_id() == 0) s_red[t >> 6] = make_float4(cls, loc, dir, __int_as_float(np));
-    __syncthreads();
-    if (t == 0) {
-        float4 r = s_red[0];
-        int n = __float_as_int(r.w);
-        for (int k = 1; k < AL_TILE / 64; ++k) {
-            r.x += s_red[k].x; r.y += s_red[k].y; r.z += s_red[k].z;
-            n += __float_as_int(s_red[k].w);
-        }
-        r.w = __int_as_float(n);
-        w.part[(size_t)b * p.tiles + tile] = r;
-    }
+    int np[1] = {lab > 0 ? 1 : 0};
+    block_sum(sum, np, s_red);
+    if (t == 0) w.part[(size_t)b * p.tiles + tile] = make_float4(sum[0], sum[1], sum[2], __int_as_float(np[0]));
 }
 
 // ---------------------------------------------------------------- finalize: one workgroup, wave f sums frames f, f + 16, ...
@@ -217,13 +176,7 @@ __global__ __launch_bounds__(AL_FIN_THREADS) void anchor_loss_finalize_kernel(AL
                 const float4 r = w.part[(size_t)b * p.tiles + k];
                 c += r.x; l += r.y; d += r.z; n += __float_as_int(r.w);
             }
-#pragma unroll
-            for (int s = 32; s >= 1; s >>= 1) {
-                c += __shfl_xor(c, s, 64);
-                l += __shfl_xor(l, s, 64);
-                d += __shfl_xor(d, s, 64);
-                n += __shfl_xor(n, s, 64);
-            }
+            c = wave_sum(c); l = wave_sum(l); d = wave_sum(d); n = wave_sum(n);
             if (lane == 0) {
                 w.npos[b] = n;
                 const float norm = fmaxf((float)n, 1.0f);   // torch.clamp(pos_normalizer, min=1.0)
@@ -272,7 +225,7 @@ __global__ __launch_bounds__(AL_TILE) void anchor_loss_bwd_kernel(ALParams p, co
             const float G = gc * (cw / norm);
             for (int j = 0; j < H.c; ++j) {
                 float dx = 0.0f;
-                if (lab >= 0) al_focal(s_buf[t * H.c + j], al_onehot(p, H, lab, j), &dx);
+                if (lab >= 0) sigmoid_focal(s_buf[t * H.c + j], al_onehot(p, H, lab, j), &dx);
                 s_buf[t * H.c + j] = lab >= 0 ? G * dx : 0.0f;
             }
         }

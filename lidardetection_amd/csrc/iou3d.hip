@@ -121,7 +121,7 @@ __global__ __launch_bounds__(256) void nms_mask_kernel(const float *__restrict__
                 if (hit && j >= start && j < col_size) cand |= 1ull << j;
             }
         }
-        const int total_all = wave_sum(__popcll(cand));
+        const int total_all = wave_sum((int)__popcll(cand));
         W.word[l] = 0ull;
         // The pair list holds NMS_PAIR_CAP entries.  A tile with more candidates (most of its 4096 pairs nearly coincide:
         // a row of parked cars, a few objects with thousands of proposals each) goes through the SAME three steps in four

@@ -19,15 +19,15 @@
 // The (N, C) logits and all three gradient outputs go through LDS so that global accesses are contiguous over the tile; box and
 // part rows are read by the positive rows only (a few per cent of the points), directly.
 //
-// cls: the focal element op by op as anchor_loss.hip; the one-hot column of label c > 0 is c - 1; rows with label -1 weigh 0.
-// box: (pred - label) * code_weight with a NaN label taking the prediction, smooth-L1 beta 1/9, positives only.
-// part: BCE in its stable logits form max(x, 0) - x t + log1p(exp(-|x|)), gradient sigmoid(x) - t: equal to the reference's
-// binary_cross_entropy(sigmoid(x), t) wherever that function's -100 log clamp does not engage, continued past it (the deviation
-// roi_loss.hip documents for its cls term).
+// The element math is loss_dev.h's, the ordered sums common.h's block_sum.
+// cls: sigmoid_focal; the one-hot column of label c > 0 is c - 1; rows with label -1 weigh 0.
+// box: smooth_l1 over the 8 codes, positives only.
+// part: bce_logits, positives only (the deviation from binary_cross_entropy that roi_loss.hip documents for its cls term).
 //
 // Declared support (lidar_point_head_supported): 0 <= N <= 2^20, 1 <= B <= 64, 0 <= M <= 128, 1 <= num_class <= 8,
 // 0 <= n_mean <= 8, gt rows of exactly 8 columns [box7 | class].
 #include "common.h"
+#include "loss_dev.h"
 #include "pt_in_box_dev.h"
 #include <math.h>
 
@@ -170,46 +170,12 @@ struct PHWs {
 };
 
 static inline size_t ph_ws_layout(int tiles, PHWs *w, char *base) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return base ? base + o : nullptr; };
+    WsCarve c{base};
     char *p;
-    p = take(sizeof(float) * 3 * (size_t)tiles); if (w) w->partial = (float *)p;
-    p = take(sizeof(int) * (size_t)tiles);       if (w) w->npos = (int *)p;
-    p = take(sizeof(int));                       if (w) w->count = (int *)p;
-    return off;
-}
-
-// SigmoidFocalClassificationLoss.forward of one element before the row weight (alpha 0.25, gamma 2); *dx as autograd forms it
-__device__ __forceinline__ float ph_focal(float x, float tg, float *dx) {
-    const float p = 1.0f / (1.0f + expf(-x));
-    const float aw = tg * 0.25f + (1.0f - tg) * 0.75f;
-    const float pt = tg * (1.0f - p) + (1.0f - tg) * p;
-    const float fw = aw * (pt * pt);
-    const float e = expf(-fabsf(x));
-    const float bce = (fmaxf(x, 0.0f) - x * tg) + log1pf(e);
-    if (dx) {
-        const float dpt = aw * (2.0f * pt);
-        const float dp = dpt * (-tg) + dpt * (1.0f - tg);
-        const float dfw = dp * (1.0f - p) * p;
-        const float sgn = x > 0.0f ? 1.0f : (x < 0.0f ? -1.0f : 0.0f);
-        const float dbce = (x >= 0.0f ? 1.0f : 0.0f) - tg - (e / (1.0f + e)) * sgn;
-        *dx = dfw * bce + fw * dbce;
-    }
-    return fw * bce;
-}
-
-// one code of WeightedSmoothL1Loss (beta 1/9); *dx = d / d pred
-__device__ __forceinline__ float ph_smooth_l1(float pred, float label, float cw, float *dx) {
-    const float BETA = (float)(1.0 / 9.0), HALF_BETA = (float)(0.5 / 9.0);
-    const bool nan_t = isnan(label);
-    const float d = nan_t ? 0.0f : (pred - label) * cw;
-    const float n = fabsf(d);
-    const bool quad = n < BETA;
-    if (dx) {
-        const float sgn = d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f);
-        *dx = nan_t ? 0.0f : ((quad ? n / BETA : 1.0f) * sgn) * cw;
-    }
-    return quad ? 0.5f * (n * n) / BETA : n - HALF_BETA;
+    p = c.take(sizeof(float) * 3 * (size_t)tiles); if (w) w->partial = (float *)p;
+    p = c.take(sizeof(int) * (size_t)tiles);       if (w) w->npos = (int *)p;
+    p = c.take(sizeof(int));                       if (w) w->count = (int *)p;
+    return c.off;
 }
 
 // the rows [row0, row0 + PH_THREADS) x width floats of a row-major matrix -> s (contiguous global reads)
@@ -232,8 +198,7 @@ __global__ __launch_bounds__(PH_THREADS) void point_loss_tile_kernel(PHLossParam
                                                                      const float *__restrict__ box_labels,
                                                                      const float *__restrict__ part_labels, PHWs w) {
     __shared__ float s_buf[PH_THREADS * PH_MAX_C];
-    __shared__ float s_f[PH_THREADS / 64][3];
-    __shared__ int s_i[PH_THREADS / 64];
+    __shared__ BlockSumLds<PH_THREADS / 64, 3, 1> s_red;
     const int t = threadIdx.x, C = p.num_class;
     const long long row0 = (long long)blockIdx.x * PH_THREADS;
     const long long i = row0 + t;
@@ -244,72 +209,49 @@ __global__ __launch_bounds__(PH_THREADS) void point_loss_tile_kernel(PHLossParam
     if (i < p.n) {
         const long long lab = labels[i];
         if (cls_preds && lab >= 0)
-            for (int j = 0; j < C; ++j) cls += ph_focal(s_buf[t * C + j], lab == j + 1 ? 1.0f : 0.0f, nullptr);
+            for (int j = 0; j < C; ++j) cls += sigmoid_focal(s_buf[t * C + j], lab == j + 1 ? 1.0f : 0.0f, nullptr);
         if (lab > 0) {
             npos = 1;
             if (box_preds) {
 #pragma unroll
                 for (int q = 0; q < 8; ++q)
-                    box += ph_smooth_l1(box_preds[(size_t)i * 8 + q], box_labels[(size_t)i * 8 + q], p.code_w[q], nullptr);
+                    box += smooth_l1(box_preds[(size_t)i * 8 + q], box_labels[(size_t)i * 8 + q], p.code_w[q], nullptr);
             }
             if (part_preds) {
 #pragma unroll
-                for (int q = 0; q < 3; ++q) {
-                    const float x = part_preds[(size_t)i * 3 + q], tg = part_labels[(size_t)i * 3 + q];
-                    part += (fmaxf(x, 0.0f) - x * tg) + log1pf(expf(-fabsf(x)));
-                }
+                for (int q = 0; q < 3; ++q)
+                    part += bce_logits(part_preds[(size_t)i * 3 + q], part_labels[(size_t)i * 3 + q], nullptr);
             }
         }
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        cls += __shfl_xor(cls, d, 64);
-        box += __shfl_xor(box, d, 64);
-        part += __shfl_xor(part, d, 64);
-        npos += __shfl_xor(npos, d, 64);
-    }
-    if (lane_id() == 0) { s_f[t >> 6][0] = cls; s_f[t >> 6][1] = box; s_f[t >> 6][2] = part; s_i[t >> 6] = npos; }
-    __syncthreads();
+    float sum[3] = {cls, box, part};
+    int cnt[1] = {npos};
+    block_sum(sum, cnt, s_red);
     if (t == 0) {
-        float a = 0.0f, b = 0.0f, c = 0.0f;
-        int f = 0;
-        for (int k = 0; k < PH_THREADS / 64; ++k) { a += s_f[k][0]; b += s_f[k][1]; c += s_f[k][2]; f += s_i[k]; }
-        w.partial[(size_t)blockIdx.x * 3] = a;
-        w.partial[(size_t)blockIdx.x * 3 + 1] = b;
-        w.partial[(size_t)blockIdx.x * 3 + 2] = c;
-        w.npos[blockIdx.x] = f;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) w.partial[(size_t)blockIdx.x * 3 + q] = sum[q];
+        w.npos[blockIdx.x] = cnt[0];
     }
 }
 
 __global__ __launch_bounds__(PH_THREADS) void point_loss_finalize_kernel(PHLossParams p, PHWs w, float *__restrict__ out) {
-    __shared__ float s_f[PH_THREADS / 64][3];
-    __shared__ int s_i[PH_THREADS / 64];
+    __shared__ BlockSumLds<PH_THREADS / 64, 3, 1> s_red;
     const int t = threadIdx.x;
-    float cls = 0.0f, box = 0.0f, part = 0.0f;
-    int npos = 0;
+    float sum[3] = {0.0f, 0.0f, 0.0f};      // cls, box, part
+    int npos[1] = {0};
     for (int k = t; k < p.tiles; k += PH_THREADS) {
-        cls += w.partial[(size_t)k * 3]; box += w.partial[(size_t)k * 3 + 1]; part += w.partial[(size_t)k * 3 + 2];
-        npos += w.npos[k];
-    }
 #pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        cls += __shfl_xor(cls, d, 64);
-        box += __shfl_xor(box, d, 64);
-        part += __shfl_xor(part, d, 64);
-        npos += __shfl_xor(npos, d, 64);
+        for (int q = 0; q < 3; ++q) sum[q] += w.partial[(size_t)k * 3 + q];
+        npos[0] += w.npos[k];
     }
-    if (lane_id() == 0) { s_f[t >> 6][0] = cls; s_f[t >> 6][1] = box; s_f[t >> 6][2] = part; s_i[t >> 6] = npos; }
-    __syncthreads();
+    block_sum(sum, npos, s_red);
     if (t == 0) {
-        float a = 0.0f, b = 0.0f, c = 0.0f;
-        int f = 0;
-        for (int k = 0; k < PH_THREADS / 64; ++k) { a += s_f[k][0]; b += s_f[k][1]; c += s_f[k][2]; f += s_i[k]; }
-        const float nf = fmaxf((float)f, 1.0f);
-        out[0] = a / nf * p.w_cls;
-        out[1] = b / nf * p.w_box;
-        out[2] = c / (3.0f * nf) * p.w_part;
-        out[3] = (float)f;
-        *w.count = f;
+        const float nf = fmaxf((float)npos[0], 1.0f);
+        out[0] = sum[0] / nf * p.w_cls;
+        out[1] = sum[1] / nf * p.w_box;
+        out[2] = sum[2] / (3.0f * nf) * p.w_part;
+        out[3] = (float)npos[0];
+        *w.count = npos[0];
     }
 }
 
@@ -334,7 +276,7 @@ __global__ __launch_bounds__(PH_THREADS) void point_loss_bwd_kernel(PHLossParams
             const float sc = grad[0] * p.w_cls / nf;
             for (int j = 0; j < C; ++j) {
                 float dx = 0.0f;
-                if (lab >= 0) ph_focal(s_buf[t * C + j], lab == j + 1 ? 1.0f : 0.0f, &dx);
+                if (lab >= 0) sigmoid_focal(s_buf[t * C + j], lab == j + 1 ? 1.0f : 0.0f, &dx);
                 s_buf[t * C + j] = lab >= 0 ? sc * dx : 0.0f;      // each thread rewrites only its own row
             }
         }
@@ -348,7 +290,7 @@ __global__ __launch_bounds__(PH_THREADS) void point_loss_bwd_kernel(PHLossParams
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
                 float dx = 0.0f;
-                if (lab > 0) ph_smooth_l1(box_preds[(size_t)i * 8 + q], box_labels[(size_t)i * 8 + q], p.code_w[q], &dx);
+                if (lab > 0) smooth_l1(box_preds[(size_t)i * 8 + q], box_labels[(size_t)i * 8 + q], p.code_w[q], &dx);
                 s_buf[t * 8 + q] = lab > 0 ? sc * dx : 0.0f;
             }
         }
@@ -362,11 +304,7 @@ __global__ __launch_bounds__(PH_THREADS) void point_loss_bwd_kernel(PHLossParams
 #pragma unroll
             for (int q = 0; q < 3; ++q) {
                 float dx = 0.0f;
-                if (lab > 0) {
-                    const float x = part_preds[(size_t)i * 3 + q], tg = part_labels[(size_t)i * 3 + q];
-                    const float e = expf(-fabsf(x));
-                    dx = (x >= 0.0f ? 1.0f / (1.0f + e) : e / (1.0f + e)) - tg;
-                }
+                if (lab > 0) bce_logits(part_preds[(size_t)i * 3 + q], part_labels[(size_t)i * 3 + q], &dx);
                 s_buf[t * 3 + q] = lab > 0 ? sc * dx : 0.0f;
             }
         }

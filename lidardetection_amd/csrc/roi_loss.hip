@@ -7,19 +7,20 @@
 //   forward   ONE workgroup of 1024 threads.  The workload is a few thousand rows at most and latency-bound, so the kernel is
 //             sized for launch count: thread t takes rows t, t + 1024, ... in order, evaluates the three terms of its rows and
 //             leaves each row's UNSCALED gradient pieces (d bce / d logit, d smooth-L1 / d code, d corner / d code) in the
-//             workspace; the five sums (three losses, #fg, #valid) go through wave64 shuffles and an LDS pass over the 16 waves in
-//             wave order.  No atomics of any kind: two calls are bit-equal.  Thread 0 normalises, writes the 5-float record and
-//             keeps the two counts in the workspace.
+//             workspace; the five sums (three losses, #fg, #valid) go through common.h's block_sum (wave64 shuffles, then the 16
+//             waves in wave order).  No atomics of any kind: two calls are bit-equal.  Thread 0 normalises, writes the 5-float
+//             record and keeps the two counts in the workspace.
 //   backward  one thread per row: d_cls = g0 * w_cls / max(n_valid, 1) * piece, d_reg = g1 * w_reg / max(fg, 1) * piece_reg +
 //             g2 * w_corner / max(fg, 1) * piece_corner, the upstream triple read from device memory.
 //
-// Classification is BCE-with-logits in its stable form max(x, 0) - x t + log1p(exp(-|x|)) with gradient sigmoid(x) - t: equal to
-// the reference's binary_cross_entropy(sigmoid(x), t) wherever that function's -100 log clamp and 1e-12 denominator clamp do not
-// engage, and continued past them (the one deliberate deviation).  Non-fg rows are skipped, not multiplied by 0.  The corner
+// Classification is loss_dev.h's bce_logits: equal to the reference's binary_cross_entropy(sigmoid(x), t) wherever that function's
+// -100 log clamp and 1e-12 denominator clamp do not engage, and continued past them (the one deliberate deviation).  The regression
+// codes are loss_dev.h's smooth_l1.  Non-fg rows are skipped, not multiplied by 0.  The corner
 // difference subtracts the roi centre from the gt instead of adding it to the prediction, and the flipped gt's corners are the
 // unflipped ones with x and y offsets negated (a rotation by pi).  The corner gradient never divides by a zero distance: below the
 // smooth-L1 knee (beta 1) d L / d diff is diff itself.
 #include "common.h"
+#include "loss_dev.h"
 #include <math.h>
 
 #define RL_THREADS 1024
@@ -42,14 +43,13 @@ struct RLWs {
 };
 
 static inline size_t rl_ws_layout(long long n, RLWs *w, char *base) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return base ? base + o : nullptr; };
+    WsCarve c{base};
     char *p;
-    p = take(sizeof(float) * (size_t)n);     if (w) w->g_cls = (float *)p;
-    p = take(sizeof(float) * (size_t)n * 7); if (w) w->g_reg = (float *)p;
-    p = take(sizeof(float) * (size_t)n * 7); if (w) w->g_corner = (float *)p;
-    p = take(sizeof(int) * 2);               if (w) w->counts = (int *)p;
-    return off;
+    p = c.take(sizeof(float) * (size_t)n);     if (w) w->g_cls = (float *)p;
+    p = c.take(sizeof(float) * (size_t)n * 7); if (w) w->g_reg = (float *)p;
+    p = c.take(sizeof(float) * (size_t)n * 7); if (w) w->g_corner = (float *)p;
+    p = c.take(sizeof(int) * 2);               if (w) w->counts = (int *)p;
+    return c.off;
 }
 
 // torch.clamp_min(x, 1e-5): a NaN stays a NaN (fmaxf would drop it)
@@ -58,22 +58,13 @@ __device__ __forceinline__ float rl_clamp_min(float x) { return x < 1e-5f ? 1e-5
 // the regression term of one fg row: ResidualCoder.encode_torch(gt (canonical frame), roi with centre and heading zeroed), NaN
 // targets take the prediction, code weights, smooth-L1 beta 1/9 summed over the 7 codes; g[q] = d / d pred[q]
 __device__ __forceinline__ float rl_reg(const RLParams &p, const float *pr, const float *roi, const float *gt, float *g) {
-    const float BETA = (float)(1.0 / 9.0), HALF_BETA = (float)(0.5 / 9.0);
     const float dxa = rl_clamp_min(roi[3]), dya = rl_clamp_min(roi[4]), dza = rl_clamp_min(roi[5]);
     const float dxg = rl_clamp_min(gt[3]), dyg = rl_clamp_min(gt[4]), dzg = rl_clamp_min(gt[5]);
     const float diag = sqrtf(dxa * dxa + dya * dya);
     const float tg[7] = {gt[0] / diag, gt[1] / diag, gt[2] / dza, logf(dxg / dxa), logf(dyg / dya), logf(dzg / dza), gt[6]};
     float loss = 0.0f;
 #pragma unroll
-    for (int q = 0; q < 7; ++q) {
-        const bool nan_t = isnan(tg[q]);
-        const float d = nan_t ? 0.0f : (pr[q] - tg[q]) * p.code_w[q];
-        const float n = fabsf(d);
-        const bool quad = n < BETA;
-        loss += quad ? 0.5f * (n * n) / BETA : n - HALF_BETA;
-        const float sgn = d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f);
-        g[q] = nan_t ? 0.0f : ((quad ? n / BETA : 1.0f) * sgn) * p.code_w[q];
-    }
+    for (int q = 0; q < 7; ++q) loss += smooth_l1(pr[q], tg[q], p.code_w[q], &g[q]);
     return loss;
 }
 
@@ -143,8 +134,7 @@ __global__ __launch_bounds__(RL_THREADS) void roi_loss_fwd_kernel(RLParams p, co
                                                                   const long long *__restrict__ reg_valid,
                                                                   const float *__restrict__ labels, RLWs w,
                                                                   float *__restrict__ out) {
-    __shared__ float s_f[RL_THREADS / 64][3];
-    __shared__ int s_i[RL_THREADS / 64][2];
+    __shared__ BlockSumLds<RL_THREADS / 64, 3, 2> s_red;
     const int t = threadIdx.x;
     float cls = 0.0f, reg = 0.0f, cor = 0.0f;
     int nfg = 0, nvalid = 0;
@@ -152,10 +142,7 @@ __global__ __launch_bounds__(RL_THREADS) void roi_loss_fwd_kernel(RLParams p, co
         const float tl = labels[i];
         float gc = 0.0f;
         if (tl >= 0.0f) {
-            const float x = rcnn_cls[i];
-            const float e = expf(-fabsf(x));
-            cls += (fmaxf(x, 0.0f) - x * tl) + log1pf(e);
-            gc = (x >= 0.0f ? 1.0f / (1.0f + e) : e / (1.0f + e)) - tl;
+            cls += bce_logits(rcnn_cls[i], tl, &gc);
             ++nvalid;
         }
         w.g_cls[i] = gc;
@@ -179,30 +166,14 @@ __global__ __launch_bounds__(RL_THREADS) void roi_loss_fwd_kernel(RLParams p, co
             w.g_corner[(size_t)i * 7 + q] = gk[q];
         }
     }
-    // fixed-order reduction: lanes by shuffle, then the 16 waves in order
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        cls += __shfl_xor(cls, d, 64);
-        reg += __shfl_xor(reg, d, 64);
-        cor += __shfl_xor(cor, d, 64);
-        nfg += __shfl_xor(nfg, d, 64);
-        nvalid += __shfl_xor(nvalid, d, 64);
-    }
-    if (lane_id() == 0) {
-        s_f[t >> 6][0] = cls; s_f[t >> 6][1] = reg; s_f[t >> 6][2] = cor;
-        s_i[t >> 6][0] = nfg; s_i[t >> 6][1] = nvalid;
-    }
-    __syncthreads();
+    float sum[3] = {cls, reg, cor};
+    int cnt[2] = {nfg, nvalid};
+    block_sum(sum, cnt, s_red);      // fixed order: lanes by shuffle, then the 16 waves in order
     if (t == 0) {
-        float a = 0.0f, b = 0.0f, c = 0.0f;
-        int f = 0, v = 0;
-        for (int k = 0; k < RL_THREADS / 64; ++k) {
-            a += s_f[k][0]; b += s_f[k][1]; c += s_f[k][2];
-            f += s_i[k][0]; v += s_i[k][1];
-        }
-        out[0] = a / fmaxf((float)v, 1.0f) * p.w_cls;
-        out[1] = b / fmaxf((float)f, 1.0f) * p.w_reg;
-        out[2] = c / fmaxf((float)f, 1.0f) * p.w_corner;      // 0 without fg rows or with the option off
+        const int f = cnt[0], v = cnt[1];
+        out[0] = sum[0] / fmaxf((float)v, 1.0f) * p.w_cls;
+        out[1] = sum[1] / fmaxf((float)f, 1.0f) * p.w_reg;
+        out[2] = sum[2] / fmaxf((float)f, 1.0f) * p.w_corner;      // 0 without fg rows or with the option off
         out[3] = (float)f;
         out[4] = (float)v;
         w.counts[0] = f;

@@ -11,13 +11,14 @@ import types
 import numpy as np
 import torch
 
-from .anchor_head_template import AnchorHeadTemplate, _get
+from ...._lib import cfg_get
+from .anchor_head_template import AnchorHeadTemplate
 
 
 class AnchorHeadMulti(AnchorHeadTemplate):
     def __init__(self, model_cfg, input_channels, num_class, class_names, grid_size, point_cloud_range,
                  predict_boxes_when_training=True):
-        self.separate_multihead = bool(_get(model_cfg, 'SEPARATE_MULTIHEAD', False))
+        self.separate_multihead = bool(cfg_get(model_cfg, 'SEPARATE_MULTIHEAD', False))
         names = [n for cfg in model_cfg.RPN_HEAD_CFGS for n in cfg['HEAD_CLS_NAME']]
         self._head_nc = [len(cfg['HEAD_CLS_NAME']) if self.separate_multihead else num_class for cfg in model_cfg.RPN_HEAD_CFGS]
         super().__init__(model_cfg=model_cfg, num_class=num_class, class_names=class_names, grid_size=grid_size,

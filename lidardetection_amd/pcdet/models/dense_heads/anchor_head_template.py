@@ -19,13 +19,10 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .... import anchor_loss
+from ...._lib import cfg_get
 from .target_assigner.anchor_generator import AnchorGenerator
 from .target_assigner.atss_target_assigner import ATSSTargetAssigner
 from .target_assigner.axis_aligned_target_assigner import AxisAlignedTargetAssigner
-
-
-def _get(cfg, key, default=None):
-    return cfg.get(key, default) if hasattr(cfg, "get") else getattr(cfg, key, default)
 
 
 class AnchorHeadTemplate(nn.Module):
@@ -33,12 +30,12 @@ class AnchorHeadTemplate(nn.Module):
         super().__init__()
         self.model_cfg, self.num_class, self.class_names = model_cfg, num_class, class_names
         self.predict_boxes_when_training = predict_boxes_when_training
-        self.use_multihead = _get(model_cfg, 'USE_MULTIHEAD', False)
+        self.use_multihead = cfg_get(model_cfg, 'USE_MULTIHEAD', False)
 
         assigner_cfg = model_cfg.TARGET_ASSIGNER_CONFIG
         if assigner_cfg.BOX_CODER != 'ResidualCoder':
             raise NotImplementedError(f"AnchorHeadTemplate: BOX_CODER {assigner_cfg.BOX_CODER} (ResidualCoder only)")
-        coder_cfg = _get(assigner_cfg, 'BOX_CODER_CONFIG', {}) or {}
+        coder_cfg = cfg_get(assigner_cfg, 'BOX_CODER_CONFIG', {}) or {}
         by_sincos = bool(coder_cfg.get('encode_angle_by_sincos', False))
         self.box_coder = types.SimpleNamespace(code_size=int(coder_cfg.get('code_size', 7)) + int(by_sincos),
                                                encode_angle_by_sincos=by_sincos)

@@ -14,10 +14,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .... import point_head
-
-
-def _get(cfg, key, default=None):
-    return cfg.get(key, default) if hasattr(cfg, "get") else getattr(cfg, key, default)
+from ...._lib import cfg_get
 
 
 def _in_boxes(pts, boxes):
@@ -51,7 +48,7 @@ class PointHeadTemplate(nn.Module):
     def build_losses(self, losses_cfg):
         """the reference registers a focal-loss module and picks reg_loss_func; here the fused kernels carry both (alpha 0.25,
         gamma 2; WeightedSmoothL1Loss beta 1/9) and the torch formulation below restates them, so only the choice is kept"""
-        self.reg_loss_type = _get(losses_cfg, 'LOSS_REG', None)
+        self.reg_loss_type = cfg_get(losses_cfg, 'LOSS_REG', None)
 
     def fused_spec(self):
         """-> the fused path's PointHeadSpec, or None for a config it refuses"""

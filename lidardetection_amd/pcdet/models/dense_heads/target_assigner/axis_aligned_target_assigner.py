@@ -18,10 +18,7 @@ import numpy as np
 import torch
 
 from ..... import anchor_assign
-
-
-def _get(cfg, key, default):
-    return cfg.get(key, default) if hasattr(cfg, "get") else getattr(cfg, key, default)
+from ....._lib import cfg_get
 
 
 class AxisAlignedTargetAssigner(object):
@@ -42,12 +39,12 @@ class AxisAlignedTargetAssigner(object):
         self.box_coder, self.match_height = box_coder, match_height
         self.class_names = np.array(class_names)
         self.anchor_class_names = [g['class_name'] for g in gen_cfgs]
-        self.pos_fraction, self.sample_size = None, _get(tgt_cfg, 'SAMPLE_SIZE', None)
+        self.pos_fraction, self.sample_size = None, cfg_get(tgt_cfg, 'SAMPLE_SIZE', None)
         self.norm_by_num_examples = tgt_cfg.NORM_BY_NUM_EXAMPLES
         self.matched_thresholds = {g['class_name']: g['matched_threshold'] for g in gen_cfgs}
         self.unmatched_thresholds = {g['class_name']: g['unmatched_threshold'] for g in gen_cfgs}
-        self.use_multihead = _get(model_cfg, 'USE_MULTIHEAD', False)
-        self.seperate_multihead = _get(model_cfg, 'SEPERATE_MULTIHEAD', False)   # the reference's key, misspelling included
+        self.use_multihead = cfg_get(model_cfg, 'USE_MULTIHEAD', False)
+        self.seperate_multihead = cfg_get(model_cfg, 'SEPERATE_MULTIHEAD', False)   # the reference's key, misspelling included
         if self.seperate_multihead:
             self.gt_remapping = {name: pos + 1 for head in model_cfg.RPN_HEAD_CFGS
                                  for pos, name in enumerate(head['HEAD_CLS_NAME'])}

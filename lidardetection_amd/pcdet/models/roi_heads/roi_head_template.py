@@ -12,13 +12,10 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .... import roi_loss
+from ...._lib import cfg_get
 from .target_assigner.proposal_target_layer import ProposalTargetLayer
 
 _CORNER_SIGNS = [(1, 1, -1), (1, -1, -1), (-1, -1, -1), (-1, 1, -1), (1, 1, 1), (1, -1, 1), (-1, -1, 1), (-1, 1, 1)]
-
-
-def _get(cfg, key, default=None):
-    return cfg.get(key, default) if hasattr(cfg, "get") else getattr(cfg, key, default)
 
 
 def _smooth_l1(n, beta):
@@ -56,7 +53,7 @@ class RoIHeadTemplate(nn.Module):
     def build_losses(self, losses_cfg=None):
         """-> the fused path's RoILossSpec, or None for a config it refuses (the torch formulation then runs).  The reference's
         build_losses registers a WeightedSmoothL1Loss module; here the code weights live in the spec / are read from the config."""
-        cfg = self.model_cfg if losses_cfg is None else dict(LOSS_CONFIG=losses_cfg, TARGET_CONFIG=_get(self.model_cfg, "TARGET_CONFIG"))
+        cfg = self.model_cfg if losses_cfg is None else dict(LOSS_CONFIG=losses_cfg, TARGET_CONFIG=cfg_get(self.model_cfg, "TARGET_CONFIG"))
         try:
             spec = roi_loss.spec_from_cfg(cfg)
         except NotImplementedError:
@@ -77,20 +74,20 @@ class RoIHeadTemplate(nn.Module):
         return cached[2]
 
     def _code_size(self):
-        tcfg = _get(self.model_cfg, "TARGET_CONFIG")
-        ccfg = _get(tcfg, "BOX_CODER_CONFIG") or {}
-        return int(_get(ccfg, "code_size", 7)) + (1 if _get(ccfg, "encode_angle_by_sincos", False) else 0), bool(_get(ccfg, "encode_angle_by_sincos", False))
+        tcfg = cfg_get(self.model_cfg, "TARGET_CONFIG")
+        ccfg = cfg_get(tcfg, "BOX_CODER_CONFIG") or {}
+        return int(cfg_get(ccfg, "code_size", 7)) + (1 if cfg_get(ccfg, "encode_angle_by_sincos", False) else 0), bool(cfg_get(ccfg, "encode_angle_by_sincos", False))
 
     def _torch_reg_loss(self, d):
         """get_box_reg_layer_loss (:133-200) in torch -> (reg, corner or None, fg_sum tensor); nothing is written in place and
         nothing is read back"""
-        loss_cfgs = _get(self.model_cfg, "LOSS_CONFIG")
-        tcfg = _get(self.model_cfg, "TARGET_CONFIG")
-        if _get(loss_cfgs, "REG_LOSS") != "smooth-l1" or _get(tcfg, "BOX_CODER", "ResidualCoder") != "ResidualCoder":
+        loss_cfgs = cfg_get(self.model_cfg, "LOSS_CONFIG")
+        tcfg = cfg_get(self.model_cfg, "TARGET_CONFIG")
+        if cfg_get(loss_cfgs, "REG_LOSS") != "smooth-l1" or cfg_get(tcfg, "BOX_CODER", "ResidualCoder") != "ResidualCoder":
             raise NotImplementedError
         code_size, sincos = self._code_size()
         box = code_size - 1 if sincos else code_size                   # width of a box: the coder reads that many columns
-        lw = _get(loss_cfgs, "LOSS_WEIGHTS")
+        lw = cfg_get(loss_cfgs, "LOSS_WEIGHTS")
         rcnn_reg = d["rcnn_reg"]
         n = rcnn_reg.shape[0]
         fg = d["reg_valid_mask"].reshape(n) > 0
@@ -104,14 +101,14 @@ class RoIHeadTemplate(nn.Module):
                 torch.log(dg[:, 2] / da[:, 2])]
         cols += [torch.cos(gt[:, 6]) - 1.0, torch.sin(gt[:, 6])] if sincos else [gt[:, 6]]        # the anchor's heading is 0
         cols += [gt[:, k] - roi[:, k] for k in range(7, box)]
-        if _get(tcfg, "REG_TRACKING_INFO", False):
+        if cfg_get(tcfg, "REG_TRACKING_INFO", False):
             cols += list(gt[:, box + 1:].unbind(dim=1))
         tg = torch.stack(cols, dim=1)
         tg = torch.where(torch.isnan(tg), rcnn_reg, tg)
         diff = (rcnn_reg - tg) * rcnn_reg.new_tensor([float(w) for w in lw["code_weights"]])
         per_row = _smooth_l1(diff.abs(), 1.0 / 9.0).sum(dim=1)
         reg = torch.where(fg, per_row, torch.zeros_like(per_row)).sum() / denom * lw["rcnn_reg_weight"]
-        if not _get(loss_cfgs, "CORNER_LOSS_REGULARIZATION", False):
+        if not cfg_get(loss_cfgs, "CORNER_LOSS_REGULARIZATION", False):
             return reg, None, fg_sum
         pr = rcnn_reg[:, :code_size]
         diag_r = torch.sqrt(roi[:, 3] ** 2 + roi[:, 4] ** 2)
@@ -133,11 +130,11 @@ class RoIHeadTemplate(nn.Module):
 
     def _torch_cls_loss(self, d):
         """get_box_cls_layer_loss (:202-220) in torch -> cls"""
-        loss_cfgs = _get(self.model_cfg, "LOSS_CONFIG")
+        loss_cfgs = cfg_get(self.model_cfg, "LOSS_CONFIG")
         rcnn_cls = d["rcnn_cls"]
         labels = d["rcnn_cls_labels"].reshape(-1)
         valid = labels >= 0
-        kind = _get(loss_cfgs, "CLS_LOSS")
+        kind = cfg_get(loss_cfgs, "CLS_LOSS")
         if kind == "BinaryCrossEntropy":
             # the stable logit form, as the fused path evaluates it (equal to binary_cross_entropy(sigmoid(x), t) for |x| < 27.6)
             each = F.binary_cross_entropy_with_logits(rcnn_cls.reshape(-1), labels.to(rcnn_cls.dtype), reduction="none")
@@ -146,7 +143,7 @@ class RoIHeadTemplate(nn.Module):
         else:
             raise NotImplementedError
         each = torch.where(valid, each, torch.zeros_like(each))
-        return each.sum() / torch.clamp(valid.sum().to(each.dtype), min=1.0) * _get(loss_cfgs, "LOSS_WEIGHTS")["rcnn_cls_weight"]
+        return each.sum() / torch.clamp(valid.sum().to(each.dtype), min=1.0) * cfg_get(loss_cfgs, "LOSS_WEIGHTS")["rcnn_cls_weight"]
 
     def _terms(self, d):
         """-> (cls, reg, corner or None, record): record = device [cls, reg, corner, fg_sum, n_valid]"""

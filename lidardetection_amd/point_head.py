@@ -11,6 +11,7 @@ from dataclasses import dataclass
 import torch
 
 from . import _lib
+from ._lib import cfg_get
 
 # include/lidar_hip.h: LIDAR_POINT_HEAD_*
 MAX_POINTS, MAX_BATCH, MAX_GT, MAX_CLASS, MAX_MEAN = 1 << 20, 64, 128, 8, 8
@@ -29,49 +30,45 @@ class PointHeadSpec:
     code_weights: tuple         # 8 entries (ones where the config has no box term)
 
 
-def _get(cfg, key, default=None):
-    return cfg.get(key, default) if hasattr(cfg, "get") else getattr(cfg, key, default)
-
-
 def spec_from_cfg(model_cfg, num_class):
     """model_cfg: a POINT_HEAD config (TARGET_CONFIG.GT_EXTRA_WIDTH / BOX_CODER / BOX_CODER_CONFIG, LOSS_CONFIG.LOSS_REG /
     LOSS_WEIGHTS).  NotImplementedError for what the kernels do not cover."""
-    tcfg, loss_cfg = _get(model_cfg, "TARGET_CONFIG"), _get(model_cfg, "LOSS_CONFIG")
+    tcfg, loss_cfg = cfg_get(model_cfg, "TARGET_CONFIG"), cfg_get(model_cfg, "LOSS_CONFIG")
     if tcfg is None or loss_cfg is None:
         raise ValueError("point_head: the config needs TARGET_CONFIG and LOSS_CONFIG")
     num_class = int(num_class)
     if not 1 <= num_class <= MAX_CLASS:
         raise NotImplementedError(f"point_head: num_class {num_class} is not supported (1..{MAX_CLASS})")
-    extra = tuple(float(x) for x in _get(tcfg, "GT_EXTRA_WIDTH"))
+    extra = tuple(float(x) for x in cfg_get(tcfg, "GT_EXTRA_WIDTH"))
     if len(extra) != 3:
         raise ValueError(f"point_head: GT_EXTRA_WIDTH needs 3 entries, got {extra}")
-    lw = _get(loss_cfg, "LOSS_WEIGHTS")
-    coder = _get(tcfg, "BOX_CODER", None)
+    lw = cfg_get(loss_cfg, "LOSS_WEIGHTS")
+    coder = cfg_get(tcfg, "BOX_CODER", None)
     mean, code_weights = (), (1.0,) * CODE_SIZE
     if coder is not None:
         if coder != "PointResidualCoder":
             raise NotImplementedError(f"point_head: box coder {coder!r} is not supported (PointResidualCoder)")
-        ccfg = _get(tcfg, "BOX_CODER_CONFIG") or {}
-        if int(_get(ccfg, "code_size", CODE_SIZE)) != CODE_SIZE:
-            raise NotImplementedError(f"point_head: code_size {_get(ccfg, 'code_size')} is not supported ({CODE_SIZE})")
-        if _get(ccfg, "use_mean_size", True):
-            mean = tuple(tuple(float(v) for v in row) for row in _get(ccfg, "mean_size"))
+        ccfg = cfg_get(tcfg, "BOX_CODER_CONFIG") or {}
+        if int(cfg_get(ccfg, "code_size", CODE_SIZE)) != CODE_SIZE:
+            raise NotImplementedError(f"point_head: code_size {cfg_get(ccfg, 'code_size')} is not supported ({CODE_SIZE})")
+        if cfg_get(ccfg, "use_mean_size", True):
+            mean = tuple(tuple(float(v) for v in row) for row in cfg_get(ccfg, "mean_size"))
             if not 1 <= len(mean) <= MAX_MEAN or any(len(r) != 3 or min(r) <= 0 for r in mean):
                 raise NotImplementedError(f"point_head: mean_size must be 1..{MAX_MEAN} rows of 3 positive sizes, got {mean}")
-        reg = _get(loss_cfg, "LOSS_REG", None)
+        reg = cfg_get(loss_cfg, "LOSS_REG", None)
         if reg != "WeightedSmoothL1Loss":
             # point_head_template.py:23-33 maps every other value to F.smooth_l1_loss / F.l1_loss, which get_box_layer_loss then
             # calls with a `weights=` keyword those functions do not have: the reference raises a TypeError there
             raise NotImplementedError(f"point_head: LOSS_REG {reg!r} with a box term is not supported: the reference hands "
                                       "F.smooth_l1_loss / F.l1_loss a `weights=` argument they do not take and raises; use "
                                       "WeightedSmoothL1Loss")
-        cw = _get(lw, "code_weights", None)
+        cw = cfg_get(lw, "code_weights", None)
         if cw is None or len(cw) != CODE_SIZE:
             raise NotImplementedError(f"point_head: the box term needs {CODE_SIZE} code_weights, got {cw}")
         code_weights = tuple(float(x) for x in cw)
     return PointHeadSpec(num_class=num_class, extra_width=extra, box_coder=coder is not None, mean_size=mean,
-                         cls_weight=float(_get(lw, "point_cls_weight")), box_weight=float(_get(lw, "point_box_weight", 0.0)),
-                         part_weight=float(_get(lw, "point_part_weight", 0.0)), code_weights=code_weights)
+                         cls_weight=float(cfg_get(lw, "point_cls_weight")), box_weight=float(cfg_get(lw, "point_box_weight", 0.0)),
+                         part_weight=float(cfg_get(lw, "point_part_weight", 0.0)), code_weights=code_weights)
 
 
 def supported(n, batch, m, gt_dim=8, num_class=1, n_mean=0):
@@ -84,29 +81,25 @@ def workspace_bytes(n):
     return int(_lib.lib().lidar_point_loss_ws_bytes(int(n)))
 
 
-def _fail(what, msg):
-    raise _lib.LidarHipError(f"{what}: {msg}")
-
-
 def assign_point_targets(points, gt_boxes, spec, ret_box_labels=False, ret_part_labels=False):
     """points (N, 4) [bs_idx, x, y, z] and gt_boxes (B, M, 8) [box7 | class] fp32 on the device -> the reference's targets_dict
     {point_cls_labels (N) int64, point_box_labels (N, 8) or None, point_part_labels (N, 3) or None} plus point_box_idx (N) int32,
     the owner gt row of each point (-1: none).  One launch, no host synchronisation; the inputs are never written."""
     what = "assign_point_targets"
     if points.dim() != 2 or points.shape[1] != 4:
-        _fail(what, f"points must be (N, 4), got {tuple(points.shape)}")
+        _lib.fail(what, f"points must be (N, 4), got {tuple(points.shape)}")
     if gt_boxes.dim() != 3:
-        _fail(what, f"gt_boxes must be (B, M, 8), got {tuple(gt_boxes.shape)}")
+        _lib.fail(what, f"gt_boxes must be (B, M, 8), got {tuple(gt_boxes.shape)}")
     if ret_box_labels and not spec.box_coder:
-        _fail(what, "box labels need a config with a PointResidualCoder")
+        _lib.fail(what, "box labels need a config with a PointResidualCoder")
     N, (B, M, D) = int(points.shape[0]), (int(s) for s in gt_boxes.shape)
     n_mean = len(spec.mean_size)
     if not supported(N, B, M, D, spec.num_class, n_mean):
-        _fail(what, f"supported: N <= {MAX_POINTS}, 1 <= B <= {MAX_BATCH}, M <= {MAX_GT}, gt rows of 8 columns, num_class <= "
-                    f"{MAX_CLASS}; got points {tuple(points.shape)}, gt_boxes {tuple(gt_boxes.shape)}, num_class {spec.num_class}")
+        _lib.fail(what, f"supported: N <= {MAX_POINTS}, 1 <= B <= {MAX_BATCH}, M <= {MAX_GT}, gt rows of 8 columns, num_class <= "
+                  f"{MAX_CLASS}; got points {tuple(points.shape)}, gt_boxes {tuple(gt_boxes.shape)}, num_class {spec.num_class}")
     for name, t in (("points", points), ("gt_boxes", gt_boxes)):
         if t.dtype != torch.float32:
-            _fail(what, f"{name} must be float32, got {t.dtype}")
+            _lib.fail(what, f"{name} must be float32, got {t.dtype}")
     points, gt_boxes = points.detach().contiguous(), gt_boxes.detach().contiguous()
     _lib.require_cuda(points, gt_boxes)
     dev = points.device
@@ -163,9 +156,9 @@ def point_head_loss(cls_preds, box_preds, part_preds, targets, spec):
     labels = targets["point_cls_labels"].reshape(-1)
     n = int(labels.shape[0])
     if labels.dtype != torch.int64:
-        _fail(what, f"point_cls_labels must be int64, got {labels.dtype}")
+        _lib.fail(what, f"point_cls_labels must be int64, got {labels.dtype}")
     if not supported(n, 1, 0, 8, spec.num_class, 0):
-        _fail(what, f"supported: N <= {MAX_POINTS}, num_class <= {MAX_CLASS}; got N {n}, num_class {spec.num_class}")
+        _lib.fail(what, f"supported: N <= {MAX_POINTS}, num_class <= {MAX_CLASS}; got N {n}, num_class {spec.num_class}")
     box_labels = targets.get("point_box_labels") if box_preds is not None else None
     part_labels = targets.get("point_part_labels") if part_preds is not None else None
     if cls_preds is not None:
@@ -175,11 +168,11 @@ def point_head_loss(cls_preds, box_preds, part_preds, targets, spec):
         if t is None:
             continue
         if lab is None:
-            _fail(what, f"{name} without its labels in the targets")
+            _lib.fail(what, f"{name} without its labels in the targets")
         if t.dim() != 2 or tuple(t.shape) != (n, width) or t.dtype != torch.float32:
-            _fail(what, f"{name} must be float32 ({n}, {width}), got {t.dtype} {tuple(t.shape)}")
+            _lib.fail(what, f"{name} must be float32 ({n}, {width}), got {t.dtype} {tuple(t.shape)}")
         if lab is not labels and (tuple(lab.shape) != (n, width) or lab.dtype != torch.float32):
-            _fail(what, f"the labels of {name} must be float32 ({n}, {width}), got {lab.dtype} {tuple(lab.shape)}")
+            _lib.fail(what, f"the labels of {name} must be float32 ({n}, {width}), got {lab.dtype} {tuple(lab.shape)}")
     cont = lambda t: None if t is None else t.contiguous()      # noqa: E731
     det = lambda t: None if t is None else t.detach().contiguous()      # noqa: E731
     labels, box_labels, part_labels = det(labels), det(box_labels), det(part_labels)

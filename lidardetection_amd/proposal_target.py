@@ -26,10 +26,6 @@ def hard_quota_table(hard_bg_ratio, roi_per_image):
     return [int(n * hard_bg_ratio) for n in range(int(roi_per_image) + 1)]
 
 
-def _fail(msg):
-    raise _lib.LidarHipError("proposal_target: " + msg)
-
-
 def assign(rois, roi_scores, roi_labels, gt_boxes, fg_keys, draws, roi_per_image, fg_ratio, reg_fg_thresh, cls_fg_thresh,
            cls_bg_thresh, cls_bg_thresh_lo, hard_bg_ratio, by_class=False, cls_score_type="roi_iou", gt_boxes_enlarged=None):
     """rois (B, R, D) f32, roi_scores (B, R) f32, roi_labels (B, R) i64, gt_boxes (B, M, D + 1) f32 [box | class id],
@@ -38,27 +34,27 @@ def assign(rois, roi_scores, roi_labels, gt_boxes, fg_keys, draws, roi_per_image
     roi_labels, reg_valid_mask (B, P) i64, sampled_inds (B, P) i32, frame_status (B,) i32, max_overlaps (B, R) f32,
     gt_assignment (B, R) i32."""
     if cls_score_type not in CLS_SCORE_TYPES:
-        _fail(f"CLS_SCORE_TYPE must be one of {sorted(CLS_SCORE_TYPES)}, got {cls_score_type!r}")
+        _lib.fail("proposal_target", f"CLS_SCORE_TYPE must be one of {sorted(CLS_SCORE_TYPES)}, got {cls_score_type!r}")
     if rois.dim() != 3 or rois.dtype != torch.float32:
-        _fail(f"rois must be float32 (B, R, D), got {rois.dtype} {tuple(rois.shape)}")
+        _lib.fail("proposal_target", f"rois must be float32 (B, R, D), got {rois.dtype} {tuple(rois.shape)}")
     B, R, D = (int(x) for x in rois.shape)
     P = int(roi_per_image)
     if gt_boxes.dim() != 3 or gt_boxes.dtype != torch.float32 or gt_boxes.shape[0] != B or gt_boxes.shape[2] != D + 1:
-        _fail(f"gt_boxes must be float32 ({B}, M, {D + 1}), got {gt_boxes.dtype} {tuple(gt_boxes.shape)}")
+        _lib.fail("proposal_target", f"gt_boxes must be float32 ({B}, M, {D + 1}), got {gt_boxes.dtype} {tuple(gt_boxes.shape)}")
     M = int(gt_boxes.shape[1])
     if gt_boxes_enlarged is not None and (gt_boxes_enlarged.shape != gt_boxes.shape or gt_boxes_enlarged.dtype != torch.float32):
-        _fail(f"gt_boxes_enlarged must match gt_boxes {tuple(gt_boxes.shape)} float32, got {gt_boxes_enlarged.dtype} "
-              f"{tuple(gt_boxes_enlarged.shape)}")
+        _lib.fail("proposal_target", f"gt_boxes_enlarged must match gt_boxes {tuple(gt_boxes.shape)} float32, got {gt_boxes_enlarged.dtype} "
+                  f"{tuple(gt_boxes_enlarged.shape)}")
     for name, t, shape, dtype in [("roi_scores", roi_scores, (B, R), torch.float32), ("roi_labels", roi_labels, (B, R), torch.int64),
                                   ("fg_keys", fg_keys, (B, R), torch.float32), ("draws", draws, (B, P), torch.float32)]:
         if tuple(t.shape) != shape or t.dtype != dtype:
-            _fail(f"{name} must be {dtype} {shape}, got {t.dtype} {tuple(t.shape)}")
+            _lib.fail("proposal_target", f"{name} must be {dtype} {shape}, got {t.dtype} {tuple(t.shape)}")
     if not (1 <= R <= MAX_ROIS and 1 <= M <= MAX_GT and 1 <= P <= MAX_SAMPLES and 7 <= D <= MAX_DIM):
-        _fail(f"supported: 1 <= R <= {MAX_ROIS}, 1 <= M <= {MAX_GT}, 1 <= ROI_PER_IMAGE <= {MAX_SAMPLES}, 7 <= D <= {MAX_DIM}; "
-              f"got R {R}, M {M}, ROI_PER_IMAGE {P}, D {D}")
+        _lib.fail("proposal_target", f"supported: 1 <= R <= {MAX_ROIS}, 1 <= M <= {MAX_GT}, 1 <= ROI_PER_IMAGE <= {MAX_SAMPLES}, "
+                  f"7 <= D <= {MAX_DIM}; got R {R}, M {M}, ROI_PER_IMAGE {P}, D {D}")
     fg_n = fg_rois_per_image(fg_ratio, P)
     if not 0 <= fg_n <= P or not 0.0 <= hard_bg_ratio <= 1.0:
-        _fail(f"FG_RATIO {fg_ratio} / HARD_BG_RATIO {hard_bg_ratio} must lie in [0, 1]")
+        _lib.fail("proposal_target", f"FG_RATIO {fg_ratio} / HARD_BG_RATIO {hard_bg_ratio} must lie in [0, 1]")
     _lib.require_cuda(rois, roi_scores, roi_labels, gt_boxes, gt_boxes_enlarged, fg_keys, draws, allow=(torch.int64,))
     dev = rois.device
     f32 = dict(dtype=torch.float32, device=dev)

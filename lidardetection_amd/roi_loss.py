@@ -10,6 +10,7 @@ from dataclasses import dataclass
 import torch
 
 from . import _lib
+from ._lib import cfg_get
 
 MAX_SAMPLES, MAX_ROWS = 512, 65536      # include/lidar_hip.h: LIDAR_ROI_LOSS_*
 
@@ -23,33 +24,29 @@ class RoILossSpec:
     corner: bool
 
 
-def _get(cfg, key, default=None):
-    return cfg.get(key, default) if hasattr(cfg, "get") else getattr(cfg, key, default)
-
-
 def spec_from_cfg(model_cfg):
     """model_cfg: a ROI_HEAD config (LOSS_CONFIG; TARGET_CONFIG.BOX_CODER / BOX_CODER_CONFIG / REG_TRACKING_INFO when it has a
     TARGET_CONFIG).  NotImplementedError for what the kernel does not cover: the caller keeps a torch formulation for those."""
-    loss_cfg = _get(model_cfg, "LOSS_CONFIG")
+    loss_cfg = cfg_get(model_cfg, "LOSS_CONFIG")
     if loss_cfg is None:
         raise ValueError("roi_head_loss: the config has no LOSS_CONFIG")
-    cls_loss, reg_loss = _get(loss_cfg, "CLS_LOSS"), _get(loss_cfg, "REG_LOSS")
+    cls_loss, reg_loss = cfg_get(loss_cfg, "CLS_LOSS"), cfg_get(loss_cfg, "REG_LOSS")
     if cls_loss != "BinaryCrossEntropy":
         raise NotImplementedError(f"roi_head_loss: CLS_LOSS {cls_loss!r} is not supported (BinaryCrossEntropy)")
     if reg_loss != "smooth-l1":
         raise NotImplementedError(f"roi_head_loss: REG_LOSS {reg_loss!r} is not supported (smooth-l1)")
-    tcfg = _get(model_cfg, "TARGET_CONFIG") or {}
-    coder = _get(tcfg, "BOX_CODER", "ResidualCoder")
-    coder_cfg = _get(tcfg, "BOX_CODER_CONFIG") or {}
-    if coder != "ResidualCoder" or _get(coder_cfg, "encode_angle_by_sincos", False) or int(_get(coder_cfg, "code_size", 7)) != 7:
+    tcfg = cfg_get(model_cfg, "TARGET_CONFIG") or {}
+    coder = cfg_get(tcfg, "BOX_CODER", "ResidualCoder")
+    coder_cfg = cfg_get(tcfg, "BOX_CODER_CONFIG") or {}
+    if coder != "ResidualCoder" or cfg_get(coder_cfg, "encode_angle_by_sincos", False) or int(cfg_get(coder_cfg, "code_size", 7)) != 7:
         raise NotImplementedError(f"roi_head_loss: box coder {coder!r} {dict(coder_cfg)} is not supported (plain ResidualCoder, code size 7)")
-    if _get(tcfg, "REG_TRACKING_INFO", False):
+    if cfg_get(tcfg, "REG_TRACKING_INFO", False):
         raise NotImplementedError("roi_head_loss: REG_TRACKING_INFO is not supported")
-    lw = _get(loss_cfg, "LOSS_WEIGHTS")
+    lw = cfg_get(loss_cfg, "LOSS_WEIGHTS")
     code_weights = tuple(float(x) for x in lw["code_weights"])
     if len(code_weights) != 7:
         raise NotImplementedError(f"roi_head_loss: {len(code_weights)} code weights for a code size of 7")
-    corner = bool(_get(loss_cfg, "CORNER_LOSS_REGULARIZATION", False))
+    corner = bool(cfg_get(loss_cfg, "CORNER_LOSS_REGULARIZATION", False))
     return RoILossSpec(cls_weight=float(lw["rcnn_cls_weight"]), reg_weight=float(lw["rcnn_reg_weight"]),
                        corner_weight=float(lw["rcnn_corner_weight"]) if corner else 0.0, code_weights=code_weights, corner=corner)
 
@@ -96,10 +93,6 @@ class _RoILoss(torch.autograd.Function):
         return (None,) * 8 + (d_cls, d_reg)
 
 
-def _fail(msg):
-    raise _lib.LidarHipError("roi_head_loss: " + msg)
-
-
 def roi_head_loss(rcnn_cls, rcnn_reg, targets_dict, spec):
     """-> (cls, reg, corner, stats): the three weighted terms as 0-dim fp32 device tensors (reg WITHOUT the corner term; the
     reference's rcnn_loss_reg is reg + corner) and the device record stats = [cls, reg, corner, fg_sum, n_valid].
@@ -110,27 +103,27 @@ def roi_head_loss(rcnn_cls, rcnn_reg, targets_dict, spec):
     rois, gt, gt_src = targets_dict["rois"], targets_dict["gt_of_rois"], targets_dict["gt_of_rois_src"]
     mask, labels = targets_dict["reg_valid_mask"], targets_dict["rcnn_cls_labels"]
     if rois.dim() != 3:
-        _fail(f"rois must be (B, P, 7), got {tuple(rois.shape)}")
+        _lib.fail("roi_head_loss", f"rois must be (B, P, 7), got {tuple(rois.shape)}")
     B, P = int(rois.shape[0]), int(rois.shape[1])
     n = B * P
     if rcnn_cls.dim() != 2 or rcnn_reg.dim() != 2 or rcnn_cls.shape[0] != n or rcnn_reg.shape[0] != n:
-        _fail(f"rcnn_cls / rcnn_reg must be ({n}, 1) / ({n}, 7), got {tuple(rcnn_cls.shape)} / {tuple(rcnn_reg.shape)}")
+        _lib.fail("roi_head_loss", f"rcnn_cls / rcnn_reg must be ({n}, 1) / ({n}, 7), got {tuple(rcnn_cls.shape)} / {tuple(rcnn_reg.shape)}")
     if gt.dim() != 3 or tuple(gt.shape[:2]) != (B, P) or gt_src.shape != gt.shape:
-        _fail(f"gt_of_rois / gt_of_rois_src must be ({B}, {P}, 8), got {tuple(gt.shape)} / {tuple(gt_src.shape)}")
+        _lib.fail("roi_head_loss", f"gt_of_rois / gt_of_rois_src must be ({B}, {P}, 8), got {tuple(gt.shape)} / {tuple(gt_src.shape)}")
     if not supported(B, P, rois.shape[2], gt.shape[2], rcnn_reg.shape[1], rcnn_cls.shape[1]):
-        _fail(f"supported: rois (B, P, 7), gts (B, P, 8), rcnn_reg (n, 7), rcnn_cls (n, 1), 1 <= P <= {MAX_SAMPLES}, B * P <= "
-              f"{MAX_ROWS}; got rois {tuple(rois.shape)}, gts {tuple(gt.shape)}, rcnn_reg {tuple(rcnn_reg.shape)}, rcnn_cls "
-              f"{tuple(rcnn_cls.shape)}")
+        _lib.fail("roi_head_loss", f"supported: rois (B, P, 7), gts (B, P, 8), rcnn_reg (n, 7), rcnn_cls (n, 1), 1 <= P <= {MAX_SAMPLES}, B * P <= "
+                  f"{MAX_ROWS}; got rois {tuple(rois.shape)}, gts {tuple(gt.shape)}, rcnn_reg {tuple(rcnn_reg.shape)}, rcnn_cls "
+                  f"{tuple(rcnn_cls.shape)}")
     if tuple(mask.shape) != (B, P) or mask.dtype != torch.int64:
-        _fail(f"reg_valid_mask must be int64 ({B}, {P}), got {mask.dtype} {tuple(mask.shape)}")
+        _lib.fail("roi_head_loss", f"reg_valid_mask must be int64 ({B}, {P}), got {mask.dtype} {tuple(mask.shape)}")
     if tuple(labels.shape) != (B, P):
-        _fail(f"rcnn_cls_labels must be ({B}, {P}), got {tuple(labels.shape)}")
+        _lib.fail("roi_head_loss", f"rcnn_cls_labels must be ({B}, {P}), got {tuple(labels.shape)}")
     if labels.dtype == torch.int64:      # CLS_SCORE_TYPE cls: the target layer returns the 1 / 0 / -1 labels as int64, like the reference
         labels = labels.to(torch.float32)
     for name, t in [("rcnn_cls", rcnn_cls), ("rcnn_reg", rcnn_reg), ("rois", rois), ("gt_of_rois", gt), ("gt_of_rois_src", gt_src),
                     ("rcnn_cls_labels", labels)]:
         if t.dtype != torch.float32:
-            _fail(f"{name} must be float32, got {t.dtype}")
+            _lib.fail("roi_head_loss", f"{name} must be float32, got {t.dtype}")
     rois, gt, gt_src, mask, labels = (t.detach().contiguous() for t in (rois, gt, gt_src, mask, labels))
     rcnn_cls, rcnn_reg = rcnn_cls.contiguous(), rcnn_reg.contiguous()
     _lib.require_cuda(rcnn_cls, rcnn_reg, rois, gt, gt_src, mask, labels, allow=(torch.int64,))
