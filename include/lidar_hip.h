@@ -898,6 +898,72 @@ int lidar_sparse_to_bev_nhwc(const float *features, const int *indices, int n, i
  * 1: inter / area(box), 2: intersection area. */
 int lidar_rotate_iou_eval(const float *boxes, int n, const float *query_boxes, int k, int criterion, float *iou, void *stream);
 
+/* ------------------------------------------------------------------ KITTI AP evaluation
+ * What get_official_eval_result runs around the rotated IoU (pcdet/datasets/kitti/kitti_object_eval_python/eval.py: clean_data :30-83,
+ * image_box_overlap :86-113, d3_box_overlap :121-154, compute_statistics_jit :157-275, get_thresholds :9-27, eval_class :448-553;
+ * numba in the reference) for a whole evaluation set, on the caller's stream, without a host read, an allocation or a float atomic:
+ * two runs give the same bits (csrc/kitti_eval.hip).
+ *   Rows.  The set is packed once: every frame's boxes stacked, frame f owning rows [off[f], off[f + 1]) of
+ *     gt (total_gt, LIDAR_KITTI_EVAL_GT_COLS) f64: bbox 0..3, location 4..6, dimensions 7..9, rotation_y 10, alpha 11, occluded 12,
+ *         truncated 13;  dt (total_dt, LIDAR_KITTI_EVAL_DT_COLS) f64: the same first twelve columns, score 12 (finite);
+ *     gt_cls / dt_cls i32: 0 car, 1 pedestrian, 2 cyclist, 3 van, 4 person_sitting, 5 truck (lower-cased names, as clean_data
+ *         compares them), LIDAR_KITTI_EVAL_CLS_DONTCARE for the exact name "DontCare", LIDAR_KITTI_EVAL_CLS_OTHER for the rest;
+ *     gt_off, dt_off (frames + 1) i32 and ov_off (frames + 1) i64, ov_off[f + 1] - ov_off[f] = dt_f * gt_f, all DEVICE.
+ *     max_gt / max_dt: the caller's bound on the rows of one frame.  A frame whose offsets break it, or leave total_gt / total_dt /
+ *     ov_total, takes no part (it counts as empty); nothing outside the arrays is touched whatever the offsets hold.
+ *   lidar_kitti_eval_overlaps -> overlaps (ov_total) f64: frame f's (dt_f, gt_f) block, dt-major, at ov_off[f] (same-frame pairs
+ *     only: the reference computes all pairs of 100 frames and discards the rest).  metric 0: image_box_overlap in fp64 (boxes = dt,
+ *     query = gt); 1: the rotated BEV IoU of lidar_rotate_iou_eval on (x, z, dx, dz, ry) rounded to fp32; 2: d3_box_overlap: the
+ *     criterion-2 intersection area ROUNDED TO FP32, d3_box_overlap_kernel's arithmetic in fp64, the result rounded to fp32 again
+ *     (the reference works in place on the fp32 array before its cast to float64).  criterion as in the reference (-1 IoU, 0 over
+ *     the dt box, 1 over the gt box, else the intersection); the matcher takes -1, and for metric 0 a second block set with
+ *     criterion 0 whose DontCare columns are compute_statistics_jit's overlaps_dt_dc.
+ *   lidar_kitti_eval_class: eval_class for one metric.  classes HOST (num_class) ids 0..5, difficulties HOST (num_diff) 0..2,
+ *     min_overlaps HOST (num_overlap, num_class) f64 (min_overlaps[:, metric, :]).  A configuration is (class slot m, difficulty
+ *     slot l, overlap row k), index c = (m * num_diff + l) * num_overlap + k.  dc_overlaps: metric 0 only (else NULL).  Outputs, DEVICE:
+ *       matched (n_cfg, total_gt) f64   pass 1 (compute_fp False, thresh 0): the score a gt row's match emitted, -inf for none.
+ *                                       Gts in row order take the unassigned det with overlap > min_overlap and the highest score;
+ *                                       the comparisons are strict, so the lowest row wins a tie
+ *       num_valid_gt (num_class * num_diff) i32
+ *       thresholds (n_cfg, 41) f64, num_thresholds (n_cfg) i32   get_thresholds' sequential scan in fp64 over the scores sorted
+ *                                       descending; no matched score: no thresholds, and the curves stay zero
+ *       counts (n_cfg, 41, 3) i64       tp, fp, fn of pass 2 (compute_fp True) summed over frames, 0 past num_thresholds.  Pass 2
+ *                                       skips dets below the threshold; among the eligible dets with ignored_det 0 the largest overlap
+ *                                       wins (lowest row on a tie), otherwise the first eligible one with ignored_det 1; for metric 0
+ *                                       an unmatched det with overlap > min_overlap over a DontCare box is not a false positive
+ *       curves (3, n_cfg, 41) f64       precision, recall, orientation: per threshold, then the running maximum from the right over
+ *                                       the first num_thresholds entries; zero beyond (orientation all zero without compute_aos).
+ *                                       The similarity sum(1 + cos(gt alpha - dt alpha)) / 2 is written per frame and added over
+ *                                       frames in frame order in fp64
+ *     ws: lidar_kitti_eval_workspace_bytes(...) bytes, 256-byte aligned.
+ * Supported (lidar_kitti_eval_supported, pure host): 0 <= frames <= 2^20, total_gt <= 2^20, total_dt <= 2^22, max_gt and max_dt
+ * <= 1024, 1..8 classes, 1..3 difficulties, 1..16 overlap rows; frames with no gt, no dt or neither are valid, and so is an empty
+ * set.  Negative sizes, a metric outside 0..2, ids outside their ranges and missing pointers are LIDAR_ERR_ARG, sizes beyond the
+ * support LIDAR_ERR_UNSUPPORTED, a short workspace LIDAR_ERR_WORKSPACE, all before any launch. */
+#define LIDAR_KITTI_EVAL_GT_COLS 14
+#define LIDAR_KITTI_EVAL_DT_COLS 13
+#define LIDAR_KITTI_EVAL_CLS_DONTCARE 6
+#define LIDAR_KITTI_EVAL_CLS_OTHER 7
+#define LIDAR_KITTI_EVAL_MAX_GT 1024
+#define LIDAR_KITTI_EVAL_MAX_DT 1024
+#define LIDAR_KITTI_EVAL_MAX_CLASS 8
+#define LIDAR_KITTI_EVAL_MAX_DIFF 3
+#define LIDAR_KITTI_EVAL_MAX_OVERLAP 16
+#define LIDAR_KITTI_EVAL_PTS 41
+int lidar_kitti_eval_supported(int frames, long long total_gt, long long total_dt, int max_gt, int max_dt, int num_class,
+                               int num_diff, int num_overlap);
+size_t lidar_kitti_eval_workspace_bytes(int frames, long long total_gt, long long total_dt, int max_gt, int max_dt, int num_class,
+                                        int num_diff, int num_overlap);
+int lidar_kitti_eval_overlaps(int metric, int criterion, const double *gt, const double *dt, const int *gt_off, const int *dt_off,
+                              const long long *ov_off, int frames, long long total_gt, long long total_dt, long long ov_total,
+                              int max_gt, int max_dt, double *overlaps, void *stream);
+int lidar_kitti_eval_class(int metric, const double *gt, const double *dt, const int *gt_cls, const int *dt_cls, const int *gt_off,
+                           const int *dt_off, const long long *ov_off, const double *overlaps, const double *dc_overlaps, int frames,
+                           long long total_gt, long long total_dt, long long ov_total, int max_gt, int max_dt, const int *classes,
+                           int num_class, const int *difficulties, int num_diff, const double *min_overlaps, int num_overlap,
+                           int compute_aos, double *matched, int *num_valid_gt, double *thresholds, int *num_thresholds,
+                           long long *counts, double *curves, void *ws, size_t ws_bytes, void *stream);
+
 /* ------------------------------------------------------------------ CPU entry points (HOST pointers, no GPU touched)
  * Called by the reference from DataLoader workers (augmentation / database creation). */
 /* boxes_iou_bev_cpu (pcdet/ops/iou3d_nms/src/iou3d_cpu.cpp:232-252): out (n_a, n_b) rotated BEV IoU */

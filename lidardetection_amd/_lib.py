@@ -174,7 +174,12 @@ SIGNATURES = {
     "lidar_optim_adam_step": (i32, [vp, i32, vp, vp, C.c_longlong, vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                     C.c_longlong, i32, vp]),
     "lidar_rotate_iou_eval": (i32, [vp, i32, vp, i32, i32, vp, vp]),
-    "lidar_boxes_iou_bev_cpu": (i32, [vp, i32, vp, i32, vp]),
+    "lidar_kitti_eval_supported": (i32, [i32, C.c_longlong, C.c_longlong, i32, i32, i32, i32, i32]),
+    "lidar_kitti_eval_workspace_bytes": (sz, [i32, C.c_longlong, C.c_longlong, i32, i32, i32, i32, i32]),
+    "lidar_kitti_eval_overlaps": (i32, [i32, i32, vp, vp, vp, vp, vp, i32, C.c_longlong, C.c_longlong, C.c_longlong, i32, i32, vp, vp]),
+    "lidar_kitti_eval_class": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, C.c_longlong, C.c_longlong, C.c_longlong, i32, i32,
+                                     vp, i32, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "lidar_boxes_iou_bev_cpu":(i32, [vp, i32, vp, i32, vp]),
     "lidar_points_in_boxes_cpu": (i32, [vp, i32, vp, i32, vp]),
     "lidar_voxelize_cpu_scratch_bytes": (sz, [i32]),
     "lidar_voxelize_cpu": (i32, [vp, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp, sz]),
