@@ -191,6 +191,20 @@ int lidar_bn_relu_train_backward(int nseg, void *const *x, const int *x_ld, cons
                                  const float *grad_y, int g_ld, int g_off, const float *gamma, const double *stats,
                                  const float *scale_shift, void *const *dx, float *d_gamma, float *d_beta, void *ws, size_t ws_bytes,
                                  void *stream);
+/* The residual form, y = max(BN(z) + r, 0), for SparseBasicBlock's bn2 -> += identity -> relu on one (rows, channels) map (the
+ * reference's pcdet/models/backbones_3d/spconv_backbone.py:57-62): z / dz at row stride x_ld, the residual r at r_ld, d_r at dr_ld,
+ * y at y_ld, grad_y at g_ld (floats; every stride % 4 == 0 and >= channels; no channel offsets).  The same kernels, statistics
+ * and fixed-order fp64 reductions as above, with r added before the ReLU; the backward recomputes the mask from
+ * z * scale + shift + r > 0, writes d_r = the masked gradient, and dz / d_gamma / d_beta as above.  Supported: channels % 4 == 0,
+ * 4 <= channels <= 1024, rows >= 2, 16-byte aligned pointers.  stats / scale_shift / batch_stats / ws as above
+ * (lidar_bn_relu_train_workspace_bytes(rows, channels)).  No float atomics, no host read: bitwise reproducible. */
+int lidar_bn_add_relu_train_forward(const float *x, int x_ld, const float *r, int r_ld, int channels, long long rows,
+                                    const float *gamma, const float *beta, float eps, float *y, int y_ld, double *stats,
+                                    float *scale_shift, float *batch_stats, void *ws, size_t ws_bytes, void *stream);
+int lidar_bn_add_relu_train_backward(const float *x, int x_ld, const float *r, int r_ld, int channels, long long rows,
+                                     const float *grad_y, int g_ld, const float *gamma, const double *stats, const float *scale_shift,
+                                     float *dx, float *d_r, int dr_ld, float *d_gamma, float *d_beta, void *ws, size_t ws_bytes,
+                                     void *stream);
 
 /* ------------------------------------------------------------------ iou3d_nms
  * boxes are (N,7) f32 [x, y, z, dx, dy, dz, heading].
@@ -891,6 +905,15 @@ int lidar_optim_adam_step(const long long *table, int n_tensors, const int *chun
  * as lidar_sparse_to_dense. */
 int lidar_sparse_to_bev_nhwc(const float *features, const int *indices, int n, int channels, int batch, int D, int H, int W,
                              float *out, void *ws, size_t ws_bytes, void *stream);
+/* Its backward (csrc/sparse_train.hip): d_features (n, channels) with d_features[row][c] = grad_out[b][y][x][c * D + z] for the
+ * row's indices [b, z, y, x] (the ones the forward took).  grad_out is the gradient of the channels-last (batch, H, W, channels * D)
+ * map or a channel slice of a wider one: g_ld floats per pixel, the slice starting at channel g_off (g_off >= 0,
+ * g_off + channels * D <= g_ld).  A pure gather: no atomics, no workspace, every output element written once; a row the forward
+ * skips (b outside [0, batch), z / y / x outside the volume) gets an exactly zero gradient.  Supported (the forward's range):
+ * channels % 4 == 0, 1 <= D <= 4, n >= 0 (0: success, nothing is launched); indices and d_features 16-byte aligned; 16-byte reads
+ * when grad_out is 16-byte aligned and g_ld % 4 == g_off % 4 == 0, scalar reads otherwise.  LIDAR_ERR_ARG outside that range. */
+int lidar_sparse_to_bev_nhwc_backward(const float *grad_out, int g_ld, int g_off, const int *indices, int n, int channels, int batch,
+                                      int D, int H, int W, float *d_features, void *stream);
 
 /* ------------------------------------------------------------------ KITTI-eval rotated BEV IoU (8f rank 4)
  * rotate_iou_gpu_eval (pcdet/datasets/kitti/kitti_object_eval_python/rotate_iou.py:290-330; numba.cuda in the reference):

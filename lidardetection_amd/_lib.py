@@ -40,6 +40,8 @@ SIGNATURES = {
     "lidar_bn_relu_train_workspace_bytes": (sz, [C.c_longlong, i32]),
     "lidar_bn_relu_train_forward": (i32, [i32, vp, vp, vp, vp, C.c_longlong, vp, vp, f32, vp, i32, i32, vp, vp, vp, vp, sz, vp]),
     "lidar_bn_relu_train_backward": (i32, [i32, vp, vp, vp, vp, C.c_longlong, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "lidar_bn_add_relu_train_forward": (i32, [vp, i32, vp, i32, i32, C.c_longlong, vp, vp, f32, vp, i32, vp, vp, vp, vp, sz, vp]),
+    "lidar_bn_add_relu_train_backward": (i32, [vp, i32, vp, i32, i32, C.c_longlong, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, sz, vp]),
     "lidar_iou_workspace_bytes": (sz, [i32, i32]),
     "lidar_boxes_pairwise_bev": (i32, [vp, i32, vp, i32, i32, vp, vp, sz, vp]),
     "lidar_nms_workspace_bytes": (sz, [i32, i32]),
@@ -104,6 +106,7 @@ SIGNATURES = {
     "lidar_sparse_to_dense_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "lidar_sparse_to_dense": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp]),
     "lidar_sparse_to_bev_nhwc": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp]),
+    "lidar_sparse_to_bev_nhwc_backward": (i32, [vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
     "lidar_bias_act_nhwc": (i32, [vp, vp, C.c_longlong, i32, i32, vp, i32, i32, vp]),
     "lidar_bias_act_upsample_nhwc": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, vp]),
     "lidar_dense_gemm_bias_act": (i32, [vp, C.c_longlong, i32, vp, i32, vp, i32, vp, i32, vp, sz, vp]),

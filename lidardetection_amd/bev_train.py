@@ -165,6 +165,13 @@ def bn_relu_train(z, bn):
     return y
 
 
+def bn_relu_train_rows(z, bn, residual=None):
+    """bn_relu_train's form for an (N, C) feature matrix and a train-mode BatchNorm1d (sparse features): relu(bn(z)) or, with
+    `residual`, relu(bn(z) + residual) on the same kernels with rows = N and row stride C (spconv.train.bn_relu_train)"""
+    from .spconv import train
+    return train.bn_relu_train(z, bn, residual)
+
+
 # ------------------------------------------------------------------ stride-1 3x3 convolution on the Winograd kernels
 def wino_train_supported(cin, cout):
     """both directions run on the Winograd kernels: the forward (Cin -> Cout) and the input gradient (Cout -> Cin).  Pure host."""

@@ -16,6 +16,11 @@
 //             coefficients left dz at 4.5e-5 of its scale against float64 (now 6.8e-8).  The pass moves 12 bytes
 //             per element for five fp64 operations; its time with fp64 has not been measured in isolation.
 // No float atomics and no host read: every result is bitwise reproducible and every call can be captured in a graph.
+//
+// The residual form (SparseBasicBlock's bn2 -> += identity -> relu, spconv_backbone.py:57-62 of the reference) is the
+// same kernels with RES = true: y = max(z scale + shift + r, 0) for a residual r (rows, C) at its own row stride, the backward's
+// mask recomputed from that sum, and d_r = delta written beside dz.  The statistics, the reductions and the coefficients are the one
+// copy above; RES = false compiles to the code the plain entry points always ran.
 #include "common.h"
 
 #define BT_MAX_SEG 4
@@ -26,6 +31,9 @@ struct BtSeg {
     const float *x;                // z (forward and backward input)
     float *dx;                     // dz (backward output; same row stride and channel offset as x)
     int C, ld, off, c0;
+    const float *r;                // RES only: the residual added before the ReLU, (rows, C) at row stride r_ld
+    float *dr;                     // RES only: its gradient (backward output), (rows, C) at row stride dr_ld
+    int r_ld, dr_ld;
 };
 struct BtSegs {
     BtSeg s[BT_MAX_SEG];
@@ -131,6 +139,7 @@ __global__ __launch_bounds__(256) void bt_finalize_kernel(const double *__restri
 }
 
 // forward pass 3: y = max(z scale + shift, 0) into channels [y_off + c0, + C) of the (rows, y_ld) output.  grid (nb, segments)
+template <bool RES>
 __global__ __launch_bounds__(256) void bt_apply_kernel(BtSegs segs, long long rows, int nb, const float *__restrict__ scale_shift,
                                                        float *__restrict__ y, int y_ld, int y_off) {
     const BtSeg sg = segs.s[blockIdx.y];
@@ -144,8 +153,14 @@ __global__ __launch_bounds__(256) void bt_apply_kernel(BtSegs segs, long long ro
     for (long long row = (long long)blockIdx.x * L.R + L.r; row < rows; row += step) {
         const float4 v = bt_ld4(src + row * sg.ld);
         float4 o;
-        o.x = fmaxf(fmaf(v.x, sc.x, sh.x), 0.f); o.y = fmaxf(fmaf(v.y, sc.y, sh.y), 0.f);
-        o.z = fmaxf(fmaf(v.z, sc.z, sh.z), 0.f); o.w = fmaxf(fmaf(v.w, sc.w, sh.w), 0.f);
+        if constexpr (RES) {
+            const float4 r = bt_ld4(sg.r + 4 * L.q + row * sg.r_ld);
+            o.x = fmaxf(fmaf(v.x, sc.x, sh.x) + r.x, 0.f); o.y = fmaxf(fmaf(v.y, sc.y, sh.y) + r.y, 0.f);
+            o.z = fmaxf(fmaf(v.z, sc.z, sh.z) + r.z, 0.f); o.w = fmaxf(fmaf(v.w, sc.w, sh.w) + r.w, 0.f);
+        } else {
+            o.x = fmaxf(fmaf(v.x, sc.x, sh.x), 0.f); o.y = fmaxf(fmaf(v.y, sc.y, sh.y), 0.f);
+            o.z = fmaxf(fmaf(v.z, sc.z, sh.z), 0.f); o.w = fmaxf(fmaf(v.w, sc.w, sh.w), 0.f);
+        }
         bt_st4(dst + row * (long long)y_ld, o);
     }
 }
@@ -153,8 +168,25 @@ __global__ __launch_bounds__(256) void bt_apply_kernel(BtSegs segs, long long ro
 __device__ __forceinline__ float bt_delta(float z, float g, float sc, float sh) {
     return fmaxf(fmaf(z, sc, sh), 0.f) > 0.f ? g : 0.f;        // the forward's y, bit for bit
 }
+__device__ __forceinline__ float bt_delta_res(float z, float g, float sc, float sh, float r) {
+    return fmaxf(fmaf(z, sc, sh) + r, 0.f) > 0.f ? g : 0.f;    // the residual forward's y, bit for bit
+}
+// delta of one quad; rv is read only when RES
+template <bool RES>
+__device__ __forceinline__ float4 bt_delta4(const float4 &z, const float4 &g, const float4 &sc, const float4 &sh, const float4 &rv) {
+    float4 d;
+    if constexpr (RES) {
+        d.x = bt_delta_res(z.x, g.x, sc.x, sh.x, rv.x); d.y = bt_delta_res(z.y, g.y, sc.y, sh.y, rv.y);
+        d.z = bt_delta_res(z.z, g.z, sc.z, sh.z, rv.z); d.w = bt_delta_res(z.w, g.w, sc.w, sh.w, rv.w);
+    } else {
+        d.x = bt_delta(z.x, g.x, sc.x, sh.x); d.y = bt_delta(z.y, g.y, sc.y, sh.y);
+        d.z = bt_delta(z.z, g.z, sc.z, sh.z); d.w = bt_delta(z.w, g.w, sc.w, sh.w);
+    }
+    return d;
+}
 
 // backward pass 1: sum delta, sum delta z (fp64) per channel and block.  grid (nb, segments)
+template <bool RES>
 __global__ __launch_bounds__(256) void bt_bwd_stats_kernel(BtSegs segs, long long rows, int nb, const float *__restrict__ scale_shift,
                                                            const float *__restrict__ g, int g_ld, int g_off, double *__restrict__ part) {
     const BtSeg sg = segs.s[blockIdx.y];
@@ -167,26 +199,27 @@ __global__ __launch_bounds__(256) void bt_bwd_stats_kernel(BtSegs segs, long lon
         const long long step = (long long)nb * L.R;
         long long row = (long long)blockIdx.x * L.R + L.r;
         for (; row + step < rows; row += 2 * step) {          // two rows in flight
-            float4 z[2], gv[2];
+            float4 z[2], gv[2], rv[2];
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
                 z[u] = bt_ld4(zs + (row + u * step) * sg.ld);
                 gv[u] = bt_ld4(gs + (row + u * step) * (long long)g_ld);
+                if constexpr (RES) rv[u] = bt_ld4(sg.r + 4 * L.q + (row + u * step) * sg.r_ld);
             }
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
-                const float d0 = bt_delta(z[u].x, gv[u].x, sc.x, sh.x), d1 = bt_delta(z[u].y, gv[u].y, sc.y, sh.y);
-                const float d2 = bt_delta(z[u].z, gv[u].z, sc.z, sh.z), d3 = bt_delta(z[u].w, gv[u].w, sc.w, sh.w);
-                a[0] += d0; a[1] += d1; a[2] += d2; a[3] += d3;
-                a[4] += (double)d0 * z[u].x; a[5] += (double)d1 * z[u].y; a[6] += (double)d2 * z[u].z; a[7] += (double)d3 * z[u].w;
+                const float4 d = bt_delta4<RES>(z[u], gv[u], sc, sh, rv[u]);
+                a[0] += d.x; a[1] += d.y; a[2] += d.z; a[3] += d.w;
+                a[4] += (double)d.x * z[u].x; a[5] += (double)d.y * z[u].y; a[6] += (double)d.z * z[u].z; a[7] += (double)d.w * z[u].w;
             }
         }
         for (; row < rows; row += step) {
             const float4 z = bt_ld4(zs + row * sg.ld), gv = bt_ld4(gs + row * (long long)g_ld);
-            const float d0 = bt_delta(z.x, gv.x, sc.x, sh.x), d1 = bt_delta(z.y, gv.y, sc.y, sh.y);
-            const float d2 = bt_delta(z.z, gv.z, sc.z, sh.z), d3 = bt_delta(z.w, gv.w, sc.w, sh.w);
-            a[0] += d0; a[1] += d1; a[2] += d2; a[3] += d3;
-            a[4] += (double)d0 * z.x; a[5] += (double)d1 * z.y; a[6] += (double)d2 * z.z; a[7] += (double)d3 * z.w;
+            float4 rv;
+            if constexpr (RES) rv = bt_ld4(sg.r + 4 * L.q + row * sg.r_ld);
+            const float4 d = bt_delta4<RES>(z, gv, sc, sh, rv);
+            a[0] += d.x; a[1] += d.y; a[2] += d.z; a[3] += d.w;
+            a[4] += (double)d.x * z.x; a[5] += (double)d.y * z.y; a[6] += (double)d.z * z.z; a[7] += (double)d.w * z.w;
         }
     }
     bt_block_partials(a, L, sg.C, sg.c0, segs.ctot, nb, part);
@@ -211,6 +244,7 @@ __global__ __launch_bounds__(256) void bt_bwd_finalize_kernel(const double *__re
 }
 
 // backward pass 3: dz into the segment's dx (the row stride and channel offset of its z).  grid (nb, segments)
+template <bool RES>
 __global__ __launch_bounds__(256) void bt_bwd_apply_kernel(BtSegs segs, long long rows, int nb, const float *__restrict__ scale_shift,
                                                            const double *__restrict__ coef, const float *__restrict__ g, int g_ld,
                                                            int g_off) {
@@ -229,12 +263,16 @@ __global__ __launch_bounds__(256) void bt_bwd_apply_kernel(BtSegs segs, long lon
     const long long step = (long long)nb * L.R;
     for (long long row = (long long)blockIdx.x * L.R + L.r; row < rows; row += step) {
         const float4 z = bt_ld4(zs + row * sg.ld), gv = bt_ld4(gs + row * (long long)g_ld);
+        float4 rv;
+        if constexpr (RES) rv = bt_ld4(sg.r + 4 * L.q + row * sg.r_ld);
+        const float4 d = bt_delta4<RES>(z, gv, sc, sh, rv);
         float4 o;
-        o.x = (float)(A[0] * ((double)bt_delta(z.x, gv.x, sc.x, sh.x) - m1[0] - ((double)z.x - mu[0]) * m2[0]));
-        o.y = (float)(A[1] * ((double)bt_delta(z.y, gv.y, sc.y, sh.y) - m1[1] - ((double)z.y - mu[1]) * m2[1]));
-        o.z = (float)(A[2] * ((double)bt_delta(z.z, gv.z, sc.z, sh.z) - m1[2] - ((double)z.z - mu[2]) * m2[2]));
-        o.w = (float)(A[3] * ((double)bt_delta(z.w, gv.w, sc.w, sh.w) - m1[3] - ((double)z.w - mu[3]) * m2[3]));
+        o.x = (float)(A[0] * ((double)d.x - m1[0] - ((double)z.x - mu[0]) * m2[0]));
+        o.y = (float)(A[1] * ((double)d.y - m1[1] - ((double)z.y - mu[1]) * m2[1]));
+        o.z = (float)(A[2] * ((double)d.z - m1[2] - ((double)z.z - mu[2]) * m2[2]));
+        o.w = (float)(A[3] * ((double)d.w - m1[3] - ((double)z.w - mu[3]) * m2[3]));
         bt_st4(ds + row * sg.ld, o);
+        if constexpr (RES) bt_st4(sg.dr + 4 * L.q + row * sg.dr_ld, d);
     }
 }
 
@@ -264,6 +302,7 @@ static int bt_segs(int nseg, void *const *x, void *const *dx, const int *x_ld, c
         S.s[i].x = (const float *)x[i];
         S.s[i].dx = dx ? (float *)dx[i] : nullptr;
         S.s[i].C = C; S.s[i].ld = ld; S.s[i].off = off; S.s[i].c0 = S.ctot;
+        S.s[i].r = nullptr; S.s[i].dr = nullptr; S.s[i].r_ld = S.s[i].dr_ld = 0;
         S.ctot += C;
     }
     return LIDAR_OK;
@@ -290,7 +329,7 @@ LIDAR_EXPORT int lidar_bn_relu_train_forward(int nseg, void *const *x, const int
     hipLaunchKernelGGL(bt_reduce_kernel, dim3(2 * S.ctot), dim3(256), 0, s, part, nb, tot);
     hipLaunchKernelGGL(bt_finalize_kernel, dim3(divup(S.ctot, 256)), dim3(256), 0, s, tot, S.ctot, rows, gamma, beta, eps, stats,
                        scale_shift, batch_stats);
-    hipLaunchKernelGGL(bt_apply_kernel, dim3(nb, nseg), dim3(256), 0, s, S, rows, nb, scale_shift, y, y_ld, y_off);
+    hipLaunchKernelGGL(bt_apply_kernel<false>, dim3(nb, nseg), dim3(256), 0, s, S, rows, nb, scale_shift, y, y_ld, y_off);
     return lidar_check_launch("lidar_bn_relu_train_forward");
 }
 
@@ -307,10 +346,62 @@ LIDAR_EXPORT int lidar_bn_relu_train_backward(int nseg, void *const *x, const in
     const int nb = bt_blocks(rows);
     double *part = (double *)ws, *tot = part + (size_t)2 * S.ctot * nb;
     double *coef = tot + 2 * S.ctot;
-    hipLaunchKernelGGL(bt_bwd_stats_kernel, dim3(nb, nseg), dim3(256), 0, s, S, rows, nb, scale_shift, grad_y, g_ld, g_off, part);
+    hipLaunchKernelGGL(bt_bwd_stats_kernel<false>, dim3(nb, nseg), dim3(256), 0, s, S, rows, nb, scale_shift, grad_y, g_ld, g_off, part);
     hipLaunchKernelGGL(bt_reduce_kernel, dim3(2 * S.ctot), dim3(256), 0, s, part, nb, tot);
     hipLaunchKernelGGL(bt_bwd_finalize_kernel, dim3(divup(S.ctot, 256)), dim3(256), 0, s, tot, S.ctot, rows, gamma, stats, coef,
                        d_gamma, d_beta);
-    hipLaunchKernelGGL(bt_bwd_apply_kernel, dim3(nb, nseg), dim3(256), 0, s, S, rows, nb, scale_shift, coef, grad_y, g_ld, g_off);
+    hipLaunchKernelGGL(bt_bwd_apply_kernel<false>, dim3(nb, nseg), dim3(256), 0, s, S, rows, nb, scale_shift, coef, grad_y, g_ld, g_off);
     return lidar_check_launch("lidar_bn_relu_train_backward");
+}
+
+// ---- the residual form: y = max(BN(z) + r, 0) on one (rows, C) map; z / dz at x_ld, r at r_ld, d_r at dr_ld, y at y_ld, grad_y at g_ld
+static int bt_res_seg(const float *x, float *dx, int x_ld, const float *r, float *dr, int r_ld, int dr_ld, int C, BtSegs &S) {
+    void *xs[1] = {(void *)x}, *dxs[1] = {(void *)dx};
+    const int off = 0;
+    if (bt_segs(1, xs, dx ? dxs : nullptr, &x_ld, &off, &C, S) != LIDAR_OK) return LIDAR_ERR_ARG;
+    if (!bt_aligned(r) || r_ld % 4 || r_ld < C) return LIDAR_ERR_ARG;
+    if (dx && (!bt_aligned(dr) || dr_ld % 4 || dr_ld < C)) return LIDAR_ERR_ARG;
+    S.s[0].r = r; S.s[0].dr = dr; S.s[0].r_ld = r_ld; S.s[0].dr_ld = dr_ld;
+    return LIDAR_OK;
+}
+
+LIDAR_EXPORT int lidar_bn_add_relu_train_forward(const float *x, int x_ld, const float *r, int r_ld, int channels, long long rows,
+                                                 const float *gamma, const float *beta, float eps, float *y, int y_ld, double *stats,
+                                                 float *scale_shift, float *batch_stats, void *ws, size_t ws_bytes, void *stream) {
+    BtSegs S;
+    if (bt_res_seg(x, nullptr, x_ld, r, nullptr, r_ld, 0, channels, S) != LIDAR_OK) return LIDAR_ERR_ARG;
+    if (rows < 2 || !gamma || !beta || !stats || !bt_aligned(scale_shift) || !batch_stats || !bt_aligned(ws) || !(eps >= 0.f))
+        return LIDAR_ERR_ARG;
+    if (!bt_map_ok(y, y_ld, 0, S.ctot)) return LIDAR_ERR_ARG;
+    if (ws_bytes < lidar_bn_relu_train_workspace_bytes(rows, S.ctot)) return LIDAR_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    const int nb = bt_blocks(rows);
+    double *part = (double *)ws, *tot = part + (size_t)2 * S.ctot * nb;
+    hipLaunchKernelGGL(bt_stats_kernel, dim3(nb, 1), dim3(256), 0, s, S, rows, nb, part);
+    hipLaunchKernelGGL(bt_reduce_kernel, dim3(2 * S.ctot), dim3(256), 0, s, part, nb, tot);
+    hipLaunchKernelGGL(bt_finalize_kernel, dim3(divup(S.ctot, 256)), dim3(256), 0, s, tot, S.ctot, rows, gamma, beta, eps, stats,
+                       scale_shift, batch_stats);
+    hipLaunchKernelGGL(bt_apply_kernel<true>, dim3(nb, 1), dim3(256), 0, s, S, rows, nb, scale_shift, y, y_ld, 0);
+    return lidar_check_launch("lidar_bn_add_relu_train_forward");
+}
+
+LIDAR_EXPORT int lidar_bn_add_relu_train_backward(const float *x, int x_ld, const float *r, int r_ld, int channels, long long rows,
+                                                  const float *grad_y, int g_ld, const float *gamma, const double *stats,
+                                                  const float *scale_shift, float *dx, float *d_r, int dr_ld, float *d_gamma,
+                                                  float *d_beta, void *ws, size_t ws_bytes, void *stream) {
+    BtSegs S;
+    if (!dx || !d_r || bt_res_seg(x, dx, x_ld, r, d_r, r_ld, dr_ld, channels, S) != LIDAR_OK) return LIDAR_ERR_ARG;
+    if (rows < 2 || !gamma || !stats || !bt_aligned(scale_shift) || !d_gamma || !d_beta || !bt_aligned(ws)) return LIDAR_ERR_ARG;
+    if (!bt_map_ok(grad_y, g_ld, 0, S.ctot)) return LIDAR_ERR_ARG;
+    if (ws_bytes < lidar_bn_relu_train_workspace_bytes(rows, S.ctot)) return LIDAR_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    const int nb = bt_blocks(rows);
+    double *part = (double *)ws, *tot = part + (size_t)2 * S.ctot * nb;
+    double *coef = tot + 2 * S.ctot;
+    hipLaunchKernelGGL(bt_bwd_stats_kernel<true>, dim3(nb, 1), dim3(256), 0, s, S, rows, nb, scale_shift, grad_y, g_ld, 0, part);
+    hipLaunchKernelGGL(bt_reduce_kernel, dim3(2 * S.ctot), dim3(256), 0, s, part, nb, tot);
+    hipLaunchKernelGGL(bt_bwd_finalize_kernel, dim3(divup(S.ctot, 256)), dim3(256), 0, s, tot, S.ctot, rows, gamma, stats, coef,
+                       d_gamma, d_beta);
+    hipLaunchKernelGGL(bt_bwd_apply_kernel<true>, dim3(nb, 1), dim3(256), 0, s, S, rows, nb, scale_shift, coef, grad_y, g_ld, 0);
+    return lidar_check_launch("lidar_bn_add_relu_train_backward");
 }

@@ -51,10 +51,17 @@ class SparseBasicBlock(spconv.SparseModule):
             # inference: each conv + BN (+ shortcut) + ReLU is one launch
             mid = self.conv1.forward_fused(x, self.bn1, relu=True)
             return self.conv2.forward_fused(mid, self.bn2, relu=True, residual=shortcut.features)
+        fused = torch.is_grad_enabled() and spconv.train.fused_bn_train_enabled()      # opt-in: spconv.fused_bn_train
         out = self.conv1(x)
-        out.features = self.relu(self.bn1(out.features))
+        if fused and spconv.train.takes(self.bn1, out.features):
+            out.features = spconv.bn_relu_train(out.features, self.bn1)
+        else:
+            out.features = self.relu(self.bn1(out.features))
         out = self.conv2(out)
-        out.features = self.relu(self.bn2(out.features) + shortcut.features)
+        if fused and spconv.train.takes(self.bn2, out.features) and shortcut.features.shape == out.features.shape:
+            out.features = spconv.bn_relu_train(out.features, self.bn2, residual=shortcut.features)
+        else:
+            out.features = self.relu(self.bn2(out.features) + shortcut.features)
         return out
 
 

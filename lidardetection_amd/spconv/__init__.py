@@ -14,7 +14,9 @@ from .conv import SparseConv3d, SparseConvolution, SparseInverseConv3d, SubMConv
 from .modules import SparseModule, SparseSequential, prebuild_rulebooks, run_stages_pipelined
 from .tensor import SparseConvTensor
 from .graphed import GraphedStages
-from . import ops, utils
+from .train import bn_relu_train, fused_bn_train
+from . import ops, train, utils
 
 __all__ = ["SparseConvTensor", "SparseModule", "SparseSequential", "SparseConvolution", "SubMConv3d", "SparseConv3d",
-           "SparseInverseConv3d", "prebuild_rulebooks", "run_stages_pipelined", "GraphedStages", "ops", "utils"]
+           "SparseInverseConv3d", "prebuild_rulebooks", "run_stages_pipelined", "GraphedStages", "fused_bn_train", "bn_relu_train", "ops", "train",
+           "utils"]

@@ -4,7 +4,7 @@ from collections import OrderedDict
 import torch
 from torch import nn
 
-from . import ops
+from . import ops, train
 from .tensor import SparseConvTensor
 
 
@@ -56,13 +56,25 @@ class SparseSequential(SparseModule):
     def forward(self, input):
         if not torch.is_grad_enabled():
             return self._forward_inference(input)
-        for module in self._modules.values():
+        fused = train.fused_bn_train_enabled()
+        mods = list(self._modules.values())
+        skip = False
+        for i, module in enumerate(mods):
+            if skip:                                   # the ReLU of a fused BatchNorm1d -> ReLU pair
+                skip = False
+                continue
             if is_spconv_module(module):
                 assert isinstance(input, SparseConvTensor)
                 input = module(input)
             elif isinstance(input, SparseConvTensor):
                 if input.indices.shape[0] != 0:        # BatchNorm1d cannot take an empty batch
-                    input.features = module(input.features)
+                    if (fused and i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
+                            and train.takes(module, input.features)):
+                        # opt-in (spconv.fused_bn_train): the pair as one fused train-mode call (csrc/bn_train.hip)
+                        input.features = train.bn_relu_train(input.features, module)
+                        skip = True
+                    else:
+                        input.features = module(input.features)
             else:
                 input = module(input)
         return input

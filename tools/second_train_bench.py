@@ -1,0 +1,134 @@
+"""Times one SECOND-KITTI training iteration (SECONDKitti.train_step: voxelise, MeanVFE, VoxelBackBone8x, HeightCompression, BEV
+backbone, heads, loss, backward, the fused optimiser step) on synthetic 64-beam frames, at batch 4 (the reference's
+BATCH_SIZE_PER_GPU) and batch 16, with the sparse half and the BEV backbone each on the stock torch modules or on this package's
+fused train-mode kernels:
+
+  sparse="stock" / "fused":    BatchNorm1d -> ReLU between the sparse convolutions as torch modules, or spconv.fused_bn_train
+  backbone="stock" / "fused":  backbone_head_stock, or backbone_head_train (bev_train.TrainBEVBackbone)
+
+ms per step from a host clock around `steps` iterations that end in a device synchronise (the step reads counts back, so it is
+not sync-free), the four configurations of one batch size alternating in every round of the same process; best and all rounds are
+printed.  Also: HeightCompression forward + backward alone (SparseConvTensor.dense_bev() on the one-pass kernels against the old
+expression dense().view().contiguous(channels_last) with its index_put backward) on a random site set of the same size.
+One JSON line.
+
+Usage: python tools/second_train_bench.py [--batches 4 16] [--steps 5] [--warmup 3] [--rounds 3]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from lidardetection_amd import optim, spconv, synth  # noqa: E402
+from lidardetection_amd.second import SECONDKitti  # noqa: E402
+
+CONFIGS = [("stock", "stock"), ("fused", "stock"), ("stock", "fused"), ("fused", "fused")]      # (sparse, backbone)
+SIZES = np.array([[3.9, 1.6, 1.56], [0.8, 0.6, 1.73], [1.76, 0.6, 1.73]], np.float32)
+
+
+def inputs(B, dev, seed=0):
+    frames = [synth.cloud_ring(2000 + seed + i) for i in range(B)]
+    pts = torch.from_numpy(np.concatenate(frames)).to(dev)
+    lens = np.cumsum([0] + [len(f) for f in frames])
+    offs = torch.tensor(lens, dtype=torch.int32, device=dev)
+    r = np.random.default_rng(seed)
+    gt = np.zeros((B, 12, 8), np.float32)
+    for b in range(B):
+        n = 8
+        cls = r.integers(1, 4, n)
+        gt[b, :n, 0], gt[b, :n, 1], gt[b, :n, 2] = r.uniform(5, 60, n), r.uniform(-30, 30, n), r.uniform(-1.5, -0.5, n)
+        gt[b, :n, 3:6] = SIZES[cls - 1] * r.uniform(0.9, 1.1, (n, 1))
+        gt[b, :n, 6], gt[b, :n, 7] = r.uniform(-np.pi, np.pi, n), cls
+    return pts, offs, torch.from_numpy(gt).to(dev), [int(v) for v in lens]
+
+
+def timed(fn, steps):
+    """ms per call of `steps` calls of fn(), host clock, the queue drained before and after"""
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3 / steps
+
+
+def bench_steps(B, dev, args):
+    torch.manual_seed(0)
+    model = SECONDKitti(batch_size=B, device=dev).train()
+    pts, offs, gt, host_offs = inputs(B, dev)
+    opt = optim.AdamOneCycle(model, wd=0.01, max_grad_norm=10.0)
+    opt.lr, opt.mom = optim.one_cycle(0, 100)
+    fns = {}
+    for sparse, backbone in CONFIGS:
+        fns[f"sparse={sparse},backbone={backbone}"] = (
+            lambda s=sparse, b=backbone: model.train_step(pts, offs, gt, opt, host_offsets=host_offs, sparse=s, backbone=b))
+    for fn in fns.values():
+        timed(fn, args.warmup)
+    rows = {k: [] for k in fns}
+    for _ in range(args.rounds):                     # alternate, so that a drift of the machine hits every configuration
+        for k, fn in fns.items():
+            rows[k].append(timed(fn, args.steps))
+    with torch.no_grad():
+        vox = model.voxelizer(pts, offs, model.n_max, compact=True, host_offsets=host_offs)
+        voxels = int(vox["voxel_offsets"][B])
+    del model, opt
+    torch.cuda.empty_cache()
+    return {"voxels": voxels, "ms_per_step_best": {k: min(v) for k, v in rows.items()}, "ms_per_step_all_rounds": rows}
+
+
+def bench_dense_bev(B, dev, args, C=128, D=2, H=200, W=176, rows_per_frame=12000):
+    r = np.random.default_rng(1)
+    idx = []
+    for b in range(B):
+        flat = r.choice(D * H * W, rows_per_frame, replace=False)
+        z, rem = np.divmod(flat, H * W)
+        y, x = np.divmod(rem, W)
+        idx.append(np.stack([np.full_like(z, b), z, y, x], 1))
+    idx = torch.from_numpy(np.concatenate(idx).astype(np.int32)).to(dev)
+    feats = torch.randn(idx.shape[0], C, device=dev)
+    G = torch.randn(B, C * D, H, W, device=dev).contiguous(memory_format=torch.channels_last)
+
+    def run(new):
+        f = feats.detach().requires_grad_(True)
+        t = spconv.SparseConvTensor(f, idx, [D, H, W], B)
+        out = t.dense_bev() if new else t.dense().view(B, C * D, H, W).contiguous(memory_format=torch.channels_last)
+        out.backward(G)
+        return f.grad
+
+    assert torch.equal(run(True), run(False))
+    fns = {"fallback": lambda: run(False), "kernels": lambda: run(True)}
+    for fn in fns.values():
+        timed(fn, args.warmup)
+    rows = {k: [] for k in fns}
+    for _ in range(args.rounds):
+        for k, fn in fns.items():
+            rows[k].append(timed(fn, 4 * args.steps))
+    return {"rows": int(idx.shape[0]), "map": [B, C * D, H, W], "ms_fwd_bwd_best": {k: min(v) for k, v in rows.items()},
+            "ms_fwd_bwd_all_rounds": rows}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", type=int, nargs="+", default=[4, 16])
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--rounds", type=int, default=3)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("second_train_bench needs the GPU: a CPU run measures nothing")
+    dev = "cuda:0"
+    out = {"metric": "SECOND-KITTI train_step, ms per step (host clock around synchronised windows)", "steps": args.steps,
+           "warmup": args.warmup, "rounds": args.rounds, "device": torch.cuda.get_device_name(0), "train_step": {}, "dense_bev": {}}
+    for B in args.batches:
+        out["dense_bev"][f"bs{B}"] = bench_dense_bev(B, dev, args)
+        out["train_step"][f"bs{B}"] = bench_steps(B, dev, args)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
