@@ -274,6 +274,47 @@ int lidar_sa_layer2_max_stack(int B, int M, int H1, int H2, int nsample, const f
 int lidar_group_points_grad_stack(int B, int M, int C, int N, int nsample, const float *grad_out, const int *idx,
                                   const int *idx_batch_cnt, const int *features_batch_cnt, float *grad_features,
                                   void *stream);
+/* ---- set abstraction, TRAIN mode (csrc/sa_train.hip): StackSAModuleMSG.forward in grad mode
+ * (pointnet2_stack/pointnet2_modules.py:58-92: QueryAndGroup -> 1x1 Conv2d / BatchNorm2d / ReLU -> max_pool2d over the samples) on
+ * row-major (M * nsample, H) fp32 matrices, row (m, s) at "pair number" m * nsample + s; idx is the RAW ball-query result as for
+ * lidar_group_rows_affine_stack (idx[m][0] < 0: empty ball).  Supported (lidar_sa_train_supported, pure host): H % 4 == 0,
+ * 4 <= H <= 128, 1 <= nsample <= 64; further M >= 0, N >= 0 (a zero size: no launch, success), M * nsample < 2^31, 16-byte aligned
+ * pointers, any per-frame count may be 0.  Anything else: LIDAR_ERR_ARG before any launch.  No float atomics, no host read: bitwise
+ * reproducible. */
+int lidar_sa_train_supported(int H, int nsample);
+/* The first layer in front of the gather, without bias and ReLU (BatchNorm follows): z (M * nsample, H) with row (m, s) =
+ * table[start_b + idx[m][s]] - query_term[m] (query_term may be null); the rows of an empty ball are exactly 0 and take part in the
+ * batch statistics, as new_features[empty_ball_mask] = 0 feeds the bias-free conv in the reference (pointnet2_utils.py:146-152).
+ * N = rows of table. */
+int lidar_sa_gather_train_forward(int B, int M, int N, int H, int nsample, const float *table, const float *query_term,
+                                  const int *features_batch_cnt, const int *idx, const int *idx_batch_cnt, float *z, void *stream);
+/* The inverse index of that gather, in place of the float atomicAdd per element of group_points_grad_kernel_stack
+ * (group_points_gpu.cu:15-45): keys (M * nsample) i32 = each pair's global source row, N for the pairs of empty balls (left out).
+ * The caller sorts (key, pair number) stably by key -- `pairs` is the sorted pair numbers -- and lidar_sa_row_start turns the sorted
+ * keys into row_start (N + 1): source row n is read by pairs[row_start[n] .. row_start[n + 1]), ascending pair numbers, duplicates
+ * kept (a ball padded with its first hit lists that source several times).  Entries of `pairs` from row_start[N] on are the
+ * left-out pairs. */
+int lidar_sa_pair_keys(int B, int M, int N, int nsample, const int *features_batch_cnt, const int *idx, const int *idx_batch_cnt,
+                       int *keys, void *stream);
+int lidar_sa_row_start(long long num_pairs, int N, const int *sorted_keys, int *row_start, void *stream);
+/* d_table (N, H)[n] = sum of dz over n's list in list order (every row written, 0 for an empty list); d_query (M, H)[m] =
+ * -sum_s dz[m, s] in ascending s, 0 for an empty ball (d_query may be null).  fp64 accumulators, rounded once. */
+int lidar_sa_gather_train_backward(int M, int N, int H, int nsample, const float *dz, const int *idx, const int *row_start,
+                                   const int *pairs, float *d_table, float *d_query, void *stream);
+/* The last layer's BatchNorm2d (batch statistics over all M * nsample rows) + ReLU + max_pool2d over the samples
+ * (pointnet2_modules.py:84-90), fused: out (M, H) = max_s relu(z * scale + shift), arg (M, H) u8 = the lowest s among equal maxima
+ * (gamma of either sign); stats / scale_shift / batch_stats as lidar_bn_relu_train_forward lays them out (the caller applies the
+ * running-statistics update).  Backward: the gradient of y is grad_out[m, c] at row (m, arg[m, c]) where z * scale + shift > 0
+ * (recomputed) and 0 elsewhere; dz (M * nsample, H) is the full BatchNorm backward of it, d_gamma / d_beta (H).  The post-activation
+ * (M * nsample, H) tensor is never written.  M * nsample >= 2.  ws: lidar_bn_relu_max_train_workspace_bytes (pure host; 0 outside
+ * the support). */
+size_t lidar_bn_relu_max_train_workspace_bytes(int M, int nsample, int H);
+int lidar_bn_relu_max_train_forward(const float *z, int M, int nsample, int H, const float *gamma, const float *beta, float eps,
+                                    float *out, unsigned char *arg, double *stats, float *scale_shift, float *batch_stats, void *ws,
+                                    size_t ws_bytes, void *stream);
+int lidar_bn_relu_max_train_backward(const float *z, int M, int nsample, int H, const float *grad_out, const unsigned char *arg,
+                                     const float *gamma, const double *stats, const float *scale_shift, float *dz, float *d_gamma,
+                                     float *d_beta, void *ws, size_t ws_bytes, void *stream);
 /* furthest_point_sampling_wrapper (sampling.cpp, sampling_gpu.cu:24-140; same kernel in pointnet2_batch):
  * points (b, n, 3), temp (b, n) = 1e10 on entry, idx (b, m) */
 int lidar_furthest_point_sampling(int b, int n, int m, const float *points, float *temp, int *idx, void *stream);

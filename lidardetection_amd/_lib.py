@@ -58,6 +58,14 @@ SIGNATURES = {
     "lidar_sa_layer2_max_supported": (i32, [i32, i32, i32]),
     "lidar_sa_layer2_max_stack": (i32, [i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "lidar_group_points_grad_stack": (i32, [i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
+    "lidar_sa_train_supported": (i32, [i32, i32]),
+    "lidar_sa_gather_train_forward": (i32, [i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "lidar_sa_pair_keys": (i32, [i32, i32, i32, i32, vp, vp, vp, vp, vp]),
+    "lidar_sa_row_start": (i32, [C.c_longlong, i32, vp, vp, vp]),
+    "lidar_sa_gather_train_backward": (i32, [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "lidar_bn_relu_max_train_workspace_bytes": (sz, [i32, i32, i32]),
+    "lidar_bn_relu_max_train_forward": (i32, [vp, i32, i32, i32, vp, vp, f32, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "lidar_bn_relu_max_train_backward": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
     "lidar_furthest_point_sampling": (i32, [i32, i32, i32, vp, vp, vp, vp]),
     "lidar_three_nn_stack": (i32, [i32, i32, vp, vp, vp, vp, vp, vp, vp]),
     "lidar_three_interpolate_stack": (i32, [i32, i32, vp, vp, vp, vp, vp]),

@@ -70,17 +70,10 @@ class StackSAModuleMSG(nn.Module):
                 return False
         return True
 
-    def forward_inference(self, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, features=None):
-        """The same result as forward() in eval mode, built for the GPU: groups are gathered ROW-major ((M * nsample, C) — one
-        contiguous run per neighbour, lidar_group_rows_stack), the shared MLP is a chain of plain GEMMs with BatchNorm folded
-        into the weights and the shift + ReLU applied in place, and the max runs over contiguous blocks of nsample rows.  The
-        (M, C, nsample) tensor of the reference layout and the 1x1 convolution over its strided view never exist."""
+    def _ball_queries(self, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt):
+        """the raw ball-query result (M, nsample) int32 of every scale (column 0 < 0: empty ball)"""
         from .....ext import pointnet2_stack_cuda as native
-        C.require_contiguous(xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt)
         n_batch, n_query = xyz_batch_cnt.shape[0], new_xyz.shape[0]
-        feats = None if features is None else features.contiguous()
-        width = 0 if feats is None else feats.shape[1]
-        per_scale = []
         idxs = [C.zeros_i32((n_query, g.nsample), xyz.device) for g in self.groupers]
         ga = self.groupers
         # scales in pairs (one pass over the distances for both radii), through a cell grid over the candidates when there are
@@ -100,6 +93,20 @@ class StackSAModuleMSG(nn.Module):
             else:
                 native.ball_query_wrapper(n_batch, n_query, ga[-1].radius, ga[-1].nsample, new_xyz, new_xyz_batch_cnt, xyz,
                                           xyz_batch_cnt, idxs[-1])
+        return idxs
+
+    def forward_inference(self, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, features=None):
+        """The same result as forward() in eval mode, built for the GPU: groups are gathered ROW-major ((M * nsample, C) — one
+        contiguous run per neighbour, lidar_group_rows_stack), the shared MLP is a chain of plain GEMMs with BatchNorm folded
+        into the weights and the shift + ReLU applied in place, and the max runs over contiguous blocks of nsample rows.  The
+        (M, C, nsample) tensor of the reference layout and the 1x1 convolution over its strided view never exist."""
+        from .....ext import pointnet2_stack_cuda as native
+        C.require_contiguous(xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt)
+        n_batch, n_query = xyz_batch_cnt.shape[0], new_xyz.shape[0]
+        feats = None if features is None else features.contiguous()
+        width = 0 if feats is None else feats.shape[1]
+        per_scale = []
+        idxs = self._ball_queries(xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt)
         src = None
         for k, grouper in enumerate(self.groupers):
             layers = self._folded_layers(k)
@@ -137,10 +144,42 @@ class StackSAModuleMSG(nn.Module):
             per_scale.append(rows.view(n_query, grouper.nsample, -1).amax(dim=1))
         return new_xyz, torch.cat(per_scale, dim=1)
 
+    def _fused_train_ready(self, xyz, new_xyz, features):
+        """inside sa_train.fused_sa_train(), in grad mode, with every scale qualifying (sa_train.module_supported), fp32 device
+        inputs and at least two (query, sample) rows per scale (BatchNorm's minimum)"""
+        from ..... import sa_train
+        if not (sa_train.fused_sa_train_enabled() and torch.is_grad_enabled() and xyz.is_cuda and xyz.dtype == torch.float32
+                and new_xyz.shape[0] * min(g.nsample for g in self.groupers) >= 2 and xyz.shape[0] >= 1):
+            return False
+        if features is None and not all(g.use_xyz for g in self.groupers):
+            return False
+        if features is not None and not (features.is_cuda and features.dtype == torch.float32 and features.dim() == 2
+                                         and features.shape[0] == xyz.shape[0]):
+            return False
+        width = 0 if features is None else features.shape[1]
+        if any(mlp[0].in_channels != (3 if g.use_xyz else 0) + width for mlp, g in zip(self.mlps, self.groupers)
+               if isinstance(mlp[0], nn.Conv2d)):
+            return False                                   # the stock route reports the mismatch as it always did
+        return new_xyz.is_cuda and new_xyz.dtype == torch.float32 and sa_train.module_supported(self)
+
+    def forward_train_fused(self, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, features=None):
+        """forward() in train mode on the fused kernels (sa_train.scale_forward per scale); the ball queries run once, with no
+        gradient, exactly as forward_inference issues them"""
+        from ..... import sa_train
+        C.require_contiguous(xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt)
+        feats = None if features is None else features.contiguous()
+        with torch.no_grad():
+            idxs = self._ball_queries(xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt)
+        per_scale = [sa_train.scale_forward(mlp, g.nsample, g.use_xyz, xyz, new_xyz, feats, idx, xyz_batch_cnt, new_xyz_batch_cnt)
+                     for g, mlp, idx in zip(self.groupers, self.mlps, idxs)]
+        return new_xyz, torch.cat(per_scale, dim=1)
+
     def forward(self, xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, features=None, empty_voxel_set_zeros=True):
         """xyz (N, 3), features (N, C), new_xyz (M, 3) -> (new_xyz, (M, sum of the scales' last MLP widths))"""
         if self._inference_ready(xyz) and new_xyz.shape[0] > 0:
             return self.forward_inference(xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, features)
+        if self._fused_train_ready(xyz, new_xyz, features):
+            return self.forward_train_fused(xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, features)
         per_scale = []
         for grouper, mlp in zip(self.groupers, self.mlps):
             grouped, _ = grouper(xyz, xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, features)      # (M, C, nsample)

@@ -193,13 +193,17 @@ class PVRCNNKitti(SECONDKitti):
         (head,) = self.backbone_head(bev)
         return bd["multi_scale_3d_features"], bev, head
 
-    def proposals(self, head):
+    def proposals(self, head, roi_pre=None, roi_thresh=None, roi_post=None):
         """proposal_layer (roi_head_template.py:45-99), all frames at once -> rois (B, post, 7) zero padded, roi_scores (raw
-        logits), roi_labels (1-based), num (B,)"""
+        logits), roi_labels (1-based), num (B,).  roi_pre / roi_thresh / roi_post: NMS_CONFIG's NMS_PRE_MAXSIZE / NMS_THRESH /
+        NMS_POST_MAXSIZE, by default the TEST values this model was built with (train_loss passes the TRAIN ones)."""
+        roi_pre = self.roi_pre if roi_pre is None else int(roi_pre)
+        roi_thresh = self.roi_thresh if roi_thresh is None else float(roi_thresh)
+        roi_post = self.roi_post if roi_post is None else int(roi_post)
         a, nc = self.num_anchor_per_loc, self.num_class
         cls = head[..., :a * nc].reshape(self.B, -1, nc)
         scores_all, labels_all = cls.max(dim=-1)                                   # raw logits: cls_preds_normalized is False
-        k = min(self.roi_pre, scores_all.shape[1])
+        k = min(roi_pre, scores_all.shape[1])
         if scores_all.is_cuda and anchor_post.topk_supported(scores_all.shape[1], k):
             # raw logits, no threshold: the exact device top-k with its signed key (csrc/topk.hip; ties by ascending anchor index)
             top_scores, top_idx, _ = anchor_post.topk_desc(scores_all.contiguous(), k, float("-inf"), score_max=float(np.finfo(np.float32).max))
@@ -208,8 +212,8 @@ class PVRCNNKitti(SECONDKitti):
         boxes = anchor_post.decode_topk(head, top_idx, self.anchors, a, box_off=a * nc, dir_off=a * (nc + 7),
                                         num_dir_bins=self.num_dir_bins, dir_offset=self.dir_offset,
                                         dir_limit_offset=self.dir_limit_offset)
-        post = min(self.roi_post, k)
-        keep, num = iou3d_nms_cuda.nms_batch(boxes, None, self.roi_thresh, max_keep=post)
+        post = min(roi_post, k)
+        keep, num = iou3d_nms_cuda.nms_batch(boxes, None, roi_thresh, max_keep=post)
         num = torch.clamp(num, max=post)
         valid = torch.arange(post, device=keep.device).unsqueeze(0) < num.unsqueeze(1)
         sel = torch.where(valid, keep[:, :post], torch.zeros_like(keep[:, :post])).clamp_(0, k - 1)
@@ -293,6 +297,12 @@ class PVRCNNKitti(SECONDKitti):
 
     def set_abstraction(self, points, sizes, kp, multi_scale, bev):
         """VoxelSetAbstraction.forward (:159-240) -> (point_features_before_fusion (B*K, 640), point_features (B*K, 128))"""
+        before = self.set_abstraction_features(points, sizes, kp, multi_scale, bev)
+        return before, self._dense["vsa_point_feature_fusion"](before)
+
+    def set_abstraction_features(self, points, sizes, kp, multi_scale, bev):
+        """VoxelSetAbstraction.forward up to the concatenation (:159-232) -> point_features_before_fusion (B*K, 640); in grad mode
+        differentiable with respect to the BEV map, the multi-scale features and the SA layers' parameters"""
         B, K = kp.shape[0], kp.shape[1]
         dev = kp.device
         feats = []
@@ -315,11 +325,11 @@ class PVRCNNKitti(SECONDKitti):
             _, f = layer(xyz=xyz.contiguous(), xyz_batch_cnt=cnt, new_xyz=new_xyz, new_xyz_batch_cnt=new_cnt,
                          features=t.features.contiguous())
             feats.append(f.view(B, K, -1))
-        before = torch.cat(feats, dim=2).view(B * K, -1)
-        return before, self._dense["vsa_point_feature_fusion"](before)
+        return torch.cat(feats, dim=2).view(B * K, -1)
 
-    def roi_head(self, rois, kp, point_features, point_scores):
-        """PVRCNNHead.forward, test mode (:145-177) -> rcnn_cls (B*R, 1), decoded boxes (B, R, 7)"""
+    def roi_grid_pool(self, rois, kp, point_features, point_scores):
+        """roi_grid_pool (pvrcnn_head.py:73-118) -> (B*R, 128 * 216) pooled features, channel-major per RoI as the shared FC reads
+        them; in grad mode differentiable with respect to point_features and point_scores"""
         B, R = rois.shape[0], rois.shape[1]
         dev = rois.device
         weighted = point_features * point_scores.view(-1, 1)                        # :88
@@ -330,7 +340,12 @@ class PVRCNNKitti(SECONDKitti):
         _, pooled = self.roi_grid_pool_layer(xyz=kp.reshape(-1, 3).contiguous(), xyz_batch_cnt=xyz_cnt, new_xyz=new_xyz,
                                              new_xyz_batch_cnt=new_cnt, features=weighted.contiguous())
         g3 = self.grid_size ** 3
-        pooled = pooled.view(B * R, g3, -1).permute(0, 2, 1).contiguous().view(B * R, -1)        # (B*R, C * 216): :150-153
+        return pooled.view(B * R, g3, -1).permute(0, 2, 1).contiguous().view(B * R, -1)          # (B*R, C * 216): :150-153
+
+    def roi_head(self, rois, kp, point_features, point_scores):
+        """PVRCNNHead.forward, test mode (:145-177) -> rcnn_cls (B*R, 1), decoded boxes (B, R, 7)"""
+        B, R = rois.shape[0], rois.shape[1]
+        pooled = self.roi_grid_pool(rois, kp, point_features, point_scores)
         shared = self._dense["shared_fc_layer"](pooled)
         rcnn_cls = self._dense["cls_layers"](shared)                                             # (B*R, 1)
         rcnn_reg = self._dense["reg_layers"](shared)                                             # (B*R, 7)
@@ -370,6 +385,62 @@ class PVRCNNKitti(SECONDKitti):
         sel = torch.where(valid, keep[:, :post], torch.zeros_like(keep[:, :post])).clamp_(0, k - 1)
         return (torch.gather(cand, 1, sel.unsqueeze(-1).expand(-1, -1, 7)), torch.gather(top, 1, sel),
                 torch.gather(roi_labels, 1, torch.gather(idx, 1, sel)), num)
+
+    # ---- training ------------------------------------------------------------------------------
+    def train_loss(self, points, point_offsets, sizes, gt_boxes, host_offsets=None, backbone="stock", sparse="stock",
+                   wgrad="library", deblock="library", sa="stock", target_config=None, fg_keys=None, draws=None, generator=None):
+        """One training forward of PV-RCNN-KITTI (pv_rcnn.py get_training_loss and the modules it calls) on this package's kernels
+        -> (rpn_cls, rpn_loc, rpn_dir, point_loss, rcnn_loss), differentiable with respect to every parameter; the step's loss is
+        their sum.  points / point_offsets / sizes as forward(); gt_boxes (B, M, 8) [box | class id].
+          1. SECOND's grad-mode trunk (SECONDKitti.train_trunk: backbone / sparse / wgrad / deblock as there) and rpn_loss;
+          2. proposals() without gradient at NMS_CONFIG.TRAIN (pre 9000, post 512, threshold 0.8), rcnn_targets (target_config,
+             fg_keys, draws, generator as there) and the keypoints (no gradient);
+          3. the set abstraction in grad mode and the fusion / point-head modules (train-mode BatchNorm1d); point_targets /
+             point_loss on the features before fusion; point_scores = sigmoid(point_cls_preds).max(-1), NOT detached
+             (point_head_simple.py:83-84, pvrcnn_head.py:91);
+          4. RoI-grid pooling on the sampled rois, shared_fc_layer / cls_layers / reg_layers as modules (Dropout live), rcnn_loss.
+        sa: "stock" (the StackSAModuleMSG modules as torch runs them: (M, C, nsample) groups, Conv2d / BatchNorm2d / ReLU, and the
+        grouping gradient's float atomicAdd) or "fused" (sa_train.fused_sa_train: DESIGN §3.31).
+        Host synchronisations: those of the trunk.  Not bitwise reproducible as a whole (library GEMMs, the index_put gradient of
+        bilinear_bev): DESIGN §3.31."""
+        from . import sa_train
+        err = roi_loss._lib.LidarHipError
+        if not self.training:
+            raise err("PVRCNNKitti.train_loss needs train mode (call .train() first)")
+        if sa not in ("stock", "fused"):
+            raise err(f"PVRCNNKitti.train_loss: sa must be 'stock' or 'fused', got {sa!r}")
+        head, multi_scale, bev = self.train_trunk(points, point_offsets, host_offsets, backbone, sparse, wgrad, deblock,
+                                                  "PVRCNNKitti.train_loss")
+        rpn_cls, rpn_loc, rpn_dir = self.rpn_loss(head, gt_boxes)
+        with torch.no_grad():
+            # the three head outputs in the merged layout proposals() reads: (B, locations, [cls | box | dir] of the location's anchors)
+            merged = torch.cat([t.reshape(self.B, -1, t.shape[-1] * self.num_anchor_per_loc) for t in head], dim=-1).contiguous()
+            rois, roi_scores, roi_labels, _, _ = self.proposals(merged, roi_pre=9000, roi_thresh=0.8, roi_post=512)
+            targets = self.rcnn_targets(rois, roi_scores, roi_labels, gt_boxes, target_config=target_config, fg_keys=fg_keys,
+                                        draws=draws, generator=generator)
+            kp = self.keypoints(points, point_offsets, sizes)
+        with sa_train.fused_sa_train(sa == "fused"):
+            before = self.set_abstraction_features(points, sizes, kp, multi_scale, bev)
+            fused = self.vsa_point_feature_fusion(before)
+            point_cls_preds = self.point_cls_layers(before)                          # (B * K, 1)
+            point_loss, _ = self.point_loss(point_cls_preds, self.point_targets(kp, gt_boxes))
+            point_scores = torch.sigmoid(point_cls_preds).max(dim=-1)[0]
+            pooled = self.roi_grid_pool(targets["rois"], kp, fused, point_scores)
+        shared = self.shared_fc_layer(pooled.unsqueeze(-1))                          # Conv1d stacks over (rows, C, 1): :150-160
+        rcnn_cls = self.cls_layers(shared).transpose(1, 2).contiguous().squeeze(dim=1)
+        rcnn_reg = self.reg_layers(shared).transpose(1, 2).contiguous().squeeze(dim=1)
+        rcnn_loss, _ = self.rcnn_loss(rcnn_cls, rcnn_reg, targets)
+        return rpn_cls, rpn_loc, rpn_dir, point_loss, rcnn_loss
+
+    def train_step(self, points, point_offsets, sizes, gt_boxes, optimizer, **train_loss_kwargs):
+        """One training iteration as PointPillarKITTI.train_step runs it, with optimizer = optim.AdamOneCycle(self, ...): zero_grad,
+        train_loss, backward of the sum of its five terms, optimizer.step().  -> (rpn_cls, rpn_loc, rpn_dir, point_loss, rcnn_loss,
+        total_norm), detached device tensors; total_norm is the gradient norm before clipping."""
+        optimizer.zero_grad()
+        losses = self.train_loss(points, point_offsets, sizes, gt_boxes, **train_loss_kwargs)
+        sum(losses).backward()
+        total_norm = optimizer.step()
+        return (*[t.detach() for t in losses], total_norm)
 
     @torch.no_grad()
     def forward(self, points, point_offsets, sizes):

@@ -108,14 +108,21 @@ class SECONDKitti(PointPillarKITTI):
         Host synchronisations: the voxel total is read back once (the sparse stack needs exact row counts), and the exact rulebook
         path reads one output-site count back per strided convolution (4 in VoxelBackBone8x).  The step is therefore not
         graph-capturable."""
+        head, _, _ = self.train_trunk(points, point_offsets, host_offsets, backbone, sparse, wgrad, deblock, "SECONDKitti.train_loss")
+        return self.rpn_loss(head, gt_boxes)
+
+    def train_trunk(self, points, point_offsets, host_offsets=None, backbone="stock", sparse="stock", wgrad="library",
+                    deblock="library", who="SECONDKitti.train_trunk"):
+        """train_loss() up to the heads -> (head outputs (cls, box, dirs), the sparse backbone's multi-scale tensors, the BEV map):
+        what a second stage (PVRCNNKitti.train_loss) reads beside the RPN loss.  Arguments as train_loss()."""
         err = pillar_ops._lib.LidarHipError
         if not self.training:
-            raise err("SECONDKitti.train_loss needs train mode (call .train() first)")
+            raise err(f"{who} needs train mode (call .train() first)")
         if backbone not in ("stock", "fused"):
-            raise err(f"SECONDKitti.train_loss: backbone must be 'stock' or 'fused', got {backbone!r}")
-        _check_sparse(sparse, "SECONDKitti.train_loss")
-        _check_wgrad(wgrad, "SECONDKitti.train_loss")
-        _check_deblock(deblock, "SECONDKitti.train_loss")
+            raise err(f"{who}: backbone must be 'stock' or 'fused', got {backbone!r}")
+        _check_sparse(sparse, who)
+        _check_wgrad(wgrad, who)
+        _check_deblock(deblock, who)
         with torch.no_grad():   # fresh voxel buffers: the first sparse layer's backward reads the features after the next step may have voxelised
             vox = self.voxelizer(points, point_offsets, self.n_max, compact=True, host_offsets=host_offsets)
             total = int(vox["voxel_offsets"][self.B])           # one read-back: exact row counts for the sparse stack
@@ -128,4 +135,4 @@ class SECONDKitti(PointPillarKITTI):
             head = self.backbone_head_stock(canvas)
         else:
             head = self.backbone_head_train(canvas, wgrad, deblock)
-        return self.rpn_loss(head, gt_boxes)
+        return head, bd["multi_scale_3d_features"], canvas

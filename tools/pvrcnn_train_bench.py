@@ -1,0 +1,127 @@
+"""Times one PV-RCNN-KITTI training iteration (PVRCNNKitti.train_step: the SECOND trunk, proposals, RoI targets, keypoints, set
+abstraction, point head, RoI-grid pooling, RoI head, the five losses, backward, the fused optimiser step) on synthetic 64-beam
+frames with the set abstraction on the stock modules (sa="stock") or on the fused train-mode kernels (sa="fused").
+
+The two configurations alternate: every round starts one child process per configuration, each under its own time limit (--limit
+seconds); the parent never opens the GPU, runs the children one after the other and stops at the first one that fails or
+overruns.  A child builds the model, warms up, and reports ms per step from a host clock around one window of `steps` iterations
+that ends in a device synchronise (the default of 8 steps is 0.7 - 1.5 s), the peak allocated memory, and the forward time of the set
+abstraction (VoxelSetAbstraction + RoI-grid pooling, device events) with its share of the step; its backward time is not measured.
+One JSON line with the best and all rounds.
+
+Usage: python tools/pvrcnn_train_bench.py [--batch 8] [--steps 8] [--warmup 3] [--rounds 3] [--limit 240]
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def worker(args):
+    import numpy as np
+    import torch
+    from lidardetection_amd import optim, synth
+    from lidardetection_amd.pvrcnn import PVRCNNKitti
+    dev, B = "cuda:0", args.batch
+    sizes_tab = np.array([[3.9, 1.6, 1.56], [0.8, 0.6, 1.73], [1.76, 0.6, 1.73]], np.float32)
+    frames = [synth.cloud_ring(2000 + i) for i in range(B)]
+    n = min(len(f) for f in frames)
+    frames = [f[:n] for f in frames]                          # equal sizes: one furthest-point-sampling launch for all frames
+    pts = torch.from_numpy(np.concatenate(frames)).to(dev)
+    lens = np.cumsum([0] + [len(f) for f in frames])
+    offs = torch.tensor(lens, dtype=torch.int32, device=dev)
+    r = np.random.default_rng(0)
+    gt = np.zeros((B, 12, 8), np.float32)
+    for b in range(B):
+        k = 8
+        cls = r.integers(1, 4, k)
+        gt[b, :k, 0], gt[b, :k, 1], gt[b, :k, 2] = r.uniform(5, 60, k), r.uniform(-30, 30, k), r.uniform(-1.5, -0.5, k)
+        gt[b, :k, 3:6] = sizes_tab[cls - 1] * r.uniform(0.9, 1.1, (k, 1))
+        gt[b, :k, 6], gt[b, :k, 7] = r.uniform(-np.pi, np.pi, k), cls
+    gt = torch.from_numpy(gt).to(dev)
+    torch.manual_seed(0)
+    model = PVRCNNKitti(batch_size=B, device=dev).train()
+    opt = optim.AdamOneCycle(model, wd=0.01, max_grad_norm=10.0)
+    opt.lr, opt.mom = optim.one_cycle(0, 100)
+    sizes = [n] * B
+    spans = []
+
+    def timed_stage(fn):
+        def run(*a, **k):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            out = fn(*a, **k)
+            e1.record()
+            spans.append((e0, e1))
+            return out
+        return run
+    model.set_abstraction_features = timed_stage(model.set_abstraction_features)
+    model.roi_grid_pool = timed_stage(model.roi_grid_pool)
+
+    def step():
+        model.train_step(pts, offs, sizes, gt, opt, host_offsets=[int(v) for v in lens], sa=args.worker, sparse="fused",
+                         backbone="fused")
+
+    def timed(steps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            step()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / steps
+    timed(args.warmup)
+    torch.cuda.reset_peak_memory_stats()
+    spans.clear()
+    ms = timed(args.steps)
+    sa_ms = sum(a.elapsed_time(b) for a, b in spans) / args.steps
+    print(json.dumps({"ms_per_step": ms, "sa_forward_ms": sa_ms, "points_per_frame": n,
+                      "peak_allocated_gib": torch.cuda.max_memory_allocated() / 2 ** 30, "device": torch.cuda.get_device_name(0)}))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--steps", type=int, default=8)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--limit", type=float, default=240.0, help="time limit of one configuration's process, seconds")
+    ap.add_argument("--worker", choices=["stock", "fused"], help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    if args.worker:
+        return worker(args)
+    out = {"metric": "PV-RCNN-KITTI train_step, ms per step (host clock around one synchronised window per process)", "batch": args.batch,
+           "steps": args.steps, "warmup": args.warmup, "rounds": args.rounds, "configs": {sa: {"rounds": []} for sa in ("stock", "fused")}}
+    ok = True
+    for _ in range(args.rounds):                              # alternate, so that a drift of the machine hits both configurations
+        for sa in ("stock", "fused"):
+            cmd = [sys.executable, os.path.abspath(__file__), "--worker", sa, "--batch", str(args.batch), "--steps", str(args.steps),
+                   "--warmup", str(args.warmup)]
+            try:
+                res = subprocess.run(cmd, capture_output=True, text=True, timeout=args.limit)
+                err = None if res.returncode == 0 else {"error": f"exit status {res.returncode}", "stderr_tail": res.stderr[-2000:]}
+            except subprocess.TimeoutExpired:
+                err = {"error": f"no result within {args.limit} s"}
+            if err:                                           # nothing more is started on the device after a failure or an overrun
+                out["configs"][sa].update(err)
+                ok = False
+                break
+            out["configs"][sa]["rounds"].append(json.loads(res.stdout.strip().splitlines()[-1]))
+        if not ok:
+            break
+    for cfg in out["configs"].values():
+        if cfg["rounds"]:
+            best = min(cfg["rounds"], key=lambda r: r["ms_per_step"])
+            cfg.update(ms_per_step_best=best["ms_per_step"], ms_per_step_all_rounds=[r["ms_per_step"] for r in cfg["rounds"]],
+                       sa_forward_ms=best["sa_forward_ms"], sa_forward_share=best["sa_forward_ms"] / best["ms_per_step"],
+                       peak_allocated_gib=max(r["peak_allocated_gib"] for r in cfg["rounds"]))
+    print(json.dumps(out))
+    return 0 if ok else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
