@@ -28,23 +28,19 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _lib, wino, workspace
+from . import _lib, bn_train, wino, workspace
 from .bev_backbone import _cl, block_layer, parse_block
 
-_MAX_SEG = 4          # inputs of one fused call (csrc/bn_train.hip BT_MAX_SEG)
-_MAX_C = 1024         # channels of one input (BT_MAX_C)
+_MAX_SEG = 4          # inputs of one fused call (csrc/bn_train_dev.h BT_MAX_SEG)
+_MAX_C = bn_train.MAX_C
 
 
-# ------------------------------------------------------------------ fused train-mode BatchNorm2d + ReLU (csrc/bn_train.hip)
+# ------------------------------------------------------------------ fused train-mode BatchNorm2d + ReLU (csrc/bn_train.hip; what it
+# shares with the other fused BatchNorm routes is bn_train.py's)
 def bn_supported(bn, channels=None):
     """the fused kernels take this BatchNorm2d: affine, with running statistics and a numeric momentum (momentum=None's cumulative
     average stays on torch), C % 4 == 0 and 4 <= C <= 1024.  Pure host."""
-    if not isinstance(bn, nn.BatchNorm2d):
-        return False
-    c = bn.num_features if channels is None else int(channels)
-    return (bn.affine and bn.track_running_stats and bn.running_mean is not None and bn.num_batches_tracked is not None
-            and isinstance(bn.momentum, (int, float)) and not isinstance(bn.momentum, bool)
-            and c == bn.num_features and c % 4 == 0 and 4 <= c <= _MAX_C)
+    return bn_train.supported(bn, nn.BatchNorm2d, False, channels)
 
 
 def _segments(zs):
@@ -78,16 +74,12 @@ def bn_relu_forward(zs, gamma, beta, eps, out=None, out_offset=0):
     B, _, H, W = z0.shape
     out, out_offset = _lib.nhwc_out("bn_relu_forward", B, (H, W), ctot, z0.device, out, out_offset, sliced=True)
     y_ld = out.stride(3)
-    dev = z0.device
-    stats = torch.empty(2 * ctot, dtype=torch.float64, device=dev)
-    scale_shift = torch.empty(2 * ctot, dtype=torch.float32, device=dev)
-    batch_stats = torch.empty(3 * ctot, dtype=torch.float32, device=dev)
-    L = _lib.lib()
-    wsb = L.lidar_bn_relu_train_workspace_bytes(rows, ctot)
-    ws = workspace.get("bn_train", wsb, dev)
-    _lib.check(L.lidar_bn_relu_train_forward(n, ptrs, lds, offs, cs, rows, _lib.ptr(gamma), _lib.ptr(beta), float(eps), _lib.ptr(out),
-                                             y_ld, int(out_offset), _lib.ptr(stats), _lib.ptr(scale_shift), _lib.ptr(batch_stats),
-                                             _lib.ptr(ws), wsb, _lib.stream()), "lidar_bn_relu_train_forward")
+    stats, scale_shift, batch_stats = bn_train.alloc_stats(ctot, z0.device)
+    ws, wsb = bn_train.get_workspace("bn_train", z0.device, rows, ctot)
+    _lib.check(_lib.lib().lidar_bn_relu_train_forward(n, ptrs, lds, offs, cs, rows, _lib.ptr(gamma), _lib.ptr(beta), float(eps),
+                                                      _lib.ptr(out), y_ld, int(out_offset), _lib.ptr(stats), _lib.ptr(scale_shift),
+                                                      _lib.ptr(batch_stats), _lib.ptr(ws), wsb, _lib.stream()),
+               "lidar_bn_relu_train_forward")
     return out, stats, scale_shift, batch_stats
 
 
@@ -107,12 +99,11 @@ def bn_relu_backward(zs, grad_y, gamma, stats, scale_shift, grad_offset=0):
     d_gamma = torch.empty(ctot, dtype=torch.float32, device=gamma.device)
     d_beta = torch.empty(ctot, dtype=torch.float32, device=gamma.device)
     dptrs = (C.c_void_p * n)(*[d.data_ptr() for d in dzs])
-    L = _lib.lib()
-    wsb = L.lidar_bn_relu_train_workspace_bytes(rows, ctot)
-    ws = workspace.get("bn_train", wsb, gamma.device)
-    _lib.check(L.lidar_bn_relu_train_backward(n, ptrs, lds, offs, cs, rows, _lib.ptr(grad_y), g_ld, int(grad_offset), _lib.ptr(gamma),
-                                              _lib.ptr(stats), _lib.ptr(scale_shift), dptrs, _lib.ptr(d_gamma), _lib.ptr(d_beta),
-                                              _lib.ptr(ws), wsb, _lib.stream()), "lidar_bn_relu_train_backward")
+    ws, wsb = bn_train.get_workspace("bn_train", gamma.device, rows, ctot)
+    _lib.check(_lib.lib().lidar_bn_relu_train_backward(n, ptrs, lds, offs, cs, rows, _lib.ptr(grad_y), g_ld, int(grad_offset),
+                                                       _lib.ptr(gamma), _lib.ptr(stats), _lib.ptr(scale_shift), dptrs, _lib.ptr(d_gamma),
+                                                       _lib.ptr(d_beta), _lib.ptr(ws), wsb, _lib.stream()),
+               "lidar_bn_relu_train_backward")
     return dzs, d_gamma, d_beta
 
 
@@ -153,23 +144,17 @@ def bn_relu_train(z, bn):
     else:
         gamma, beta = torch.cat([b.weight for b in bns]), torch.cat([b.bias for b in bns])
     y, batch_stats = _BNReLUTrain.apply(float(bns[0].eps), gamma, beta, *zs)
-    ctot = gamma.numel()
-    with torch.no_grad():   # BatchNorm2d's running update (momentum form), on the device
-        off = 0
-        for b in bns:
-            c, m = b.num_features, float(b.momentum)
-            b.running_mean.mul_(1.0 - m).add_(batch_stats[off:off + c], alpha=m)
-            b.running_var.mul_(1.0 - m).add_(batch_stats[2 * ctot + off:2 * ctot + off + c], alpha=m)
-            b.num_batches_tracked.add_(1)
-            off += c
+    off = 0
+    for b in bns:           # BatchNorm2d's running update (momentum form), on the device
+        bn_train.update_module(b, batch_stats, gamma.numel(), off)
+        off += b.num_features
     return y
 
 
 def bn_relu_train_rows(z, bn, residual=None):
     """bn_relu_train's form for an (N, C) feature matrix and a train-mode BatchNorm1d (sparse features): relu(bn(z)) or, with
     `residual`, relu(bn(z) + residual) on the same kernels with rows = N and row stride C (spconv.train.bn_relu_train)"""
-    from .spconv import train
-    return train.bn_relu_train(z, bn, residual)
+    return bn_train.bn_relu_rows_train(z, bn, residual)
 
 
 # ------------------------------------------------------------------ stride-1 3x3 convolution on the Winograd kernels

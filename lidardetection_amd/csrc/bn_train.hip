@@ -23,7 +23,8 @@
 // copy above; RES = false compiles to the code the plain entry points always ran.
 //
 // The segment tables, the thread layout, the statistics kernels (forward passes 1 and 2, backward pass 2) and the reduction are in
-// bn_train_dev.h, shared with csrc/sa_train.hip.
+// bn_train_dev.h, shared with csrc/sa_train.hip; so are the element math (y, delta, the fp64 dz) and the launch helpers; the
+// reduction kernel is ordered_reduce.h's.  The four exported launchers are wrappers over bt_forward<RES> / bt_backward<RES>.
 #include "bn_train_dev.h"
 
 // forward pass 3: y = max(z scale + shift, 0) into channels [y_off + c0, + C) of the (rows, y_ld) output.  grid (nb, segments)
@@ -40,37 +41,10 @@ __global__ __launch_bounds__(256) void bt_apply_kernel(BtSegs segs, long long ro
     const long long step = (long long)nb * L.R;
     for (long long row = (long long)blockIdx.x * L.R + L.r; row < rows; row += step) {
         const float4 v = bt_ld4(src + row * sg.ld);
-        float4 o;
-        if constexpr (RES) {
-            const float4 r = bt_ld4(sg.r + 4 * L.q + row * sg.r_ld);
-            o.x = fmaxf(fmaf(v.x, sc.x, sh.x) + r.x, 0.f); o.y = fmaxf(fmaf(v.y, sc.y, sh.y) + r.y, 0.f);
-            o.z = fmaxf(fmaf(v.z, sc.z, sh.z) + r.z, 0.f); o.w = fmaxf(fmaf(v.w, sc.w, sh.w) + r.w, 0.f);
-        } else {
-            o.x = fmaxf(fmaf(v.x, sc.x, sh.x), 0.f); o.y = fmaxf(fmaf(v.y, sc.y, sh.y), 0.f);
-            o.z = fmaxf(fmaf(v.z, sc.z, sh.z), 0.f); o.w = fmaxf(fmaf(v.w, sc.w, sh.w), 0.f);
-        }
-        bt_st4(dst + row * (long long)y_ld, o);
+        float4 r;
+        if constexpr (RES) r = bt_ld4(sg.r + 4 * L.q + row * sg.r_ld);
+        bt_st4(dst + row * (long long)y_ld, bt_y4<RES>(v, sc, sh, r));
     }
-}
-
-__device__ __forceinline__ float bt_delta(float z, float g, float sc, float sh) {
-    return fmaxf(fmaf(z, sc, sh), 0.f) > 0.f ? g : 0.f;        // the forward's y, bit for bit
-}
-__device__ __forceinline__ float bt_delta_res(float z, float g, float sc, float sh, float r) {
-    return fmaxf(fmaf(z, sc, sh) + r, 0.f) > 0.f ? g : 0.f;    // the residual forward's y, bit for bit
-}
-// delta of one quad; rv is read only when RES
-template <bool RES>
-__device__ __forceinline__ float4 bt_delta4(const float4 &z, const float4 &g, const float4 &sc, const float4 &sh, const float4 &rv) {
-    float4 d;
-    if constexpr (RES) {
-        d.x = bt_delta_res(z.x, g.x, sc.x, sh.x, rv.x); d.y = bt_delta_res(z.y, g.y, sc.y, sh.y, rv.y);
-        d.z = bt_delta_res(z.z, g.z, sc.z, sh.z, rv.z); d.w = bt_delta_res(z.w, g.w, sc.w, sh.w, rv.w);
-    } else {
-        d.x = bt_delta(z.x, g.x, sc.x, sh.x); d.y = bt_delta(z.y, g.y, sc.y, sh.y);
-        d.z = bt_delta(z.z, g.z, sc.z, sh.z); d.w = bt_delta(z.w, g.w, sc.w, sh.w);
-    }
-    return d;
 }
 
 // backward pass 1: sum delta, sum delta z (fp64) per channel and block.  grid (nb, segments)
@@ -123,11 +97,7 @@ __global__ __launch_bounds__(256) void bt_bwd_apply_kernel(BtSegs segs, long lon
     if (!L.live) return;
     const int ct = segs.ctot, c = sg.c0 + 4 * L.q;
     const float4 sc = bt_ld4(scale_shift + c), sh = bt_ld4(scale_shift + ct + c);
-    double A[4], m1[4], m2[4], mu[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        A[k] = coef[c + k]; m1[k] = coef[ct + c + k]; m2[k] = coef[2 * ct + c + k]; mu[k] = coef[3 * ct + c + k];
-    }
+    const BtCoef4 k = bt_coef4(coef, ct, c);
     const float *zs = sg.x + sg.off + 4 * L.q, *gs = g + g_off + c;
     float *ds = sg.dx + sg.off + 4 * L.q;
     const long long step = (long long)nb * L.R;
@@ -136,17 +106,16 @@ __global__ __launch_bounds__(256) void bt_bwd_apply_kernel(BtSegs segs, long lon
         float4 rv;
         if constexpr (RES) rv = bt_ld4(sg.r + 4 * L.q + row * sg.r_ld);
         const float4 d = bt_delta4<RES>(z, gv, sc, sh, rv);
-        float4 o;
-        o.x = (float)(A[0] * ((double)d.x - m1[0] - ((double)z.x - mu[0]) * m2[0]));
-        o.y = (float)(A[1] * ((double)d.y - m1[1] - ((double)z.y - mu[1]) * m2[1]));
-        o.z = (float)(A[2] * ((double)d.z - m1[2] - ((double)z.z - mu[2]) * m2[2]));
-        o.w = (float)(A[3] * ((double)d.w - m1[3] - ((double)z.w - mu[3]) * m2[3]));
-        bt_st4(ds + row * sg.ld, o);
+        bt_st4(ds + row * sg.ld, bt_dz4(k, d, z));
         if constexpr (RES) bt_st4(sg.dr + 4 * L.q + row * sg.dr_ld, d);
     }
 }
 
 LIDAR_EXPORT size_t lidar_bn_relu_train_workspace_bytes(long long rows, int channels) { return bt_workspace_bytes(rows, channels); }
+
+static bool bt_seg_ok(const void *x, int C, int ld, int off) {
+    return bt_aligned(x) && C >= 4 && C <= BT_MAX_C && C % 4 == 0 && ld % 4 == 0 && off % 4 == 0 && off >= 0 && off + C <= ld;
+}
 
 // host segment tables -> BtSegs; LIDAR_ERR_ARG on anything the kernels do not take
 static int bt_segs(int nseg, void *const *x, void *const *dx, const int *x_ld, const int *x_off, const int *seg_C, BtSegs &S) {
@@ -154,20 +123,56 @@ static int bt_segs(int nseg, void *const *x, void *const *dx, const int *x_ld, c
     S.n = nseg;
     S.ctot = 0;
     for (int i = 0; i < nseg; ++i) {
-        const int C = seg_C[i], ld = x_ld[i], off = x_off[i];
-        if (!bt_aligned(x[i]) || C < 4 || C > BT_MAX_C || C % 4 || ld % 4 || off % 4 || off < 0 || off + C > ld) return LIDAR_ERR_ARG;
-        if (dx && !bt_aligned(dx[i])) return LIDAR_ERR_ARG;
-        S.s[i].x = (const float *)x[i];
-        S.s[i].dx = dx ? (float *)dx[i] : nullptr;
-        S.s[i].C = C; S.s[i].ld = ld; S.s[i].off = off; S.s[i].c0 = S.ctot;
-        S.s[i].r = nullptr; S.s[i].dr = nullptr; S.s[i].r_ld = S.s[i].dr_ld = 0;
-        S.ctot += C;
+        if (!bt_seg_ok(x[i], seg_C[i], x_ld[i], x_off[i]) || (dx && !bt_aligned(dx[i]))) return LIDAR_ERR_ARG;
+        S.s[i] = BtSeg{(const float *)x[i], dx ? (float *)dx[i] : nullptr, seg_C[i], x_ld[i], x_off[i], S.ctot, nullptr, nullptr, 0, 0};
+        S.ctot += seg_C[i];
     }
+    return LIDAR_OK;
+}
+
+// the residual form's table: one (rows, C) map; z / dz at x_ld, r at r_ld, d_r at dr_ld (dx, dr: the backward's outputs, or null)
+static int bt_res_seg(const float *x, float *dx, int x_ld, const float *r, float *dr, int r_ld, int dr_ld, int C, BtSegs &S) {
+    if (!bt_seg_ok(x, C, x_ld, 0) || !bt_aligned(r) || r_ld % 4 || r_ld < C) return LIDAR_ERR_ARG;
+    if (dx && (!bt_aligned(dx) || !bt_aligned(dr) || dr_ld % 4 || dr_ld < C)) return LIDAR_ERR_ARG;
+    bt_one_seg(x, dx, C, x_ld, S);
+    S.s[0].r = r; S.s[0].dr = dr; S.s[0].r_ld = r_ld; S.s[0].dr_ld = dr_ld;
     return LIDAR_OK;
 }
 
 static bool bt_map_ok(const void *p, int ld, int off, int ctot) {
     return bt_aligned(p) && ld % 4 == 0 && off % 4 == 0 && off >= 0 && off + ctot <= ld;
+}
+
+// the forward of both forms on a checked table: stats -> reduce -> finalize -> apply
+template <bool RES>
+static int bt_forward(const char *who, const BtSegs &S, long long rows, const float *gamma, const float *beta, float eps, float *y,
+                      int y_ld, int y_off, double *stats, float *scale_shift, float *batch_stats, void *ws, size_t ws_bytes,
+                      void *stream) {
+    if (rows < 2 || !gamma || !beta || !stats || !bt_aligned(scale_shift) || !batch_stats || !bt_aligned(ws) || !(eps >= 0.f))
+        return LIDAR_ERR_ARG;
+    if (!bt_map_ok(y, y_ld, y_off, S.ctot)) return LIDAR_ERR_ARG;
+    if (ws_bytes < bt_workspace_bytes(rows, S.ctot)) return LIDAR_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    const int nb = bt_launch_stats(S, rows, gamma, beta, eps, stats, scale_shift, batch_stats, ws, s);
+    hipLaunchKernelGGL(bt_apply_kernel<RES>, dim3(nb, S.n), dim3(256), 0, s, S, rows, nb, scale_shift, y, y_ld, y_off);
+    return lidar_check_launch(who);
+}
+
+// the backward of both forms on a checked table (dx, and dr when RES, set): stats -> reduce -> backward finalize -> apply
+template <bool RES>
+static int bt_backward(const char *who, const BtSegs &S, long long rows, const float *grad_y, int g_ld, int g_off, const float *gamma,
+                       const double *stats, const float *scale_shift, float *d_gamma, float *d_beta, void *ws, size_t ws_bytes,
+                       void *stream) {
+    if (rows < 2 || !gamma || !stats || !bt_aligned(scale_shift) || !d_gamma || !d_beta || !bt_aligned(ws)) return LIDAR_ERR_ARG;
+    if (!bt_map_ok(grad_y, g_ld, g_off, S.ctot)) return LIDAR_ERR_ARG;
+    if (ws_bytes < bt_workspace_bytes(rows, S.ctot)) return LIDAR_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    const int nb = bt_blocks(rows);
+    const BtWs W = bt_ws_split(ws, S.ctot, nb);
+    hipLaunchKernelGGL(bt_bwd_stats_kernel<RES>, dim3(nb, S.n), dim3(256), 0, s, S, rows, nb, scale_shift, grad_y, g_ld, g_off, W.part);
+    bt_launch_bwd_finalize(W, S.ctot, nb, rows, gamma, stats, d_gamma, d_beta, s);
+    hipLaunchKernelGGL(bt_bwd_apply_kernel<RES>, dim3(nb, S.n), dim3(256), 0, s, S, rows, nb, scale_shift, W.coef, grad_y, g_ld, g_off);
+    return lidar_check_launch(who);
 }
 
 LIDAR_EXPORT int lidar_bn_relu_train_forward(int nseg, void *const *x, const int *x_ld, const int *x_off, const int *seg_C,
@@ -176,19 +181,8 @@ LIDAR_EXPORT int lidar_bn_relu_train_forward(int nseg, void *const *x, const int
                                              size_t ws_bytes, void *stream) {
     BtSegs S;
     if (bt_segs(nseg, x, nullptr, x_ld, x_off, seg_C, S) != LIDAR_OK) return LIDAR_ERR_ARG;
-    if (rows < 2 || !gamma || !beta || !stats || !bt_aligned(scale_shift) || !batch_stats || !bt_aligned(ws) || !(eps >= 0.f))
-        return LIDAR_ERR_ARG;
-    if (!bt_map_ok(y, y_ld, y_off, S.ctot)) return LIDAR_ERR_ARG;
-    if (ws_bytes < lidar_bn_relu_train_workspace_bytes(rows, S.ctot)) return LIDAR_ERR_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    const int nb = bt_blocks(rows);
-    double *part = (double *)ws, *tot = part + (size_t)2 * S.ctot * nb;
-    hipLaunchKernelGGL(bt_stats_kernel, dim3(nb, nseg), dim3(256), 0, s, S, rows, nb, part);
-    hipLaunchKernelGGL(bt_reduce_kernel, dim3(2 * S.ctot), dim3(256), 0, s, part, nb, tot);
-    hipLaunchKernelGGL(bt_finalize_kernel, dim3(divup(S.ctot, 256)), dim3(256), 0, s, tot, S.ctot, rows, gamma, beta, eps, stats,
-                       scale_shift, batch_stats);
-    hipLaunchKernelGGL(bt_apply_kernel<false>, dim3(nb, nseg), dim3(256), 0, s, S, rows, nb, scale_shift, y, y_ld, y_off);
-    return lidar_check_launch("lidar_bn_relu_train_forward");
+    return bt_forward<false>("lidar_bn_relu_train_forward", S, rows, gamma, beta, eps, y, y_ld, y_off, stats, scale_shift, batch_stats,
+                             ws, ws_bytes, stream);
 }
 
 LIDAR_EXPORT int lidar_bn_relu_train_backward(int nseg, void *const *x, const int *x_ld, const int *x_off, const int *seg_C,
@@ -197,50 +191,18 @@ LIDAR_EXPORT int lidar_bn_relu_train_backward(int nseg, void *const *x, const in
                                               float *d_beta, void *ws, size_t ws_bytes, void *stream) {
     BtSegs S;
     if (!dx || bt_segs(nseg, x, dx, x_ld, x_off, seg_C, S) != LIDAR_OK) return LIDAR_ERR_ARG;
-    if (rows < 2 || !gamma || !stats || !bt_aligned(scale_shift) || !d_gamma || !d_beta || !bt_aligned(ws)) return LIDAR_ERR_ARG;
-    if (!bt_map_ok(grad_y, g_ld, g_off, S.ctot)) return LIDAR_ERR_ARG;
-    if (ws_bytes < lidar_bn_relu_train_workspace_bytes(rows, S.ctot)) return LIDAR_ERR_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    const int nb = bt_blocks(rows);
-    double *part = (double *)ws, *tot = part + (size_t)2 * S.ctot * nb;
-    double *coef = tot + 2 * S.ctot;
-    hipLaunchKernelGGL(bt_bwd_stats_kernel<false>, dim3(nb, nseg), dim3(256), 0, s, S, rows, nb, scale_shift, grad_y, g_ld, g_off, part);
-    hipLaunchKernelGGL(bt_reduce_kernel, dim3(2 * S.ctot), dim3(256), 0, s, part, nb, tot);
-    hipLaunchKernelGGL(bt_bwd_finalize_kernel, dim3(divup(S.ctot, 256)), dim3(256), 0, s, tot, S.ctot, rows, gamma, stats, coef,
-                       d_gamma, d_beta);
-    hipLaunchKernelGGL(bt_bwd_apply_kernel<false>, dim3(nb, nseg), dim3(256), 0, s, S, rows, nb, scale_shift, coef, grad_y, g_ld, g_off);
-    return lidar_check_launch("lidar_bn_relu_train_backward");
+    return bt_backward<false>("lidar_bn_relu_train_backward", S, rows, grad_y, g_ld, g_off, gamma, stats, scale_shift, d_gamma, d_beta,
+                              ws, ws_bytes, stream);
 }
 
-// ---- the residual form: y = max(BN(z) + r, 0) on one (rows, C) map; z / dz at x_ld, r at r_ld, d_r at dr_ld, y at y_ld, grad_y at g_ld
-static int bt_res_seg(const float *x, float *dx, int x_ld, const float *r, float *dr, int r_ld, int dr_ld, int C, BtSegs &S) {
-    void *xs[1] = {(void *)x}, *dxs[1] = {(void *)dx};
-    const int off = 0;
-    if (bt_segs(1, xs, dx ? dxs : nullptr, &x_ld, &off, &C, S) != LIDAR_OK) return LIDAR_ERR_ARG;
-    if (!bt_aligned(r) || r_ld % 4 || r_ld < C) return LIDAR_ERR_ARG;
-    if (dx && (!bt_aligned(dr) || dr_ld % 4 || dr_ld < C)) return LIDAR_ERR_ARG;
-    S.s[0].r = r; S.s[0].dr = dr; S.s[0].r_ld = r_ld; S.s[0].dr_ld = dr_ld;
-    return LIDAR_OK;
-}
-
+// ---- the residual form: y = max(BN(z) + r, 0) on one (rows, C) map; y at y_ld, grad_y at g_ld
 LIDAR_EXPORT int lidar_bn_add_relu_train_forward(const float *x, int x_ld, const float *r, int r_ld, int channels, long long rows,
                                                  const float *gamma, const float *beta, float eps, float *y, int y_ld, double *stats,
                                                  float *scale_shift, float *batch_stats, void *ws, size_t ws_bytes, void *stream) {
     BtSegs S;
     if (bt_res_seg(x, nullptr, x_ld, r, nullptr, r_ld, 0, channels, S) != LIDAR_OK) return LIDAR_ERR_ARG;
-    if (rows < 2 || !gamma || !beta || !stats || !bt_aligned(scale_shift) || !batch_stats || !bt_aligned(ws) || !(eps >= 0.f))
-        return LIDAR_ERR_ARG;
-    if (!bt_map_ok(y, y_ld, 0, S.ctot)) return LIDAR_ERR_ARG;
-    if (ws_bytes < lidar_bn_relu_train_workspace_bytes(rows, S.ctot)) return LIDAR_ERR_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    const int nb = bt_blocks(rows);
-    double *part = (double *)ws, *tot = part + (size_t)2 * S.ctot * nb;
-    hipLaunchKernelGGL(bt_stats_kernel, dim3(nb, 1), dim3(256), 0, s, S, rows, nb, part);
-    hipLaunchKernelGGL(bt_reduce_kernel, dim3(2 * S.ctot), dim3(256), 0, s, part, nb, tot);
-    hipLaunchKernelGGL(bt_finalize_kernel, dim3(divup(S.ctot, 256)), dim3(256), 0, s, tot, S.ctot, rows, gamma, beta, eps, stats,
-                       scale_shift, batch_stats);
-    hipLaunchKernelGGL(bt_apply_kernel<true>, dim3(nb, 1), dim3(256), 0, s, S, rows, nb, scale_shift, y, y_ld, 0);
-    return lidar_check_launch("lidar_bn_add_relu_train_forward");
+    return bt_forward<true>("lidar_bn_add_relu_train_forward", S, rows, gamma, beta, eps, y, y_ld, 0, stats, scale_shift, batch_stats, ws,
+                            ws_bytes, stream);
 }
 
 LIDAR_EXPORT int lidar_bn_add_relu_train_backward(const float *x, int x_ld, const float *r, int r_ld, int channels, long long rows,
@@ -249,17 +211,7 @@ LIDAR_EXPORT int lidar_bn_add_relu_train_backward(const float *x, int x_ld, cons
                                                   float *d_beta, void *ws, size_t ws_bytes, void *stream) {
     BtSegs S;
     if (!dx || !d_r || bt_res_seg(x, dx, x_ld, r, d_r, r_ld, dr_ld, channels, S) != LIDAR_OK) return LIDAR_ERR_ARG;
-    if (rows < 2 || !gamma || !stats || !bt_aligned(scale_shift) || !d_gamma || !d_beta || !bt_aligned(ws)) return LIDAR_ERR_ARG;
-    if (!bt_map_ok(grad_y, g_ld, 0, S.ctot)) return LIDAR_ERR_ARG;
-    if (ws_bytes < lidar_bn_relu_train_workspace_bytes(rows, S.ctot)) return LIDAR_ERR_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    const int nb = bt_blocks(rows);
-    double *part = (double *)ws, *tot = part + (size_t)2 * S.ctot * nb;
-    double *coef = tot + 2 * S.ctot;
-    hipLaunchKernelGGL(bt_bwd_stats_kernel<true>, dim3(nb, 1), dim3(256), 0, s, S, rows, nb, scale_shift, grad_y, g_ld, 0, part);
-    hipLaunchKernelGGL(bt_reduce_kernel, dim3(2 * S.ctot), dim3(256), 0, s, part, nb, tot);
-    hipLaunchKernelGGL(bt_bwd_finalize_kernel, dim3(divup(S.ctot, 256)), dim3(256), 0, s, tot, S.ctot, rows, gamma, stats, coef,
-                       d_gamma, d_beta);
-    hipLaunchKernelGGL(bt_bwd_apply_kernel<true>, dim3(nb, 1), dim3(256), 0, s, S, rows, nb, scale_shift, coef, grad_y, g_ld, 0);
-    return lidar_check_launch("lidar_bn_add_relu_train_backward");
+    return bt_backward<true>("lidar_bn_add_relu_train_backward", S, rows, grad_y, g_ld, 0, gamma, stats, scale_shift, d_gamma, d_beta, ws,
+                             ws_bytes, stream);
 }
+

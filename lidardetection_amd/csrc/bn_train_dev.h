@@ -2,8 +2,12 @@
 // sparse feature rows; csrc/sa_train.hip: BatchNorm + ReLU + max over a ball's samples): the segment tables, the thread layout, the
 // fp64 per-channel sums with their fixed-order reduction, and the two finalize kernels.  One copy, so the statistics of every
 // train-mode BatchNorm here are the same arithmetic.  The kernels are static: each including file owns its copy.
+// Also here, one copy each: the element math (y of a quad with and without a residual, the backward's delta built on
+// that very y, a quad's fp64 backward coefficients and dz), and the host helpers every launcher of the family calls (the one-segment
+// table, the workspace split, "stats -> reduce -> finalize" and "reduce -> backward finalize").  The fixed-order reduce kernel itself
+// is ordered_reduce.h's, shared with csrc/pfn_train.hip.
 #pragma once
-#include "common.h"
+#include "ordered_reduce.h"
 
 #define BT_MAX_SEG 4
 #define BT_MAX_C 1024              // channels of one segment: a 256-thread block covers a row's C / 4 quads at once
@@ -39,6 +43,46 @@ __device__ __forceinline__ BtLane bt_lane(int C) {
 
 __device__ __forceinline__ float4 bt_ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
 __device__ __forceinline__ void bt_st4(float *p, float4 v) { *reinterpret_cast<float4 *>(p) = v; }
+
+// ---- element math.  The backward's ReLU mask is recomputed from z through the helper the forward writes y with: the same bits by
+// construction.  The explicit fmaf is the only fused operation (the build uses -ffp-contract=off).
+__device__ __forceinline__ float bt_y(float z, float sc, float sh) { return fmaxf(fmaf(z, sc, sh), 0.f); }
+__device__ __forceinline__ float bt_y(float z, float sc, float sh, float r) { return fmaxf(fmaf(z, sc, sh) + r, 0.f); }
+// y of one quad; r is read only when RES
+template <bool RES = false>
+__device__ __forceinline__ float4 bt_y4(const float4 &z, const float4 &sc, const float4 &sh, const float4 &r = float4()) {
+    if constexpr (RES)
+        return make_float4(bt_y(z.x, sc.x, sh.x, r.x), bt_y(z.y, sc.y, sh.y, r.y), bt_y(z.z, sc.z, sh.z, r.z), bt_y(z.w, sc.w, sh.w, r.w));
+    else
+        return make_float4(bt_y(z.x, sc.x, sh.x), bt_y(z.y, sc.y, sh.y), bt_y(z.z, sc.z, sh.z), bt_y(z.w, sc.w, sh.w));
+}
+// delta = g where the forward's y is positive
+__device__ __forceinline__ float bt_delta(float y, float g) { return y > 0.f ? g : 0.f; }
+template <bool RES = false>
+__device__ __forceinline__ float4 bt_delta4(const float4 &z, const float4 &g, const float4 &sc, const float4 &sh,
+                                            const float4 &r = float4()) {
+    const float4 y = bt_y4<RES>(z, sc, sh, r);
+    return make_float4(bt_delta(y.x, g.x), bt_delta(y.y, g.y), bt_delta(y.z, g.z), bt_delta(y.w, g.w));
+}
+
+// the fp64 backward coefficients of the quad at channel c (bt_bwd_finalize_kernel's coef) and dz = A (delta - m1 - (z - mu) m2)
+struct BtCoef4 {
+    double A[4], m1[4], m2[4], mu[4];
+};
+__device__ __forceinline__ BtCoef4 bt_coef4(const double *__restrict__ coef, int ctot, int c) {
+    BtCoef4 k;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        k.A[i] = coef[c + i]; k.m1[i] = coef[ctot + c + i]; k.m2[i] = coef[2 * ctot + c + i]; k.mu[i] = coef[3 * ctot + c + i];
+    }
+    return k;
+}
+__device__ __forceinline__ float4 bt_dz4(const BtCoef4 &k, const float4 &d, const float4 &z) {
+    return make_float4((float)(k.A[0] * ((double)d.x - k.m1[0] - ((double)z.x - k.mu[0]) * k.m2[0])),
+                       (float)(k.A[1] * ((double)d.y - k.m1[1] - ((double)z.y - k.mu[1]) * k.m2[1])),
+                       (float)(k.A[2] * ((double)d.z - k.m1[2] - ((double)z.z - k.mu[2]) * k.m2[2])),
+                       (float)(k.A[3] * ((double)d.w - k.m1[3] - ((double)z.w - k.mu[3]) * k.m2[3])));
+}
 
 // the per-block sums of thread (r, q) -> part[(which * ctot + channel) * nb + block], summed over r in a fixed order
 __device__ __forceinline__ void bt_block_partials(const double (&a)[8], const BtLane &L, int C, int c0, int ctot, int nb,
@@ -82,21 +126,6 @@ static __global__ __launch_bounds__(256) void bt_stats_kernel(BtSegs segs, long 
         }
     }
     bt_block_partials(a, L, sg.C, sg.c0, segs.ctot, nb, part);
-}
-
-// rows of `part` ([entries][nparts]) -> tot[entry]; one block per entry, fixed summation order
-static __global__ __launch_bounds__(256) void bt_reduce_kernel(const double *__restrict__ part, int nparts, double *__restrict__ tot) {
-    __shared__ double s[256];
-    const double *row = part + (size_t)blockIdx.x * nparts;
-    double a = 0.0;
-    for (int b = threadIdx.x; b < nparts; b += 256) a += row[b];
-    s[threadIdx.x] = a;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-        if ((int)threadIdx.x < h) s[threadIdx.x] += s[threadIdx.x + h];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) tot[blockIdx.x] = s[0];
 }
 
 // forward pass 2 (thread = channel): mean, biased variance, 1 / sigma in fp64; fp32 scale / shift; the running-statistics inputs
@@ -151,3 +180,39 @@ static size_t bt_workspace_bytes(long long rows, int channels) {
 }
 
 static bool bt_aligned(const void *p) { return p && ((uintptr_t)p & 15) == 0; }
+
+// the table of one (rows, C) matrix at row stride ld (dx: its gradient, or null), unchecked
+static void bt_one_seg(const float *x, float *dx, int C, int ld, BtSegs &S) {
+    S.n = 1;
+    S.ctot = C;
+    S.s[0] = BtSeg{x, dx, C, ld, 0, 0, nullptr, nullptr, 0, 0};
+}
+
+// the workspace of bt_workspace_bytes(rows, ctot), nb = bt_blocks(rows)
+struct BtWs {
+    double *part, *tot, *coef;
+};
+static BtWs bt_ws_split(void *ws, int ctot, int nb) {
+    double *part = (double *)ws, *tot = part + (size_t)2 * ctot * nb;
+    return BtWs{part, tot, tot + 2 * ctot};
+}
+
+// forward passes 1 and 2: stats -> reduce -> finalize over the segments' rows; -> nb, the blocks per segment of the row passes
+static int bt_launch_stats(const BtSegs &S, long long rows, const float *gamma, const float *beta, float eps, double *stats,
+                           float *scale_shift, float *batch_stats, void *ws, hipStream_t s) {
+    const int nb = bt_blocks(rows);
+    const BtWs W = bt_ws_split(ws, S.ctot, nb);
+    hipLaunchKernelGGL(bt_stats_kernel, dim3(nb, S.n), dim3(256), 0, s, S, rows, nb, W.part);
+    hipLaunchKernelGGL(ordered_reduce_kernel, dim3(2 * S.ctot), dim3(256), 0, s, W.part, nb, W.tot);
+    hipLaunchKernelGGL(bt_finalize_kernel, dim3(divup(S.ctot, 256)), dim3(256), 0, s, W.tot, S.ctot, rows, gamma, beta, eps, stats,
+                       scale_shift, batch_stats);
+    return nb;
+}
+
+// backward pass 2: W.part's nb partials per entry -> reduce -> backward finalize (W.coef, d_gamma, d_beta)
+static void bt_launch_bwd_finalize(const BtWs &W, int ctot, int nb, long long rows, const float *gamma, const double *stats,
+                                   float *d_gamma, float *d_beta, hipStream_t s) {
+    hipLaunchKernelGGL(ordered_reduce_kernel, dim3(2 * ctot), dim3(256), 0, s, W.part, nb, W.tot);
+    hipLaunchKernelGGL(bt_bwd_finalize_kernel, dim3(divup(ctot, 256)), dim3(256), 0, s, W.tot, ctot, rows, gamma, stats, W.coef, d_gamma,
+                       d_beta);
+}

@@ -14,8 +14,9 @@
 //       dbeta = sum delta,  dgamma = sum delta zh,
 //       dW_c = gamma_c / sigma_c (sum delta x_sel - dbeta_c / N S - dgamma_c / N (G w_c - mu_c S) / sigma_c);
 //     one pass over (V, cout) re-reads the selected point of each pillar (and the pillar's points for its mean).
-// Per-block partial sums in fp64, reduced in a fixed order: no float atomics, results are bitwise reproducible.
-#include "common.h"
+// Per-block partial sums in fp64, reduced in a fixed order (ordered_reduce.h's kernel, shared with the BatchNorm statistics of
+// bn_train_dev.h): no float atomics, results are bitwise reproducible.
+#include "ordered_reduce.h"
 
 #define PT_WAVES 4                 // waves per 256-thread block
 #define PT_MAX_BLOCKS 2048
@@ -152,21 +153,6 @@ __global__ __launch_bounds__(256) void pfn_train_stats_kernel(const float *__res
     __syncthreads();
     for (int e = threadIdx.x; e < NE; e += 256)
         part[(size_t)e * gridDim.x + blockIdx.x] = ((s_red[0][e] + s_red[1][e]) + s_red[2][e]) + s_red[3][e];
-}
-
-// rows of `part` ([entries][nparts]) -> tot[entry]; one block per entry, fixed summation order
-__global__ __launch_bounds__(256) void pt_reduce_kernel(const double *__restrict__ part, int nparts, double *__restrict__ tot) {
-    __shared__ double s[256];
-    const double *row = part + (size_t)blockIdx.x * nparts;
-    double a = 0.0;
-    for (int b = threadIdx.x; b < nparts; b += 256) a += row[b];
-    s[threadIdx.x] = a;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-        if ((int)threadIdx.x < h) s[threadIdx.x] += s[threadIdx.x + h];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) tot[blockIdx.x] = s[0];
 }
 
 __device__ __forceinline__ int pt_tri(int a, int b, int D) {   // index of (a, b), a <= b, in the row-major upper triangle
@@ -360,7 +346,7 @@ LIDAR_EXPORT int lidar_pfn_train_forward(const float *voxels, const void *num_po
     double *part = (double *)ws;
     PT_DISPATCH(pfn_train_stats_kernel, dim3(nb), dim3(256), 0, s, voxels, num_points, coords, weight, gamma, num_voxels_dev, num_voxels,
                 p, zsel, slot, part)
-    hipLaunchKernelGGL(pt_reduce_kernel, dim3(D * (D + 1) / 2), dim3(256), 0, s, part, nb, stats);
+    hipLaunchKernelGGL(ordered_reduce_kernel, dim3(D * (D + 1) / 2), dim3(256), 0, s, part, nb, stats);
     hipLaunchKernelGGL(pfn_train_finalize_kernel, dim3(1), dim3(64), 0, s, weight, gamma, beta, nf, cout, max_points, eps,
                        num_voxels_dev, num_voxels, stats, scale_shift, batch_stats);
     int ab = divup((long long)num_voxels * cout, 256);
@@ -388,7 +374,7 @@ LIDAR_EXPORT int lidar_pfn_train_backward(const float *voxels, const void *num_p
     double *btot = part + (size_t)max(D * (D + 1) / 2, cout * K) * nb;
     PT_DISPATCH(pfn_train_bwd_kernel, dim3(nb), dim3(256), 0, s, voxels, num_points, coords, grad_out, zsel, slot, scale_shift, stats,
                 num_voxels_dev, num_voxels, p, part)
-    hipLaunchKernelGGL(pt_reduce_kernel, dim3(cout * K), dim3(256), 0, s, part, nb, btot);
+    hipLaunchKernelGGL(ordered_reduce_kernel, dim3(cout * K), dim3(256), 0, s, part, nb, btot);
     hipLaunchKernelGGL(pfn_train_bwd_finalize_kernel, dim3(1), dim3(64), 0, s, btot, stats, weight, gamma, nf, cout, d_weight, d_gamma,
                        d_beta);
     return lidar_check_launch("lidar_pfn_train_backward");

@@ -15,7 +15,8 @@
 //   (d) out[m] = max_s relu(z scale + shift) with arg[m] = the lowest s among equal maxima (the maximum is taken over y, so a
 //       negative gamma is the minimum of z without a special case); the backward routes grad_out to row (m, arg) where y > 0 (y
 //       recomputed bit for bit) and applies the full BatchNorm backward with bn_train.hip's fp64 coefficients.  The (rows, H)
-//       post-activation tensor is never written.  The statistics kernels are bn_train_dev.h's.
+//       post-activation tensor is never written.  The statistics kernels are bn_train_dev.h's, and so are y, delta and dz per quad,
+//       the workspace split and the "stats -> reduce -> finalize" / "reduce -> backward finalize" launches.
 // No float atomics, no host read: every result is bitwise reproducible.  Supported: H % 4 == 0, 4 <= H <= 128, 1 <= nsample <= 64,
 // M * nsample < 2^31, 16-byte aligned pointers; a row index outside the table is treated as an empty slot and never dereferenced.
 #include "bn_train_dev.h"
@@ -153,21 +154,15 @@ __global__ __launch_bounds__(256) void sat_max_kernel(int M, int H, int ns, cons
     if (m >= M) return;
     const float4 sc = bt_ld4(scale_shift + 4 * L.q), sh = bt_ld4(scale_shift + H + 4 * L.q);
     const float *src = z + (size_t)m * ns * H + 4 * L.q;
-    float4 best;
+    float4 best = bt_y4(bt_ld4(src), sc, sh);
     uchar4 at = make_uchar4(0, 0, 0, 0);
-    {
-        const float4 v = bt_ld4(src);
-        best.x = fmaxf(fmaf(v.x, sc.x, sh.x), 0.f); best.y = fmaxf(fmaf(v.y, sc.y, sh.y), 0.f);
-        best.z = fmaxf(fmaf(v.z, sc.z, sh.z), 0.f); best.w = fmaxf(fmaf(v.w, sc.w, sh.w), 0.f);
-    }
     for (int s = 1; s < ns; ++s) {                            // strict >: the lowest s among equal maxima stays
         const float4 v = bt_ld4(src + (size_t)s * H);
-        const float yx = fmaxf(fmaf(v.x, sc.x, sh.x), 0.f), yy = fmaxf(fmaf(v.y, sc.y, sh.y), 0.f);
-        const float yz = fmaxf(fmaf(v.z, sc.z, sh.z), 0.f), yw = fmaxf(fmaf(v.w, sc.w, sh.w), 0.f);
-        if (yx > best.x) { best.x = yx; at.x = (unsigned char)s; }
-        if (yy > best.y) { best.y = yy; at.y = (unsigned char)s; }
-        if (yz > best.z) { best.z = yz; at.z = (unsigned char)s; }
-        if (yw > best.w) { best.w = yw; at.w = (unsigned char)s; }
+        const float4 y = bt_y4(v, sc, sh);
+        if (y.x > best.x) { best.x = y.x; at.x = (unsigned char)s; }
+        if (y.y > best.y) { best.y = y.y; at.y = (unsigned char)s; }
+        if (y.z > best.z) { best.z = y.z; at.z = (unsigned char)s; }
+        if (y.w > best.w) { best.w = y.w; at.w = (unsigned char)s; }
     }
     bt_st4(out + (size_t)m * H + 4 * L.q, best);
     *reinterpret_cast<uchar4 *>(arg + (size_t)m * H + 4 * L.q) = at;
@@ -179,7 +174,7 @@ __device__ __forceinline__ float sat_delta(const float *__restrict__ zrow0, int 
     zv = 0.f;
     if (a >= (unsigned)ns) return 0.f;
     zv = zrow0[(size_t)a * H + c];
-    return fmaxf(fmaf(zv, sc, sh), 0.f) > 0.f ? g : 0.f;
+    return bt_delta(bt_y(zv, sc, sh), g);
 }
 
 // (d) backward pass 1: sum delta, sum delta z (fp64) per channel and block; only the M chosen rows of a channel are non-zero
@@ -217,28 +212,16 @@ __global__ __launch_bounds__(256) void sat_bwd_apply_kernel(int M, int H, int ns
     if (m >= M) return;
     const int c = 4 * L.q;
     const float4 sc = bt_ld4(scale_shift + c), sh = bt_ld4(scale_shift + H + c);
-    double A[4], m1[4], m2[4], mu[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        A[k] = coef[c + k]; m1[k] = coef[H + c + k]; m2[k] = coef[2 * H + c + k]; mu[k] = coef[3 * H + c + k];
-    }
+    const BtCoef4 k = bt_coef4(coef, H, c);
     const float4 gv = bt_ld4(g + (size_t)m * H + c);
     const uchar4 at = *reinterpret_cast<const uchar4 *>(arg + (size_t)m * H + c);
     const float *src = z + (size_t)m * ns * H + c;
     float *dst = dzo + (size_t)m * ns * H + c;
     for (int s = 0; s < ns; ++s) {
         const float4 v = bt_ld4(src + (size_t)s * H);
-        float4 d;
-        d.x = (s == at.x && fmaxf(fmaf(v.x, sc.x, sh.x), 0.f) > 0.f) ? gv.x : 0.f;
-        d.y = (s == at.y && fmaxf(fmaf(v.y, sc.y, sh.y), 0.f) > 0.f) ? gv.y : 0.f;
-        d.z = (s == at.z && fmaxf(fmaf(v.z, sc.z, sh.z), 0.f) > 0.f) ? gv.z : 0.f;
-        d.w = (s == at.w && fmaxf(fmaf(v.w, sc.w, sh.w), 0.f) > 0.f) ? gv.w : 0.f;
-        float4 o;
-        o.x = (float)(A[0] * ((double)d.x - m1[0] - ((double)v.x - mu[0]) * m2[0]));
-        o.y = (float)(A[1] * ((double)d.y - m1[1] - ((double)v.y - mu[1]) * m2[1]));
-        o.z = (float)(A[2] * ((double)d.z - m1[2] - ((double)v.z - mu[2]) * m2[2]));
-        o.w = (float)(A[3] * ((double)d.w - m1[3] - ((double)v.w - mu[3]) * m2[3]));
-        bt_st4(dst + (size_t)s * H, o);
+        const float4 on = bt_delta4(v, gv, sc, sh);            // delta if this row is the chosen one
+        const float4 d = make_float4(s == at.x ? on.x : 0.f, s == at.y ? on.y : 0.f, s == at.z ? on.z : 0.f, s == at.w ? on.w : 0.f);
+        bt_st4(dst + (size_t)s * H, bt_dz4(k, d, v));
     }
 }
 
@@ -311,14 +294,6 @@ LIDAR_EXPORT size_t lidar_bn_relu_max_train_workspace_bytes(int M, int nsample, 
     return bt_workspace_bytes(P, H);
 }
 
-static void sat_seg(const float *z, int H, BtSegs &S) {
-    S.n = 1;
-    S.ctot = H;
-    S.s[0].x = z; S.s[0].dx = nullptr;
-    S.s[0].C = H; S.s[0].ld = H; S.s[0].off = 0; S.s[0].c0 = 0;
-    S.s[0].r = nullptr; S.s[0].dr = nullptr; S.s[0].r_ld = S.s[0].dr_ld = 0;
-}
-
 LIDAR_EXPORT int lidar_bn_relu_max_train_forward(const float *z, int M, int nsample, int H, const float *gamma, const float *beta,
                                                  float eps, float *out, unsigned char *arg, double *stats, float *scale_shift,
                                                  float *batch_stats, void *ws, size_t ws_bytes, void *stream) {
@@ -330,12 +305,8 @@ LIDAR_EXPORT int lidar_bn_relu_max_train_forward(const float *z, int M, int nsam
     if (ws_bytes < bt_workspace_bytes(P, H)) return LIDAR_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     BtSegs S;
-    sat_seg(z, H, S);
-    const int nb = bt_blocks(P);
-    double *part = (double *)ws, *tot = part + (size_t)2 * H * nb;
-    hipLaunchKernelGGL(bt_stats_kernel, dim3(nb, 1), dim3(256), 0, s, S, P, nb, part);
-    hipLaunchKernelGGL(bt_reduce_kernel, dim3(2 * H), dim3(256), 0, s, part, nb, tot);
-    hipLaunchKernelGGL(bt_finalize_kernel, dim3(1), dim3(256), 0, s, tot, H, P, gamma, beta, eps, stats, scale_shift, batch_stats);
+    bt_one_seg(z, nullptr, H, H, S);
+    bt_launch_stats(S, P, gamma, beta, eps, stats, scale_shift, batch_stats, ws, s);
     hipLaunchKernelGGL(sat_max_kernel, dim3(sat_rows_grid(M, H)), dim3(256), 0, s, M, H, nsample, z, scale_shift, out, arg);
     return lidar_check_launch("lidar_bn_relu_max_train_forward");
 }
@@ -351,13 +322,11 @@ LIDAR_EXPORT int lidar_bn_relu_max_train_backward(const float *z, int M, int nsa
         return LIDAR_ERR_ARG;
     if (ws_bytes < bt_workspace_bytes(P, H)) return LIDAR_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    const int nbp = bt_blocks(P), nb = bt_blocks(M);             // the workspace is laid out for nbp >= nb partials
-    double *part = (double *)ws, *tot = part + (size_t)2 * H * nbp;
-    double *coef = tot + 2 * H;
-    hipLaunchKernelGGL(sat_bwd_stats_kernel, dim3(nb), dim3(256), 0, s, M, H, nsample, nb, z, scale_shift, grad_out, arg, part);
-    hipLaunchKernelGGL(bt_reduce_kernel, dim3(2 * H), dim3(256), 0, s, part, nb, tot);
-    hipLaunchKernelGGL(bt_bwd_finalize_kernel, dim3(1), dim3(256), 0, s, tot, H, P, gamma, stats, coef, d_gamma, d_beta);
-    hipLaunchKernelGGL(sat_bwd_apply_kernel, dim3(sat_rows_grid(M, H)), dim3(256), 0, s, M, H, nsample, z, scale_shift, coef, grad_out,
+    const int nb = bt_blocks(M);
+    const BtWs W = bt_ws_split(ws, H, bt_blocks(P));             // laid out for bt_blocks(P) >= nb partials
+    hipLaunchKernelGGL(sat_bwd_stats_kernel, dim3(nb), dim3(256), 0, s, M, H, nsample, nb, z, scale_shift, grad_out, arg, W.part);
+    bt_launch_bwd_finalize(W, H, nb, P, gamma, stats, d_gamma, d_beta, s);
+    hipLaunchKernelGGL(sat_bwd_apply_kernel, dim3(sat_rows_grid(M, H)), dim3(256), 0, s, M, H, nsample, z, scale_shift, W.coef, grad_out,
                        arg, dz);
     return lidar_check_launch("lidar_bn_relu_max_train_backward");
 }

@@ -1,7 +1,7 @@
 """Host side of the PillarVFE / MeanVFE / PointPillarScatter kernels (include/lidar_hip.h)."""
 import torch
 
-from . import _lib, workspace
+from . import _lib, bn_train, workspace
 
 
 def fold_bn(gamma, beta, mean, var, eps):
@@ -199,11 +199,7 @@ def pillar_vfe_train(voxels, num_points, coords, weight, gamma, beta, running_me
     meta = dict(eps=float(eps), vs=_lib.host_f32(voxel_size), rng=_lib.host_f32(point_cloud_range), dist=int(bool(with_distance)),
                 cf=int(coords.dtype == torch.float32), nf=int(num_points.dtype == torch.float32))
     out, batch_stats = _PillarVFETrain.apply(meta, voxels, num_points, coords, num_voxels_dev, weight, gamma, beta)
-    with torch.no_grad():     # BatchNorm1d's running update (momentum form), on the device
-        running_mean.mul_(1.0 - momentum).add_(batch_stats[:cout], alpha=momentum)
-        running_var.mul_(1.0 - momentum).add_(batch_stats[2 * cout:], alpha=momentum)
-        if num_batches_tracked is not None:
-            num_batches_tracked.add_(1)
+    bn_train.update_running(running_mean, running_var, num_batches_tracked, momentum, batch_stats, cout)
     if return_stats:
         return out, batch_stats[:cout], batch_stats[cout:2 * cout]
     return out

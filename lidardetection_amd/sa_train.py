@@ -6,39 +6,22 @@ reference: pcdet/ops/pointnet2/pointnet2_stack/pointnet2_modules.py:58-92 (Stack
 A scale of StackSAModuleMSG in grad mode, row-major: the first 1x1 convolution runs per SOURCE point in front of the gather
 (torch.mm, so autograd yields its weight and feature gradients), `sa_gather_train` gathers its rows per (query, sample) pair and
 sends the gradient back through an inverse index (ordered sums, no float atomics), the middle layers are torch.mm plus the fused
-row BatchNorm + ReLU of spconv/train.py, and `bn_relu_max_train` is the last layer's BatchNorm + ReLU + max over the samples in
+row BatchNorm + ReLU of bn_train.py, and `bn_relu_max_train` is the last layer's BatchNorm + ReLU + max over the samples in
 one pass that never writes the (M * nsample, H) activation.
 
 Opt-in: inside `with fused_sa_train():` a grad-mode, train-mode StackSAModuleMSG whose scales all qualify (scale_supported) takes
 this route; outside it nothing changes.
 """
-import contextlib
-import ctypes as C
-
 import torch
 from torch import nn
 
-from . import _lib, workspace
-from .spconv import train as rows_train
+from . import _lib, bn_train
 
 MAX_H, MAX_NSAMPLE = 128, 64          # csrc/sa_train.hip SAT_MAX_H / SAT_MAX_NS
-_ENABLED = [False]
 
-
-@contextlib.contextmanager
-def fused_sa_train(enabled=True):
+fused_sa_train, fused_sa_train_enabled = bn_train.switch(
     """inside: a grad-mode, train-mode StackSAModuleMSG with pool_method 'max_pool' runs on the fused route when every one of its
-    scales qualifies (module_supported); anything else, and everything outside, runs the stock modules"""
-    was = _ENABLED[0]
-    _ENABLED[0] = bool(enabled)
-    try:
-        yield
-    finally:
-        _ENABLED[0] = was
-
-
-def fused_sa_train_enabled():
-    return _ENABLED[0]
+    scales qualifies (module_supported); anything else, and everything outside, runs the stock modules""")
 
 
 def supported(H, nsample):
@@ -47,8 +30,7 @@ def supported(H, nsample):
 
 
 def _bn_ok(bn):
-    return (isinstance(bn, nn.BatchNorm2d) and bn.training and bn.affine and bn.track_running_stats and bn.running_mean is not None
-            and bn.num_batches_tracked is not None and isinstance(bn.momentum, (int, float)) and not isinstance(bn.momentum, bool))
+    return bn_train.supported(bn, nn.BatchNorm2d, True, max_c=None)     # the width is supported()'s business
 
 
 def scale_supported(mlp, nsample):
@@ -161,11 +143,6 @@ def sa_gather_train(table, query_term, idx, xyz_batch_cnt, new_xyz_batch_cnt):
 
 
 # ---- (d): BatchNorm + ReLU + max ---------------------------------------------------------------------------------------------------
-def _ws(M, ns, H, dev):
-    nbytes = _lib.lib().lidar_bn_relu_max_train_workspace_bytes(M, ns, H)
-    return workspace.get("sa_train", nbytes, dev), nbytes
-
-
 def bn_relu_max_forward(z, M, nsample, gamma, beta, eps):
     """z (M * nsample, H) -> (out (M, H), arg (M, H) uint8, stats, scale_shift, batch_stats)"""
     H = z.shape[1] if z.dim() == 2 else -1
@@ -177,10 +154,8 @@ def bn_relu_max_forward(z, M, nsample, gamma, beta, eps):
     dev = z.device
     out = torch.empty((M, H), dtype=torch.float32, device=dev)
     arg = torch.empty((M, H), dtype=torch.uint8, device=dev)
-    stats = torch.empty(2 * H, dtype=torch.float64, device=dev)
-    scale_shift = torch.empty(2 * H, dtype=torch.float32, device=dev)
-    batch_stats = torch.empty(3 * H, dtype=torch.float32, device=dev)
-    ws, wsb = _ws(M, nsample, H, dev)
+    stats, scale_shift, batch_stats = bn_train.alloc_stats(H, dev)
+    ws, wsb = bn_train.get_workspace("sa_train", dev, M, nsample, H)
     _lib.check(_lib.lib().lidar_bn_relu_max_train_forward(_lib.ptr(z), M, nsample, H, _lib.ptr(gamma), _lib.ptr(beta), float(eps),
                                                           _lib.ptr(out), _lib.ptr(arg), _lib.ptr(stats), _lib.ptr(scale_shift),
                                                           _lib.ptr(batch_stats), _lib.ptr(ws), wsb, _lib.stream()),
@@ -202,7 +177,7 @@ def bn_relu_max_backward(z, M, nsample, grad_out, arg, gamma, stats, scale_shift
     dz = torch.empty_like(z)
     d_gamma = torch.empty(H, dtype=torch.float32, device=dev)
     d_beta = torch.empty(H, dtype=torch.float32, device=dev)
-    ws, wsb = _ws(M, nsample, H, dev)
+    ws, wsb = bn_train.get_workspace("sa_train", dev, M, nsample, H)
     _lib.check(_lib.lib().lidar_bn_relu_max_train_backward(_lib.ptr(z), M, nsample, H, _lib.ptr(g), _lib.ptr(arg), _lib.ptr(gamma),
                                                            _lib.ptr(stats), _lib.ptr(scale_shift), _lib.ptr(dz), _lib.ptr(d_gamma),
                                                            _lib.ptr(d_beta), _lib.ptr(ws), wsb, _lib.stream()),
@@ -227,14 +202,6 @@ class _BNReLUMax(torch.autograd.Function):
         return None, d_gamma if need[1] else None, d_beta if need[2] else None, dz if need[3] else None, None, None
 
 
-def _update_running(bn, batch_stats):
-    c, m = bn.num_features, float(bn.momentum)
-    with torch.no_grad():   # BatchNorm's running update (momentum form, unbiased variance), on the device
-        bn.running_mean.mul_(1.0 - m).add_(batch_stats[:c], alpha=m)
-        bn.running_var.mul_(1.0 - m).add_(batch_stats[2 * c:3 * c], alpha=m)
-        bn.num_batches_tracked.add_(1)
-
-
 def bn_relu_max_train(z, bn, M, nsample):
     """max over the nsample rows of every query of relu(bn(z)) for a train-mode BatchNorm2d module `bn` on the (M * nsample, H)
     matrix z -> (M, H); differentiable with respect to z and the module's weight / bias.  running_mean / running_var /
@@ -242,14 +209,14 @@ def bn_relu_max_train(z, bn, M, nsample):
     if not _bn_ok(bn) or z.dim() != 2 or bn.num_features != z.shape[1]:
         _lib.fail("bn_relu_max_train", f"unsupported BatchNorm2d / matrix {tuple(z.shape)}")
     out, batch_stats = _BNReLUMax.apply(float(bn.eps), bn.weight, bn.bias, z.contiguous(), int(M), int(nsample))
-    _update_running(bn, batch_stats)
+    bn_train.update_module(bn, batch_stats)
     return out
 
 
 def bn_relu_rows_train(z, bn):
-    """relu(bn(z)) on the (rows, H) matrix z for a train-mode BatchNorm2d module (a middle layer): spconv/train.py's row kernels"""
-    y, batch_stats = rows_train._BNReLURows.apply(float(bn.eps), bn.weight, bn.bias, z.contiguous())
-    _update_running(bn, batch_stats)
+    """relu(bn(z)) on the (rows, H) matrix z for a train-mode BatchNorm2d module (a middle layer): bn_train.py's rows path"""
+    y, batch_stats = bn_train._BNReLURows.apply(float(bn.eps), bn.weight, bn.bias, z.contiguous())
+    bn_train.update_module(bn, batch_stats)
     return y
 
 
