@@ -65,7 +65,7 @@ AB_VARIANTS = {
     "vxl_share8": ("voxelize.hip", ["-DVXL_FILL_SHARE16=8"]),      # part of the zero fill moved into the emit launch
     "dc_nowait": ("deconv_gemm.hip", ["-DDC_PROBE=1"]),
     "sc_p1": ("sparse_conv.hip", ["-DSC_PROBE=1"]), "sc_p2": ("sparse_conv.hip", ["-DSC_PROBE=2"]), "sc_p4": ("sparse_conv.hip", ["-DSC_PROBE=4"]),
-    "sc_p7": ("sparse_conv.hip", ["-DSC_PROBE=7"]),                # WRONG results: ablations of the sparse implicit GEMM            # WRONG results: the deblock GEMM's barrier does not wait for its DMA        # F(4x4) Winograd with default-policy output stores instead of nt
+    "sc_p7": ("sparse_conv.hip", ["-DSC_PROBE=7"]),                # WRONG results: SC_PROBE ablations of the register-A sparse GEMM
 }
 
 

@@ -340,9 +340,9 @@ LIDAR_EXPORT int lidar_spconv_conv_tables(int n, int kD, int kH, int kW, int sD,
 }
 
 // ------------------------------------------------------------------ implicit GEMM (fp32 MFMA 32x32x2)
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-#define IG_ROWS 128          // rows per workgroup (4 waves x 32)
-#define IG_MAX_C 128
+// sc_gemm_dev.h holds the one copy of what the seven kernels below share (accumulators, epilogue, mask walk, W staging, register-A
+// gather and MFMA stage); each kernel keeps its shape block, its buffers, its prologue order and its main loop.
+#include "sc_gemm_dev.h"
 
 // out (n_out, Cout) = sum_k in[nbr[., k]] @ W[k] (+ bias).  W is (K, Cin, Cout) row-major (spconv's
 // (kD,kH,kW,Cin,Cout) parameter viewed flat).  NT = number of 32-column tiles (Cout <= 32*NT).
@@ -359,10 +359,7 @@ __global__ __launch_bounds__(256) void sc_implicit_gemm_kernel(const float *__re
     const int row0 = blockIdx.x * IG_ROWS + wv * 32;
     float *A = s_a + (size_t)wv * 32 * Cp;
     f32x16 acc[NT];
-#pragma unroll
-    for (int q = 0; q < NT; ++q)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
+    ig_zero(acc);
     const int ar = l & 31, ak = l >> 5;           // MFMA operand coordinates of this lane
     const int CW = NT * 32;
     for (int k = 0; k < K; ++k) {
@@ -432,7 +429,7 @@ __global__ __launch_bounds__(256) void sc_implicit_gemm_kernel(const float *__re
             }
         }
     }
-    // C/D layout of 32x32 MFMA: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
+    // its own epilogue (conditional loads, the residual added only when there is one): see DESIGN §3.33
 #pragma unroll
     for (int q = 0; q < NT; ++q) {
         const int col = q * 32 + (l & 31);
@@ -440,7 +437,7 @@ __global__ __launch_bounds__(256) void sc_implicit_gemm_kernel(const float *__re
             const float bv = bias ? bias[col] : 0.f;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int row = row0 + (r & 3) + 8 * (r >> 2) + 4 * (l >> 5);
+                const int row = ig_cd_row(row0, r, ak);
                 if (row < n_out) {              // fused epilogue: (+ bias) (+ residual) (ReLU)
                     float v = acc[q][r] + bv;
                     if (residual) v += residual[(size_t)row * Cout + col];
@@ -474,39 +471,21 @@ __global__ __launch_bounds__(256) void sc_implicit_gemm_pipe_kernel(const float 
     const int myrow = row0 + (l & 31);
     // table row this lane-row reads: the permutation entry for mask-sorted execution (out_row), else the row itself
     const int trow = (out_row && myrow < n_out) ? out_row[myrow] : myrow;
-    const int Co4 = Cout >> 2;
     f32x16 acc[NT];
-#pragma unroll
-    for (int q = 0; q < NT; ++q)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
+    ig_zero(acc);
     const int ar = l & 31, ak = l >> 5;
     float4 g[NG], wr[NW];
     bool any_next;
-    // Mask-sorted tables (row_mask != NULL, K <= 32): rows arrive grouped by their neighbour-offset bit mask, so the 32 rows
-    // of a wave tile (and the 128 of the workgroup) mostly share one mask: offsets no row of the WORKGROUP uses are skipped
-    // outright (no W staging, no barriers) and a wave's MFMAs run only for offsets its own rows use.
     __shared__ unsigned s_wmask[4];
     unsigned wave_mask = 0xffffffffu, wg_mask = 0xffffffffu;
-    if (row_mask) {
-        unsigned m = (myrow < n_out) ? (unsigned)row_mask[trow] : 0u;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) m |= (unsigned)__shfl_xor((int)m, d, 64);
-        wave_mask = m;
-        if (l == 0) s_wmask[wv] = m;
-        __syncthreads();
-        wg_mask = s_wmask[0] | s_wmask[1] | s_wmask[2] | s_wmask[3];
+    if (row_mask) {                                       // mask-sorted tables: the mask walk of sc_gemm_dev.h
+        wave_mask = ig_tile_mask(row_mask, myrow, trow, n_out);
+        wg_mask = ig_wg_mask(s_wmask, wave_mask, l, wv);
     }
-    auto next_k = [&](int k) {                            // next offset > k some row of the workgroup uses (K when none)
-        if (!row_mask) return k + 1;
-        const unsigned rest = (k + 1 < 32) ? (wg_mask >> (k + 1)) : 0u;
-        return rest ? k + 1 + __builtin_ctz(rest) : K;
-    };
-    // table entries are requested one offset ahead of the gathers that use them (two ahead of the MFMAs), so no wave waits
-    // for a table load with nothing else in flight
-    auto load_src = [&](int k) { return (myrow < n_out && k < K) ? nbr[(size_t)trow * K + k] : -1; };
+    auto next_k = [&](int k) { return ig_next_k(wg_mask, k, K, row_mask != nullptr); };
+    auto load_src = [&](int k) { return ig_load_src(nbr, myrow, trow, n_out, k, K); };
     auto fetch = [&](int k, int h, const int src) {       // stage (offset k, channel slice h)
-        any_next = row_mask ? ((wave_mask >> k) & 1u) != 0u : __ballot(src >= 0) != 0ull;
+        any_next = ig_uses(wave_mask, k, src, row_mask != nullptr);
 #pragma unroll
         for (int u = 0; u < NG; ++u) {
             const int e = u * 64 + l, r = e / C4, c = e - r * C4;
@@ -514,12 +493,7 @@ __global__ __launch_bounds__(256) void sc_implicit_gemm_pipe_kernel(const float 
             g[u] = make_float4(0.f, 0.f, 0.f, 0.f);
             if (any_next && sr >= 0) g[u] = reinterpret_cast<const float4 *>(in + (size_t)sr * CinT + h * Cin)[c];
         }
-#pragma unroll
-        for (int q = 0; q < NW; ++q) {
-            const int e = q * 256 + t, ci = e / CW4, q4 = e - ci * CW4;
-            wr[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (e < Cin * CW4 && q4 < Co4) wr[q] = reinterpret_cast<const float4 *>(Wt + ((size_t)k * CinT + h * Cin + ci) * Cout)[q4];
-        }
+        ig_fetch_w<Cin, CW, 256>(wr, Wt, (size_t)k * CinT + h * Cin, Cout, t);
     };
     int k = next_k(-1), h = 0;
     int src_cur = load_src(k), src_ahead = -1;            // table entries of the offset being fetched / of the one after it
@@ -542,13 +516,8 @@ __global__ __launch_bounds__(256) void sc_implicit_gemm_pipe_kernel(const float 
                 dst[0] = g[u].x; dst[1] = g[u].y; dst[2] = g[u].z; dst[3] = g[u].w;
             }
         }
-        {   // W[k]: pieces are distributed over all 256 threads, so every thread must hold them -> fetched unconditionally below
-#pragma unroll
-            for (int q = 0; q < NW; ++q) {
-                const int e = q * 256 + t;
-                if (e < Cin * CW4) reinterpret_cast<float4 *>(s_w)[e] = wr[q];
-            }
-        }
+        // W[k]: pieces are distributed over all 256 threads, so every thread must hold them -> fetched unconditionally below
+        ig_store_w<Cin, CW, 256>(s_w, wr, t);
         __syncthreads();
         if (kn < K) {                                     // in flight while the MFMAs below run
             if (kn != k) {
@@ -571,56 +540,22 @@ __global__ __launch_bounds__(256) void sc_implicit_gemm_pipe_kernel(const float 
         k = kn;
         h = hn;
     }
-    const int last = n_out - 1;                           // n_out >= 1 (checked by the launcher)
-    // fused epilogue: (+ bias) (+ residual) (ReLU); sorted tables scatter rows.  Output row indices and residual values are
-    // requested eight rows at a time before any is used (clamped, unconditional loads: no wait per element).
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        int orow[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int r = h * 8 + j;
-            const int row = min(row0 + (r & 3) + 8 * (r >> 2) + 4 * (l >> 5), last);
-            orow[j] = out_row ? out_row[row] : row;
-        }
-#pragma unroll
-        for (int q = 0; q < NT; ++q) {
-            const int col = q * 32 + (l & 31);
-            const int cc = min(col, Cout - 1);
-            const float bv = bias ? bias[cc] : 0.f;
-            float res[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) res[j] = 0.f;
-            if (residual) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) res[j] = residual[(size_t)orow[j] * Cout + cc];
-            }
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int r = h * 8 + j;
-                const int row = row0 + (r & 3) + 8 * (r >> 2) + 4 * (l >> 5);
-                if (row < n_out && col < Cout) {
-                    const float v = acc[q][r] + bv + res[j];
-                    out[(size_t)orow[j] * Cout + col] = relu ? fmaxf(v, 0.f) : v;
-                }
-            }
-        }
-    }
+    ig_epilogue(acc, row0, ar, ak, n_out, Cout, bias, residual, relu, out, out_row);
 }
 
 // Register-A variant (r03; Cin = 4*C4*SL in {16, 32, 64, 128}, Cout % 4 == 0) — the kernel the launcher uses.
 // The MFMA's A operand wants lane (row r = lane & 31, half a = lane >> 5) to supply channel (step, a) of row r.  The
 // pipe kernel above gathers rows with coalescing lanes, transposes them through LDS (four ds_write_b32 per float4 at an odd
-// pitch) and reads them back one float per MFMA step, two barriers per offset.  Any fixed assignment of channels to
-// (step, half) gives the same products summed in a fixed order, so here half a of row r simply OWNS the 16-byte pieces a, a + 2,
-// a + 4, ... of the row (r04; r03: the contiguous half [a * Cin/2, (a + 1) * Cin/2) — then one gather instruction touched every
-// 64-byte sector of a row with a single 16-byte piece and each sector was requested by four different instructions; interleaved, the
-// two halves of a row read neighbouring pieces in the same instruction and a sector is requested twice): lane (r, a) loads those
-// Cin/2 floats of its gathered row straight into registers and feeds them to the MFMAs — no LDS for A, no transpose, no cross-lane shuffles of the table
+// pitch) and reads them back one float per MFMA step, two barriers per offset.  Here half a of row r OWNS every second 16-byte
+// piece of the row (ig_fetch_a in sc_gemm_dev.h has the ownership note): lane (r, a) loads those Cin/2 floats of its gathered row
+// straight into registers and feeds them to the MFMAs — no LDS for A, no transpose, no cross-lane shuffles of the table
 // entries.  Only W[k] goes through LDS, double-buffered: the pieces of W[k+1] and the gathered rows of offset k+1 are in flight
 // while the MFMAs of offset k run, and ONE barrier per offset separates a buffer's last reader from its next writer.
 // Per output row the channels are accumulated in a different (but fixed) order than in the pipe kernel: results differ from
 // it in the last bits, and are bit-identical between table order and mask order as before (same kernel, same order).
+// Of sc_gemm_dev.h this kernel uses the accumulator zeroing and the mask prologue only.  Its mask walk, W staging, gather, MFMA stage
+// and epilogue stay its own text: built on the shared helpers its 16 and 32 channel instances measured 5 - 12 % slower and, with
+// ig_epilogue, two instances lose a wave of occupancy (DESIGN §3.33 has the figures per helper).
 template <int NT, int C4, int SL = 1>
 __global__ __launch_bounds__(256) void sc_implicit_gemm_rega_kernel(const float *__restrict__ in, const int *__restrict__ nbr, int n_out,
                                                                     int K, int Cout, const float *__restrict__ Wt,
@@ -638,20 +573,12 @@ __global__ __launch_bounds__(256) void sc_implicit_gemm_rega_kernel(const float 
     const int trow = (out_row && myrow < n_out) ? out_row[myrow] : myrow;
     const int Co4 = Cout >> 2;
     f32x16 acc[NT];
-#pragma unroll
-    for (int q = 0; q < NT; ++q)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
+    ig_zero(acc);
     __shared__ unsigned s_wmask[4];
     unsigned wave_mask = 0xffffffffu, wg_mask = 0xffffffffu;
-    if (row_mask) {                                       // mask-sorted tables: see the pipe kernel
-        unsigned m = (myrow < n_out) ? (unsigned)row_mask[trow] : 0u;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) m |= (unsigned)__shfl_xor((int)m, d, 64);
-        wave_mask = m;
-        if (l == 0) s_wmask[wv] = m;
-        __syncthreads();
-        wg_mask = s_wmask[0] | s_wmask[1] | s_wmask[2] | s_wmask[3];
+    if (row_mask) {
+        wave_mask = ig_tile_mask(row_mask, myrow, trow, n_out);
+        wg_mask = ig_wg_mask(s_wmask, wave_mask, l, wv);
     }
     auto next_k = [&](int k) {                            // next offset > k some row of the workgroup uses (K when none)
         if (!row_mask) return k + 1;
@@ -799,60 +726,23 @@ __global__ __launch_bounds__(256) void sc_implicit_gemm_rega2_kernel(const float
         myrow[rt] = row0 + 32 * rt + ar;
         trow[rt] = (out_row && myrow[rt] < n_out) ? out_row[myrow[rt]] : myrow[rt];
     }
-    const int Co4 = Cout >> 2;
     f32x16 acc[2][NT];
-#pragma unroll
-    for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-        for (int q = 0; q < NT; ++q)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[rt][q][r] = 0.f;
+    ig_zero(acc[0]);
+    ig_zero(acc[1]);
     __shared__ unsigned s_wmask[4];
     unsigned tile_mask[2] = {0xffffffffu, 0xffffffffu}, wg_mask = 0xffffffffu;
     if (row_mask) {
 #pragma unroll
-        for (int rt = 0; rt < 2; ++rt) {
-            unsigned m = (myrow[rt] < n_out) ? (unsigned)row_mask[trow[rt]] : 0u;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) m |= (unsigned)__shfl_xor((int)m, d, 64);
-            tile_mask[rt] = m;
-        }
-        if (l == 0) s_wmask[wv] = tile_mask[0] | tile_mask[1];
-        __syncthreads();
-        wg_mask = s_wmask[0] | s_wmask[1] | s_wmask[2] | s_wmask[3];
+        for (int rt = 0; rt < 2; ++rt) tile_mask[rt] = ig_tile_mask(row_mask, myrow[rt], trow[rt], n_out);
+        wg_mask = ig_wg_mask(s_wmask, tile_mask[0] | tile_mask[1], l, wv);
     }
-    auto next_k = [&](int k) {
-        if (!row_mask) return k + 1;
-        const unsigned rest = (k + 1 < 32) ? (wg_mask >> (k + 1)) : 0u;
-        return rest ? k + 1 + __builtin_ctz(rest) : K;
-    };
-    auto load_src = [&](int rt, int k) { return (myrow[rt] < n_out && k < K) ? nbr[(size_t)trow[rt] * K + k] : -1; };
-    auto tile_uses = [&](int rt, int k, int src) { return row_mask ? ((tile_mask[rt] >> k) & 1u) != 0u : __ballot(src >= 0) != 0ull; };
+    auto next_k = [&](int k) { return ig_next_k(wg_mask, k, K, row_mask != nullptr); };
+    auto load_src = [&](int rt, int k) { return ig_load_src(nbr, myrow[rt], trow[rt], n_out, k, K); };
+    auto tile_uses = [&](int rt, int k, int src) { return ig_uses(tile_mask[rt], k, src, row_mask != nullptr); };
     float4 wr[NW], ga[2][NG], gn[2][NG];
-    auto fetch_w = [&](int k) {
-#pragma unroll
-        for (int q = 0; q < NW; ++q) {
-            const int e = q * 256 + t, ci = e / CW4, q4 = e - ci * CW4;
-            wr[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (e < Cin * CW4 && q4 < Co4) wr[q] = reinterpret_cast<const float4 *>(Wt + ((size_t)k * Cin + ci) * Cout)[q4];
-        }
-    };
-    auto store_w = [&](int buf) {
-        float4 *dst = reinterpret_cast<float4 *>(s_mem + (size_t)buf * Cin * CW);
-#pragma unroll
-        for (int q = 0; q < NW; ++q) {
-            const int e = q * 256 + t;
-            if (e < Cin * CW4) dst[e] = wr[q];
-        }
-    };
-    auto fetch_a = [&](float4 (&g)[NG], int src, bool any) {
-        const float4 *rowp = reinterpret_cast<const float4 *>(in + (size_t)max(src, 0) * Cin) + ak;      // pieces ak, ak + 2, ...
-#pragma unroll
-        for (int u = 0; u < NG; ++u) {
-            g[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (any && src >= 0) g[u] = rowp[2 * u];
-        }
-    };
+    auto fetch_w = [&](int k) { ig_fetch_w<Cin, CW, 256>(wr, Wt, (size_t)k * Cin, Cout, t); };
+    auto store_w = [&](int buf) { ig_store_w<Cin, CW, 256>(s_mem + (size_t)buf * Cin * CW, wr, t); };
+    auto fetch_a = [&](float4 (&g)[NG], int src, bool any) { ig_fetch_a<NG>(g, in, Cin, 0, src, ak, any); };
     int k = next_k(-1), buf = 0;
     if (k >= K) k = K;
     int src_cur[2] = {load_src(0, k), load_src(1, k)}, src_ahead[2] = {-1, -1};
@@ -902,17 +792,7 @@ __global__ __launch_bounds__(256) void sc_implicit_gemm_rega2_kernel(const float
         } else {
 #pragma unroll
             for (int rt = 0; rt < 2; ++rt) {
-                if (!any[rt]) continue;                   // wave-uniform
-#pragma unroll
-                for (int u = 0; u < NG; ++u) {
-                    const float av[4] = {ga[rt][u].x, ga[rt][u].y, ga[rt][u].z, ga[rt][u].w};
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-#pragma unroll
-                        for (int q = 0; q < NT; ++q)
-                            acc[rt][q] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[j], Wb[(u * 8 + j) * CW + q * 32], acc[rt][q], 0, 0, 0);
-                    }
-                }
+                if (any[rt]) ig_mma_stage<NT, NG>(acc[rt], ga[rt], Wb);       // wave-uniform
             }
         }
         if (kn < K) {
@@ -930,44 +810,8 @@ __global__ __launch_bounds__(256) void sc_implicit_gemm_rega2_kernel(const float
         k = kn;
         buf ^= 1;
     }
-    const int last = n_out - 1;                           // n_out >= 1 (checked by the launcher)
-    // fused epilogue, per row tile: (+ bias) (+ residual) (ReLU); sorted tables scatter rows (as in the register-A kernel)
-#pragma unroll
-    for (int rt = 0; rt < 2; ++rt) {
-        const int rbase = row0 + 32 * rt;
-#pragma unroll
-        for (int hh = 0; hh < 2; ++hh) {
-            int orow[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int r = hh * 8 + j;
-                const int row = min(rbase + (r & 3) + 8 * (r >> 2) + 4 * (l >> 5), last);
-                orow[j] = out_row ? out_row[row] : row;
-            }
-#pragma unroll
-            for (int q = 0; q < NT; ++q) {
-                const int col = q * 32 + (l & 31);
-                const int cc = min(col, Cout - 1);
-                const float bv = bias ? bias[cc] : 0.f;
-                float res[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) res[j] = 0.f;
-                if (residual) {
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) res[j] = residual[(size_t)orow[j] * Cout + cc];
-                }
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const int r = hh * 8 + j;
-                    const int row = rbase + (r & 3) + 8 * (r >> 2) + 4 * (l >> 5);
-                    if (row < n_out && col < Cout) {
-                        const float v = acc[rt][q][r] + bv + res[j];
-                        out[(size_t)orow[j] * Cout + col] = relu ? fmaxf(v, 0.f) : v;
-                    }
-                }
-            }
-        }
-    }
+    ig_epilogue(acc[0], row0, ar, ak, n_out, Cout, bias, residual, relu, out, out_row);        // per row tile
+    ig_epilogue(acc[1], row0 + 32, ar, ak, n_out, Cout, bias, residual, relu, out, out_row);
 }
 
 // Packed-weight variant of the register-A kernel (r04; same shapes, same channel ownership, same summation order: results are
@@ -996,28 +840,16 @@ __global__ __launch_bounds__(256) void sc_implicit_gemm_pk_kernel(const float *_
     const int myrow = row0 + ar;
     const int trow = (out_row && myrow < n_out) ? out_row[myrow] : myrow;
     f32x16 acc[NT];
-#pragma unroll
-    for (int q = 0; q < NT; ++q)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
+    ig_zero(acc);
     __shared__ unsigned s_wmask[4];
     unsigned wave_mask = 0xffffffffu, wg_mask = 0xffffffffu;
     if (row_mask) {
-        unsigned m = (myrow < n_out) ? (unsigned)row_mask[trow] : 0u;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) m |= (unsigned)__shfl_xor((int)m, d, 64);
-        wave_mask = m;
-        if (l == 0) s_wmask[wv] = m;
-        __syncthreads();
-        wg_mask = s_wmask[0] | s_wmask[1] | s_wmask[2] | s_wmask[3];
+        wave_mask = ig_tile_mask(row_mask, myrow, trow, n_out);
+        wg_mask = ig_wg_mask(s_wmask, wave_mask, l, wv);
     }
-    auto next_k = [&](int k) {
-        if (!row_mask) return k + 1;
-        const unsigned rest = (k + 1 < 32) ? (wg_mask >> (k + 1)) : 0u;
-        return rest ? k + 1 + __builtin_ctz(rest) : K;
-    };
-    auto load_src = [&](int k) { return (myrow < n_out && k < K) ? nbr[(size_t)trow * K + k] : -1; };
-    auto wave_uses = [&](int k, int src) { return row_mask ? ((wave_mask >> k) & 1u) != 0u : __ballot(src >= 0) != 0ull; };
+    auto next_k = [&](int k) { return ig_next_k(wg_mask, k, K, row_mask != nullptr); };
+    auto load_src = [&](int k) { return ig_load_src(nbr, myrow, trow, n_out, k, K); };
+    auto wave_uses = [&](int k, int src) { return ig_uses(wave_mask, k, src, row_mask != nullptr); };
     float4 ga[NG], gn[NG];
     auto dma_w = [&](int k, int h, int buf) {             // stage (k, h) -> buffer buf: piece i = wv + 4 e by wave wv
         const float4 *srcp = reinterpret_cast<const float4 *>(Wp) + ((size_t)(k * SL + h) * NI) * 64 + l;
@@ -1029,14 +861,7 @@ __global__ __launch_bounds__(256) void sc_implicit_gemm_pk_kernel(const float *_
                                                  (__attribute__((address_space(3))) void *)(s_w4 + ((size_t)buf * NI + i) * 64), 16, 0, 0);
         }
     };
-    auto fetch_a = [&](float4 (&g)[NG], int h, int src, bool any) {
-        const float4 *rowp = reinterpret_cast<const float4 *>(in + (size_t)max(src, 0) * CinT + h * Cin) + ak;    // pieces ak, ak + 2, ...: see the ownership note
-#pragma unroll
-        for (int u = 0; u < NG; ++u) {
-            g[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (any && src >= 0) g[u] = rowp[2 * u];
-        }
-    };
+    auto fetch_a = [&](float4 (&g)[NG], int h, int src, bool any) { ig_fetch_a<NG>(g, in, CinT, h * Cin, src, ak, any); };
     int k = next_k(-1), h = 0, buf = 0;
     if (k >= K) k = K;
     int src_cur = load_src(k), src_ahead = -1;
@@ -1090,39 +915,7 @@ __global__ __launch_bounds__(256) void sc_implicit_gemm_pk_kernel(const float *_
         h = hn;
         buf ^= 1;
     }
-    const int last = n_out - 1;
-#pragma unroll
-    for (int hh = 0; hh < 2; ++hh) {
-        int orow[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int r = hh * 8 + j;
-            const int row = min(row0 + (r & 3) + 8 * (r >> 2) + 4 * (l >> 5), last);
-            orow[j] = out_row ? out_row[row] : row;
-        }
-#pragma unroll
-        for (int q = 0; q < NT; ++q) {
-            const int col = q * 32 + (l & 31);
-            const int cc = min(col, Cout - 1);
-            const float bv = bias ? bias[cc] : 0.f;
-            float res[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) res[j] = 0.f;
-            if (residual) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) res[j] = residual[(size_t)orow[j] * Cout + cc];
-            }
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int r = hh * 8 + j;
-                const int row = row0 + (r & 3) + 8 * (r >> 2) + 4 * (l >> 5);
-                if (row < n_out && col < Cout) {
-                    const float v = acc[q][r] + bv + res[j];
-                    out[(size_t)orow[j] * Cout + col] = relu ? fmaxf(v, 0.f) : v;
-                }
-            }
-        }
-    }
+    ig_epilogue(acc, row0, ar, ak, n_out, Cout, bias, residual, relu, out, out_row);
 }
 
 // W (K, CinT, Cout) -> the packed order above; one thread per float4
@@ -1171,50 +964,16 @@ __global__ __launch_bounds__(256, 2) void sc_implicit_gemm_wave_kernel(const flo
     const int ar = l & 31, ak = l >> 5;
     const int myrow = row0 + ar;
     const int trow = (out_row && myrow < n_out) ? out_row[myrow] : myrow;
-    const int Co4 = Cout >> 2;
     f32x16 acc[NT];
-#pragma unroll
-    for (int q = 0; q < NT; ++q)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
+    ig_zero(acc);
     unsigned wave_mask = 0xffffffffu;
-    if (row_mask) {                                       // mask-sorted tables: the offsets some row of THIS wave uses
-        unsigned m = (myrow < n_out) ? (unsigned)row_mask[trow] : 0u;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) m |= (unsigned)__shfl_xor((int)m, d, 64);
-        wave_mask = m;
-    }
-    auto next_k = [&](int k) {                            // next offset > k some row of the wave uses (K when none)
-        if (!row_mask) return k + 1;
-        const unsigned rest = (k + 1 < 32) ? (wave_mask >> (k + 1)) : 0u;
-        return rest ? k + 1 + __builtin_ctz(rest) : K;
-    };
-    auto load_src = [&](int k) { return (myrow < n_out && k < K) ? nbr[(size_t)trow * K + k] : -1; };
+    if (row_mask) wave_mask = ig_tile_mask(row_mask, myrow, trow, n_out);     // mask-sorted tables: the offsets some row of THIS wave uses
+    auto next_k = [&](int k) { return ig_next_k(wave_mask, k, K, row_mask != nullptr); };      // the WAVE's offsets
+    auto load_src = [&](int k) { return ig_load_src(nbr, myrow, trow, n_out, k, K); };
     float4 wr[NW], ga[NG], gn[NG];
-    auto fetch_w = [&](int k, int h) {
-#pragma unroll
-        for (int q = 0; q < NW; ++q) {
-            const int e = q * 64 + l, ci = e / CW4, q4 = e - ci * CW4;
-            wr[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (e < Cin * CW4 && q4 < Co4) wr[q] = reinterpret_cast<const float4 *>(Wt + ((size_t)k * CinT + h * Cin + ci) * Cout)[q4];
-        }
-    };
-    auto store_w = [&]() {
-        float4 *dst = reinterpret_cast<float4 *>(Wl);
-#pragma unroll
-        for (int q = 0; q < NW; ++q) {
-            const int e = q * 64 + l;
-            if (e < Cin * CW4) dst[e] = wr[q];
-        }
-    };
-    auto fetch_a = [&](float4 (&g)[NG], int h, int src, bool any) {
-        const float4 *rowp = reinterpret_cast<const float4 *>(in + (size_t)max(src, 0) * CinT + h * Cin) + ak;    // pieces ak, ak + 2, ...: see the ownership note
-#pragma unroll
-        for (int u = 0; u < NG; ++u) {
-            g[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (any && src >= 0) g[u] = rowp[2 * u];
-        }
-    };
+    auto fetch_w = [&](int k, int h) { ig_fetch_w<Cin, CW, 64>(wr, Wt, (size_t)k * CinT + h * Cin, Cout, l); };
+    auto store_w = [&]() { ig_store_w<Cin, CW, 64>(Wl, wr, l); };
+    auto fetch_a = [&](float4 (&g)[NG], int h, int src, bool any) { ig_fetch_a<NG>(g, in, CinT, h * Cin, src, ak, any); };
     int k = next_k(-1), h = 0;
     if (k >= K) k = K;
     int src_cur = load_src(k), src_ahead = -1;
@@ -1241,17 +1000,7 @@ __global__ __launch_bounds__(256, 2) void sc_implicit_gemm_wave_kernel(const flo
             fetch_a(gn, hn, src_next, any_next);
         }
         if (any) {
-            const float *Wb = Wl + (size_t)ak * 4 * CW + ar;
-#pragma unroll
-            for (int u = 0; u < NG; ++u) {
-                const float av[4] = {ga[u].x, ga[u].y, ga[u].z, ga[u].w};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-#pragma unroll
-                    for (int q = 0; q < NT; ++q)
-                        acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[j], Wb[(u * 8 + j) * CW + q * 32], acc[q], 0, 0, 0);
-                }
-            }
+            ig_mma_stage<NT, NG>(acc, ga, Wl + (size_t)ak * 4 * CW + ar);
         }
         if (kn < K) {
             store_w();                                    // (after this stage's last LDS read, in the wave's own order)
@@ -1263,40 +1012,7 @@ __global__ __launch_bounds__(256, 2) void sc_implicit_gemm_wave_kernel(const flo
         k = kn;
         h = hn;
     }
-    const int last = n_out - 1;                           // n_out >= 1 (checked by the launcher)
-    // fused epilogue: (+ bias) (+ residual) (ReLU); sorted tables scatter rows (as in the pipe kernel)
-#pragma unroll
-    for (int hh = 0; hh < 2; ++hh) {
-        int orow[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int r = hh * 8 + j;
-            const int row = min(row0 + (r & 3) + 8 * (r >> 2) + 4 * (l >> 5), last);
-            orow[j] = out_row ? out_row[row] : row;
-        }
-#pragma unroll
-        for (int q = 0; q < NT; ++q) {
-            const int col = q * 32 + (l & 31);
-            const int cc = min(col, Cout - 1);
-            const float bv = bias ? bias[cc] : 0.f;
-            float res[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) res[j] = 0.f;
-            if (residual) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) res[j] = residual[(size_t)orow[j] * Cout + cc];
-            }
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int r = hh * 8 + j;
-                const int row = row0 + (r & 3) + 8 * (r >> 2) + 4 * (l >> 5);
-                if (row < n_out && col < Cout) {
-                    const float v = acc[q][r] + bv + res[j];
-                    out[(size_t)orow[j] * Cout + col] = relu ? fmaxf(v, 0.f) : v;
-                }
-            }
-        }
-    }
+    ig_epilogue(acc, row0, ar, ak, n_out, Cout, bias, residual, relu, out, out_row);
 }
 
 // Input layer (Cin == 4: x, y, z, intensity means; K * 4 <= 128): all K offsets in ONE stage.  The per-offset kernels above
@@ -1315,7 +1031,6 @@ __global__ __launch_bounds__(256) void sc_input_layer_gemm_kernel(const float *_
     float *s_a = s_mem + (size_t)KC * CW;                 // [4 waves][32][KCp]
     const int t = threadIdx.x, l = t & 63, wv = t >> 6;
     const int row0 = blockIdx.x * IG_ROWS + wv * 32;
-    const int last = n_out - 1;
     float *A = s_a + (size_t)wv * 32 * KCp;
     // the wave's 32 x K table entries are contiguous: coalesced, all requested before the first gather
     const int npairs = 32 * K;
@@ -1345,10 +1060,7 @@ __global__ __launch_bounds__(256) void sc_input_layer_gemm_kernel(const float *_
     }
     __syncthreads();
     f32x16 acc[NT];
-#pragma unroll
-    for (int q = 0; q < NT; ++q)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
+    ig_zero(acc);
     const int ar = l & 31, ak = l >> 5;
 #pragma unroll 4
     for (int c0 = 0; c0 < KC; c0 += 2) {
@@ -1359,34 +1071,7 @@ __global__ __launch_bounds__(256) void sc_input_layer_gemm_kernel(const float *_
             acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc[q], 0, 0, 0);
         }
     }
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-#pragma unroll
-        for (int q = 0; q < NT; ++q) {
-            const int col = q * 32 + (l & 31);
-            const int cc = min(col, Cout - 1);
-            const float bv = bias ? bias[cc] : 0.f;
-            float res[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) res[j] = 0.f;
-            if (residual) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const int r = h * 8 + j;
-                    res[j] = residual[(size_t)min(row0 + (r & 3) + 8 * (r >> 2) + 4 * (l >> 5), last) * Cout + cc];
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int r = h * 8 + j;
-                const int row = row0 + (r & 3) + 8 * (r >> 2) + 4 * (l >> 5);
-                if (row < n_out && col < Cout) {
-                    const float v = acc[q][r] + bv + res[j];
-                    out[(size_t)row * Cout + col] = relu ? fmaxf(v, 0.f) : v;
-                }
-            }
-        }
-    }
+    ig_epilogue(acc, row0, ar, ak, n_out, Cout, bias, residual, relu, out, nullptr);
 }
 
 // indice_conv forward / dgrad (with the transposed table and W^T) — spconv.functional indice_conv (Appendix A.3) —
@@ -1395,6 +1080,45 @@ __global__ __launch_bounds__(256) void sc_input_layer_gemm_kernel(const float *_
 static int sc_pk_stage_cin(int Cin) { return Cin == 128 ? 64 : Cin; }
 static bool sc_pk_supported(int K, int Cin, int Cout) {
     return K > 0 && K <= 32 && (Cin == 16 || Cin == 32 || Cin == 64 || Cin == 128) && Cout > 0 && Cout <= IG_MAX_C && (Cout & 3) == 0;
+}
+
+// The five mask-walking kernels share one signature; ig_kernel names the <NT, C4, SL> instance a route runs on a shape (Cin = 4 C4 SL,
+// SL = 2 only for Cin 128).  The wave-private kernel exists for NT <= 2 and one slice, the two-row-tile kernel for NT <= 2, Cin 32 / 64.
+enum IgRoute { IG_PIPE, IG_WAVE, IG_REGA, IG_REGA2, IG_PACKED };
+typedef void (*IgKernel)(const float *, const int *, int, int, int, const float *, const float *, const float *, int, float *, const int *,
+                         const int *);
+
+template <int NT, int C4, int SL>
+static IgKernel ig_kernel(IgRoute route) {
+    switch (route) {
+        case IG_PIPE: return sc_implicit_gemm_pipe_kernel<NT, C4, SL>;
+        case IG_PACKED: return sc_implicit_gemm_pk_kernel<NT, C4, SL>;
+        case IG_WAVE: if constexpr (NT <= 2 && SL == 1) return sc_implicit_gemm_wave_kernel<NT, C4>; else return nullptr;
+        case IG_REGA2: if constexpr (NT <= 2 && SL == 1 && C4 >= 8) return sc_implicit_gemm_rega2_kernel<NT, C4>; else return nullptr;
+        default: return sc_implicit_gemm_rega_kernel<NT, C4, SL>;
+    }
+}
+
+static IgKernel ig_kernel(IgRoute route, int nt, int Cin) {      // nt in 1 .. 4, Cin in {16, 32, 64, 128}
+    switch (nt * 256 + Cin) {
+        case 1 * 256 + 16: return ig_kernel<1, 4, 1>(route);
+        case 2 * 256 + 16: return ig_kernel<2, 4, 1>(route);
+        case 3 * 256 + 16: return ig_kernel<3, 4, 1>(route);
+        case 4 * 256 + 16: return ig_kernel<4, 4, 1>(route);
+        case 1 * 256 + 32: return ig_kernel<1, 8, 1>(route);
+        case 2 * 256 + 32: return ig_kernel<2, 8, 1>(route);
+        case 3 * 256 + 32: return ig_kernel<3, 8, 1>(route);
+        case 4 * 256 + 32: return ig_kernel<4, 8, 1>(route);
+        case 1 * 256 + 64: return ig_kernel<1, 16, 1>(route);
+        case 2 * 256 + 64: return ig_kernel<2, 16, 1>(route);
+        case 3 * 256 + 64: return ig_kernel<3, 16, 1>(route);
+        case 4 * 256 + 64: return ig_kernel<4, 16, 1>(route);
+        case 1 * 256 + 128: return ig_kernel<1, 16, 2>(route);
+        case 2 * 256 + 128: return ig_kernel<2, 16, 2>(route);
+        case 3 * 256 + 128: return ig_kernel<3, 16, 2>(route);
+        case 4 * 256 + 128: return ig_kernel<4, 16, 2>(route);
+        default: return nullptr;
+    }
 }
 
 static int sc_gemm_launch(const float *in_features, const int *nbr, int n_out, int K, int Cin, int Cout, const float *weight,
@@ -1413,61 +1137,38 @@ static int sc_gemm_launch(const float *in_features, const int *nbr, int n_out, i
     static const bool want_wave = getenv("LIDAR_SPCONV_WAVE_KERNEL") != nullptr;      // A/B switch: the barrier-free wave-private kernel
     const size_t lds_wave = (size_t)4 * cin_stage * nt * 32 * sizeof(float);          // one W stage per wave
     const bool use_wave = want_wave && lds_wave <= 65536;                             // (two workgroups per CU)
-#define IGP(NT, C4) do { if (use_pipe) hipLaunchKernelGGL((sc_implicit_gemm_pipe_kernel<NT, C4>), grid, dim3(256), lds, s, in_features, nbr, n_out, K, Cout, weight, bias, residual, relu, out_features, row_mask, out_row); \
-                         else if (use_wave && NT <= 2) hipLaunchKernelGGL((sc_implicit_gemm_wave_kernel<(NT <= 2 ? NT : 1), C4>), grid, dim3(256), lds_wave, s, in_features, nbr, n_out, K, Cout, weight, bias, residual, relu, out_features, row_mask, out_row); \
-                         else hipLaunchKernelGGL((sc_implicit_gemm_rega_kernel<NT, C4>), grid, dim3(256), lds_rega, s, in_features, nbr, n_out, K, Cout, weight, bias, residual, relu, out_features, row_mask, out_row); } while (0)
-#define IGP2(NT, C4) do { if (use_pipe) hipLaunchKernelGGL((sc_implicit_gemm_pipe_kernel<NT, C4, 2>), grid, dim3(256), lds, s, in_features, nbr, n_out, K, Cout, weight, bias, residual, relu, out_features, row_mask, out_row); \
-                          else hipLaunchKernelGGL((sc_implicit_gemm_rega_kernel<NT, C4, 2>), grid, dim3(256), lds_rega, s, in_features, nbr, n_out, K, Cout, weight, bias, residual, relu, out_features, row_mask, out_row); } while (0)
     const bool pipe = (Cout & 3) == 0 && (Cin == 16 || Cin == 32 || Cin == 64 || Cin == 128);
     if ((row_mask || out_row) && (!pipe || K > 32 || !row_mask || !out_row)) return LIDAR_ERR_ARG;
     if (packed && !sc_pk_supported(K, Cin, Cout)) return LIDAR_ERR_ARG;
-    if (packed) {                                         // packed weights: LDS-DMA staging + 128-bit operand reads
-        const size_t lds_pk = (size_t)2 * cin_stage * nt * 32 * sizeof(float);
-#define IGK(NT, C4, SLV) hipLaunchKernelGGL((sc_implicit_gemm_pk_kernel<NT, C4, SLV>), grid, dim3(256), lds_pk, s, in_features, nbr, n_out, K, Cout, packed, bias, residual, relu, out_features, row_mask, out_row)
-#define IGK_NT(C4, SLV) switch (nt) { case 1: IGK(1, C4, SLV); break; case 2: IGK(2, C4, SLV); break; case 3: IGK(3, C4, SLV); break; default: IGK(4, C4, SLV); break; }
-        if (Cin == 16) { IGK_NT(4, 1) } else if (Cin == 32) { IGK_NT(8, 1) } else if (Cin == 64) { IGK_NT(16, 1) } else { IGK_NT(16, 2) }
-#undef IGK_NT
-#undef IGK
-        return lidar_check_launch("lidar_spconv_implicit_gemm(packed)");
-    }
+    auto launch = [&](IgRoute route, dim3 g, size_t bytes, const float *w, const char *label) {
+        const IgKernel kern = ig_kernel(route, nt, Cin);
+        if (!kern) return (int)LIDAR_ERR_ARG;             // an instance that is not built: the route conditions above exclude it
+        hipLaunchKernelGGL(kern, g, dim3(256), bytes, s, in_features, nbr, n_out, K, Cout, w, bias, residual, relu,
+                           out_features, row_mask, out_row);
+        return lidar_check_launch(label);
+    };
+    if (packed)                                           // packed weights: LDS-DMA staging + 128-bit operand reads (two W stage buffers)
+        return launch(IG_PACKED, grid, lds_rega, packed, "lidar_spconv_implicit_gemm(packed)");
     // A/B switch, default OFF: LIDAR_SPCONV_RT2=1 selects the two-row-tile kernel for Cin 32 / 64.  Measured (profiles/r04/
     // spconv_gemm_rt2.log, SECOND stack): 2.89 vs 1.99 ms — at 272 registers one workgroup per CU is left, and this kernel family hides its
     // stage barrier and gather latency behind the OTHER resident workgroup, not behind a software pipeline of its own.
     static const bool rt2_on = getenv("LIDAR_SPCONV_RT2") && atoi(getenv("LIDAR_SPCONV_RT2")) != 0;
-    const bool rt2_off = !rt2_on;
-    if (pipe && !rt2_off && !use_pipe && !use_wave && (Cin == 64 || Cin == 32) && nt <= 2 && n_out >= 8 * 2 * IG_ROWS) {
-        const dim3 grid2(divup(n_out, 2 * IG_ROWS));
-#define IGR2(NT, C4) hipLaunchKernelGGL((sc_implicit_gemm_rega2_kernel<NT, C4>), grid2, dim3(256), lds_rega, s, in_features, nbr, n_out, K, Cout, weight, bias, residual, relu, out_features, row_mask, out_row)
-        if (Cin == 64) { if (nt == 1) IGR2(1, 16); else IGR2(2, 16); }
-        else { if (nt == 1) IGR2(1, 8); else IGR2(2, 8); }
-#undef IGR2
-        return lidar_check_launch("lidar_spconv_implicit_gemm(two row tiles)");
-    }
+    if (pipe && rt2_on && !use_pipe && !use_wave && (Cin == 64 || Cin == 32) && nt <= 2 && n_out >= 8 * 2 * IG_ROWS)
+        return launch(IG_REGA2, dim3(divup(n_out, 2 * IG_ROWS)), lds_rega, weight, "lidar_spconv_implicit_gemm(two row tiles)");
     if (pipe) {
-        const int c4 = Cin / 4;
-#define IGP_NT(C4) switch (nt) { case 1: IGP(1, C4); break; case 2: IGP(2, C4); break; case 3: IGP(3, C4); break; default: IGP(4, C4); break; }
-        if (c4 == 4) { IGP_NT(4) } else if (c4 == 8) { IGP_NT(8) } else if (c4 == 16) { IGP_NT(16) } else {
-            switch (nt) { case 1: IGP2(1, 16); break; case 2: IGP2(2, 16); break; case 3: IGP2(3, 16); break; default: IGP2(4, 16); break; }
-        }
-#undef IGP_NT
-#undef IGP2
-        return lidar_check_launch("lidar_spconv_implicit_gemm(pipe)");
+        if (use_pipe) return launch(IG_PIPE, grid, lds, weight, "lidar_spconv_implicit_gemm(pipe)");
+        if (use_wave && nt <= 2 && Cin != 128) return launch(IG_WAVE, grid, lds_wave, weight, "lidar_spconv_implicit_gemm(pipe)");
+        return launch(IG_REGA, grid, lds_rega, weight, "lidar_spconv_implicit_gemm(pipe)");
     }
-#undef IGP
     if (Cin == 4 && K * 32 <= 14 * 64 && nt <= 2) {       // the network's input layer: one stage for all offsets
         const size_t lds_in = ((size_t)K * 4 * nt * 32 + (size_t)4 * 32 * (K * 4 + 1)) * sizeof(float);
-        if (nt == 1) hipLaunchKernelGGL(sc_input_layer_gemm_kernel<1>, grid, dim3(256), lds_in, s, in_features, nbr, n_out, K, Cout, weight, bias, residual, relu, out_features);
-        else hipLaunchKernelGGL(sc_input_layer_gemm_kernel<2>, grid, dim3(256), lds_in, s, in_features, nbr, n_out, K, Cout, weight, bias, residual, relu, out_features);
+        hipLaunchKernelGGL(nt == 1 ? sc_input_layer_gemm_kernel<1> : sc_input_layer_gemm_kernel<2>, grid, dim3(256), lds_in, s, in_features,
+                           nbr, n_out, K, Cout, weight, bias, residual, relu, out_features);
         return lidar_check_launch("lidar_spconv_implicit_gemm(input layer)");
     }
-#define IG_CASE(NT) hipLaunchKernelGGL(sc_implicit_gemm_kernel<NT>, grid, dim3(256), lds, s, in_features, nbr, n_out, K, Cin, Cout, weight, bias, residual, relu, out_features)
-    switch (nt) {
-        case 1: IG_CASE(1); break;
-        case 2: IG_CASE(2); break;
-        case 3: IG_CASE(3); break;
-        default: IG_CASE(4); break;
-    }
-#undef IG_CASE
+    hipLaunchKernelGGL(nt == 1 ? sc_implicit_gemm_kernel<1> : nt == 2 ? sc_implicit_gemm_kernel<2> : nt == 3 ? sc_implicit_gemm_kernel<3>
+                                                                                                              : sc_implicit_gemm_kernel<4>,
+                       grid, dim3(256), lds, s, in_features, nbr, n_out, K, Cin, Cout, weight, bias, residual, relu, out_features);
     return lidar_check_launch("lidar_spconv_implicit_gemm");
 }
 
