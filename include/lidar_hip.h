@@ -620,6 +620,30 @@ int lidar_anchor_scores(const float *head, long long n_loc, int row_stride, int 
 int lidar_decode_topk(const float *head, int batch, long long locs_per_frame, int row_stride, int box_off, int dir_off,
                       int anchors_per_loc, int num_dir_bins, const long long *top_idx, int k, const float *anchors,
                       float dir_offset, float dir_limit_offset, float period, float *boxes, void *stream);
+/* The box / direction heads at the selected anchors only (csrc/head_rows.hip, csrc/anchor_post.hip).  The reference computes
+ * conv_box and conv_dir_cls on the whole map (pcdet/models/dense_heads/anchor_head_single.py:45-55) and class_agnostic_nms then
+ * gathers box_preds at the top-k indices (pcdet/models/model_utils/model_nms_utils.py:6-25); here the 1x1 product itself runs for
+ * those anchors only.
+ *   lidar_head_rows_supported  C % 4 == 0, 4 <= C <= LIDAR_HEAD_ROWS_MAX_C, anchors_per_loc in [1, 8], num_dir_bins in [0, 4], a part
+ *                              map of part_bytes < 2^31 - 1 bytes.  Host only.
+ *   lidar_head_rows            part0 / part1: n_parts (1 or 2) NHWC maps of frames_per_part frames x locs_per_frame rows x C floats
+ *                              (16-byte aligned); frame f lives in part f / frames_per_part.  head_wt (C, ldw) row-major and head_b
+ *                              (ldw) are the merged head's weight and bias; anchor a of a location reads columns box_off + 7 a .. + 7
+ *                              and dir_off + num_dir_bins a .. + num_dir_bins.  idx: (batch, k) int64 per-frame anchor ids
+ *                              (loc * anchors_per_loc + a, inside [0, locs_per_frame * anchors_per_loc): the caller's duty), or NULL
+ *                              = every anchor in order (k must be locs_per_frame * anchors_per_loc).
+ *                              -> out (batch, k, 7 + num_dir_bins) logits [7 box residuals | direction logits].  A value depends
+ *                              only on its row and its weight column (fixed summation order, no atomics): the same anchor gives the
+ *                              same bits at any list position, frame, part and in either mode.  batch == 0 or k == 0: nothing written.
+ *   lidar_decode_topk_rows     lidar_decode_topk reading such compact logits (batch, k, 7 + num_dir_bins) instead of the head map:
+ *                              the same device function, bit-equal boxes for bit-equal logits. */
+#define LIDAR_HEAD_ROWS_MAX_C 1024
+int lidar_head_rows_supported(int C, int anchors_per_loc, int num_dir_bins, long long part_bytes);
+int lidar_head_rows(const float *part0, const float *part1, int n_parts, int frames_per_part, long long locs_per_frame, int C,
+                    const float *head_wt, int ldw, const float *head_b, int box_off, int dir_off, int anchors_per_loc, int num_dir_bins,
+                    const long long *idx, int batch, long long k, float *out, void *stream);
+int lidar_decode_topk_rows(const float *logits, int batch, int k, int num_dir_bins, const long long *top_idx, const float *anchors,
+                           float dir_offset, float dir_limit_offset, float period, float *boxes, void *stream);
 /* Exact top-k of the masked scores that feed NMS (reference: torch.topk(box_scores, k = min(NMS_PRE_MAXSIZE, n)) in
  * class_agnostic_nms, pcdet/models/model_utils/model_nms_utils.py:9-11) for a whole batch, deterministic — descending score, ties by
  * ascending anchor index (torch.topk leaves ties unspecified) — in 3 launches, no host synchronisation (csrc/topk.hip).

@@ -149,6 +149,9 @@ SIGNATURES = {
     "lidar_decode_topk": (i32, [vp, i32, C.c_longlong, i32, i32, i32, i32, i32, vp, i32, vp, f32, f32, f32, vp, vp]),
     "lidar_topk_workspace_bytes": (sz, [i32, C.c_longlong]),
     "lidar_topk_workspace_init": (i32, [vp, sz, i32, C.c_longlong, vp]),
+    "lidar_head_rows_supported": (i32, [i32, i32, i32, C.c_longlong]),
+    "lidar_head_rows": (i32, [vp, vp, i32, i32, C.c_longlong, i32, vp, i32, vp, i32, i32, i32, i32, vp, i32, C.c_longlong, vp, vp]),
+    "lidar_decode_topk_rows": (i32, [vp, i32, i32, i32, vp, vp, f32, f32, f32, vp, vp]),
     "lidar_anchor_scores_hist": (i32, [vp, i32, C.c_longlong, i32, i32, i32, i32, f32, vp, vp, vp, sz, vp]),
     "lidar_topk_desc": (i32, [vp, i32, C.c_longlong, i32, f32, f32, i32, vp, vp, vp, vp, sz, vp]),
     "lidar_post_nms_gather": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, C.c_longlong, i32, i32, vp, vp, vp, vp, vp]),

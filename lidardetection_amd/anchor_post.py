@@ -96,6 +96,62 @@ def decode_topk(head, top_idx, anchors, anchors_per_loc, box_off, dir_off, num_d
     return boxes
 
 
+def head_rows_supported(C, anchors_per_loc, num_dir_bins, part_bytes=0):
+    """lidar_head_rows takes C % 4 == 0, 4 <= C <= 1024, 1 <= A <= 8, 0 <= nbins <= 4 and part maps under 2^31 - 1 bytes"""
+    return bool(_lib.lib().lidar_head_rows_supported(int(C), int(anchors_per_loc), int(num_dir_bins), int(part_bytes)))
+
+
+def head_rows(parts, head_wt, head_b, anchors_per_loc, box_off, dir_off, num_dir_bins, top_idx=None, batch=None):
+    """The box / direction columns of the merged 1x1 head at the anchors top_idx (B, k) int64 names, or at every anchor in order
+    (top_idx=None): -> logits (B, k, 7 + num_dir_bins) = [7 residuals | direction logits] (csrc/head_rows.hip).
+    parts: one or two contiguous NHWC maps (frames, ..., C) holding the same number of frames each, frame f in part f // frames;
+    head_wt (C, N) / head_b (N): the merged head's weight and bias.  The value of an anchor depends on its row and its weight
+    columns only: gathered and all-anchors results are bit-equal, as are repeated indices and the same row in another part."""
+    parts = list(parts)
+    _lib.require_cuda(*parts, head_wt, head_b)
+    if not 1 <= len(parts) <= 2 or any(p.shape != parts[0].shape or not p.is_contiguous() for p in parts):
+        raise _lib.LidarHipError("head_rows: one or two contiguous NHWC part maps of one shape")
+    fpp, C = parts[0].shape[0], parts[0].shape[-1]
+    locs = parts[0].numel() // max(fpp * C, 1)
+    B = fpp * len(parts) if batch is None else int(batch)
+    nc = 7 + int(num_dir_bins)
+    if not head_wt.is_contiguous() or head_wt.dim() != 2 or head_wt.shape[0] != C or head_b.numel() != head_wt.shape[1]:
+        raise _lib.LidarHipError("head_rows: head_wt must be a contiguous (C, N) matrix and head_b its (N,) bias")
+    if not head_rows_supported(C, anchors_per_loc, num_dir_bins, parts[0].numel() * 4):
+        raise _lib.LidarHipError(f"head_rows: unsupported shape (C {C}, A {anchors_per_loc}, bins {num_dir_bins}, "
+                                 f"{parts[0].numel() * 4} bytes per part)")
+    if top_idx is None:
+        k, idx_ptr = locs * int(anchors_per_loc), None
+    else:
+        _lib.require_cuda(top_idx, allow=(torch.int64,))
+        if top_idx.dtype != torch.int64 or top_idx.dim() != 2 or top_idx.shape[0] != B or not top_idx.is_contiguous():
+            raise _lib.LidarHipError("head_rows: top_idx must be a contiguous int64 (B, k) tensor")
+        k, idx_ptr = top_idx.shape[1], _lib.ptr(top_idx)
+    out = torch.empty((B, k, nc), dtype=torch.float32, device=parts[0].device)
+    _lib.check(_lib.lib().lidar_head_rows(_lib.ptr(parts[0]), _lib.ptr(parts[-1]), len(parts), fpp, locs, C, _lib.ptr(head_wt),
+                                          head_wt.shape[1], _lib.ptr(head_b), int(box_off), int(dir_off), int(anchors_per_loc),
+                                          int(num_dir_bins), idx_ptr, B, k, _lib.ptr(out), _lib.stream()), "lidar_head_rows")
+    return out
+
+
+def decode_topk_rows(logits, top_idx, anchors, num_dir_bins, dir_offset, dir_limit_offset):
+    """decode_topk on head_rows' compact logits (B, k, 7 + num_dir_bins): -> boxes (B, k, 7), bit-equal to decode_topk on a head map
+    holding the same logits (one device function)."""
+    _lib.require_cuda(logits, top_idx, anchors, allow=(torch.int64,))
+    _lib.require_last(anchors, 7, "anchors")
+    B, k = top_idx.shape
+    if top_idx.dtype != torch.int64 or not top_idx.is_contiguous():
+        raise _lib.LidarHipError("decode_topk_rows: top_idx must be contiguous int64 (B, k)")
+    if logits.dtype != torch.float32 or not logits.is_contiguous() or tuple(logits.shape) != (B, k, 7 + int(num_dir_bins)):
+        raise _lib.LidarHipError("decode_topk_rows: logits must be contiguous float32 (B, k, 7 + num_dir_bins)")
+    boxes = torch.empty((B, k, 7), dtype=torch.float32, device=logits.device)
+    period = float(np.float32(2 * np.pi / num_dir_bins)) if num_dir_bins else 1.0
+    _lib.check(_lib.lib().lidar_decode_topk_rows(_lib.ptr(logits), B, k, int(num_dir_bins), _lib.ptr(top_idx), _lib.ptr(anchors),
+                                                 float(np.float32(dir_offset)), float(np.float32(dir_limit_offset)), period,
+                                                 _lib.ptr(boxes), _lib.stream()), "lidar_decode_topk_rows")
+    return boxes
+
+
 def post_nms_gather(boxes, top_scores, top_idx, labels_all, keep, num_keep, post):
     """-> out_boxes (B, post, 7), out_scores (B, post), out_labels (B, post) int64 (class + 1), out_num (B) int32: the first `post`
     NMS survivors of every frame, in one launch (model_nms_utils.py:19-25 + detector3d_template.py:236-262, batched)."""

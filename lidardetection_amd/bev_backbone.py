@@ -1,16 +1,21 @@
 """Inference fast path of the dense BEV backbone + anchor head.
 
-The convolutions stay stock torch (MIOpen, fp32, channels-last).  What changes is everything around them:
+FoldedBEVBackbone evaluates the reference's BaseBEVBackbone + AnchorHeadSingle in eval mode, channels-last fp32:
   * eval-mode BatchNorm2d is folded into the preceding convolution (scale -> weights, shift -> bias) — the
     reference's Conv2d/BN/ReLU triplets (pcdet/models/backbones_2d/base_bev_backbone.py:34-45) and
     ConvTranspose2d/BN/ReLU deblocks (base_bev_backbone.py:51-57);
-  * shift + ReLU run as ONE in-place HIP pass (`lidar_bias_act_nhwc`) instead of a BN pass and a ReLU pass;
-  * the deblock epilogues write directly into their channel slice of the concatenated map
-    (base_bev_backbone.py:103), so `torch.cat` disappears;
-  * ConvTranspose2d with kernel == stride (every deblock of the reference configs) is evaluated as one plain GEMM on
-    the NHWC map (rocBLAS/hipBLASLt through torch.mm) and the epilogue does the pixel shuffle;
-  * the three 1x1 heads of AnchorHeadSingle (pcdet/models/dense_heads/anchor_head_single.py:18-33,45-55) read the
-    384-channel map once (one merged GEMM, torch.addmm) instead of three times.
+  * the first layer runs from the pillars as a sparse implicit GEMM when it can (csrc/pillar.hip), the stride-1 3x3 layers as
+    Winograd F(4x4, 3x3) / F(2x2, 3x3) on the fp32 MFMA with shift + ReLU in the kernel (csrc/wino43_conv.hip, csrc/wino_conv.hip);
+    the remaining (strided) convolutions stay stock torch (MIOpen) followed by ONE in-place shift + ReLU pass
+    (`lidar_bias_act_nhwc`);
+  * ConvTranspose2d deblocks with kernel == stride are GEMMs on the NHWC map that write their channel slice of the concatenated
+    map (base_bev_backbone.py:103) directly, so `torch.cat` disappears: stride > 1 on csrc/deconv_gemm.hip (pixel shuffle in the
+    epilogue), stride 1 as one hipBLASLt call with the map's row pitch (csrc/dense_gemm.hip);
+  * a batch of 16 and more runs as two part-batches on two streams (_merged_split);
+  * the three 1x1 heads of AnchorHeadSingle (pcdet/models/dense_heads/anchor_head_single.py:18-33,45-55) are one merged
+    hipBLASLt GEMM on the concatenated map — or, for a caller that reads box and direction at selected anchors only
+    (merged(defer=True)), the class columns alone, the rest computed later for just those anchors (DeferredHead,
+    csrc/head_rows.hip).
 Results match the unfolded modules to fp32 rounding (folding re-associates one multiply); tests assert 1e-4.
 """
 import ctypes as C
@@ -43,6 +48,34 @@ _SPLIT = [int(os.environ.get("LIDAR_BEV_SPLIT", "2"))]            # part-batches
 _WINO = [os.environ.get("LIDAR_BEV_WINO", "1") != "0"]            # stride-1 3x3 layers on csrc/wino_conv.hip (0: MIOpen + epilogue pass)
 _DECONV = [os.environ.get("LIDAR_BEV_DECONV", "1") != "0"]        # stride > 1 deblocks on csrc/deconv_gemm.hip (0: library GEMM + pixel-shuffle pass)
 _SPARSE_FIRST = [os.environ.get("LIDAR_BEV_SPARSE_FIRST", "1") != "0"]   # first layer straight from the pillars (0: dense canvas + MIOpen)
+_HEAD_DEFER = [os.environ.get("LIDAR_HEAD_DEFER", "1") != "0"]    # merged(defer=True): cls columns now, box / dir at the selected anchors later (0: all columns)
+
+
+class DeferredHead:
+    """What a cls-only head map (FoldedBEVBackbone.merged(defer=True)) needs to produce its box / direction columns later: the
+    concat buffer(s) it was computed from (frame f in parts[f // frames_per_part]), the full head weight and bias with the column
+    offsets of the box and direction heads, and the generation of every buffer at that time.  The buffers belong to the backbone and
+    are overwritten by its next forward; rows() refuses to read them once that has happened."""
+
+    def __init__(self, owner, slots, parts, head_wt, head_b, box_off, dir_off):
+        self.owner, self.slots, self.parts = owner, tuple(slots), tuple(parts)
+        self.gens = tuple(owner._cat_gen[s] for s in slots)
+        self.head_wt, self.head_b, self.box_off, self.dir_off = head_wt, head_b, int(box_off), int(dir_off)
+        self.frames_per_part = parts[0].shape[0]
+
+    def stale(self):
+        o = self.owner
+        return any(o._cat_gen.get(s) != g or o._cats.get(s) is not p for s, g, p in zip(self.slots, self.gens, self.parts))
+
+    def rows(self, anchors_per_loc, num_dir_bins, top_idx=None, who="DeferredHead.rows"):
+        """-> logits (B, k, 7 + num_dir_bins) at the anchors top_idx (B, k) names, or at every anchor (anchor_post.head_rows)"""
+        from . import anchor_post
+        if self.stale():
+            raise _lib.LidarHipError(f"{who}: this deferred head is stale — the backbone's concat buffers it reads its box / direction "
+                                     "columns from were overwritten by a later forward (post-process a head before the next "
+                                     "backbone_head call, or run with LIDAR_HEAD_DEFER=0)")
+        return anchor_post.head_rows([p.permute(0, 2, 3, 1) for p in self.parts], self.head_wt, self.head_b, anchors_per_loc,
+                                     self.box_off, self.dir_off, num_dir_bins, top_idx)
 
 
 def _lt_gemm(a_ptr, M, K, w_kn, bias, relu, d_ptr, ldd, device):
@@ -306,7 +339,11 @@ class FoldedBEVBackbone:
             self.head_wt = torch.cat([h.weight.detach().flatten(1) for h in heads], 0).t().contiguous()   # (C_in, sum C_head)
             self.head_b = torch.cat([h.bias.detach() if h.bias is not None else h.weight.new_zeros(h.weight.shape[0])
                                      for h in heads], 0).contiguous()
+            # the first head alone (cls when the heads are given as [cls, box, dir]): what merged(defer=True) computes for every row
+            self.head0_wt = self.head_wt[:, :self.head_split[0]].contiguous()
+            self.head0_b = self.head_b[:self.head_split[0]].contiguous()
         self._cats = {}                    # concat buffers, one per (slot of a split forward, shape)
+        self._cat_gen = {}                 # slot -> how often features() has (re)written that buffer (DeferredHead.stale)
         self._streams = None
         # the first layer as a sparse implicit GEMM over the pillars (csrc/pillar.hip lidar_pillar_conv_table): (k*k, Cin, Cout) weights
         self._first_sparse = None
@@ -360,6 +397,7 @@ class FoldedBEVBackbone:
                 if cat is None or cat.shape != shape or cat.device != x.device:
                     cat = self._cats[slot] = torch.empty(shape, dtype=torch.float32, device=x.device,
                                                          memory_format=torch.channels_last)
+                self._cat_gen[slot] = self._cat_gen.get(slot, 0) + 1      # about to be overwritten: deferred heads reading it are stale
             if y is not None:
                 bias_act_(y, up.shift, out=cat, out_offset=off)
             else:
@@ -383,9 +421,22 @@ class FoldedBEVBackbone:
     def stale(self):
         return params_key(self.sources) != self.source_key
 
-    def merged(self, canvas):
+    def _defer_ok(self, cat_bytes):
+        """merged(defer=True) can defer: the switch is on, there is something after the first head to defer, and lidar_head_rows
+        takes this channel count and part size (the anchor layout is the caller's to check: anchor_post.head_rows_supported)"""
+        from . import anchor_post
+        return (_HEAD_DEFER[0] and len(self.head_split) > 1 and self.head_wt.is_cuda
+                and anchor_post.head_rows_supported(self.head_wt.shape[0], 1, 0, cat_bytes))
+
+    def merged(self, canvas, defer=False):
         """-> the merged head output (B, H, W, sum C_head), channels [cls | box | dir] as the heads were given.
-        canvas: the channels-last BEV map, or a pillar_ops.PillarMap (the first layer then runs from the pillars when it can)."""
+        canvas: the channels-last BEV map, or a pillar_ops.PillarMap (the first layer then runs from the pillars when it can).
+        defer=True (for a caller that reads the later heads at selected anchors only, and passes the heads as [cls, box, dir]):
+        only the FIRST head's columns are computed, (B, H, W, C_head[0]), and the returned tensor carries a DeferredHead as its
+        plain attribute `deferred`, from which the other columns are computed at the anchors that need them
+        (DeferredHead.rows).  That record reads this backbone's concat buffers: it is valid until the next forward of this
+        backbone, and stale (an error, never the new batch's values) afterwards.  With LIDAR_HEAD_DEFER=0, or where
+        lidar_head_rows does not support the shape, defer=True returns the full head like defer=False."""
         first_done = False
         if not torch.is_tensor(canvas):
             if self.sparse_first_ok():
@@ -394,13 +445,17 @@ class FoldedBEVBackbone:
                 canvas = canvas.dense()
         B = canvas.shape[0]
         if 1 < _SPLIT[0] <= 2 and canvas.is_cuda and B % _SPLIT[0] == 0 and B // _SPLIT[0] >= _SPLIT_MIN[0]:   # (4-frame parts lost in r03: PV-RCNN bs 8 16.0 -> 17.5 ms)
-            return self._merged_split(canvas, _SPLIT[0], first_done)
+            return self._merged_split(canvas, _SPLIT[0], first_done, defer)
         cat = self.features(canvas, first_done=first_done)
         B, C, H, W = cat.shape
-        out = rows_gemm(cat.permute(0, 2, 3, 1).reshape(B * H * W, C), self.head_wt, self.head_b)     # 1x1 heads = one GEMM
-        return out.view(B, H, W, -1)
+        defer = bool(defer) and self._defer_ok(cat.numel() * 4)
+        wt, b = (self.head0_wt, self.head0_b) if defer else (self.head_wt, self.head_b)
+        out = rows_gemm(cat.permute(0, 2, 3, 1).reshape(B * H * W, C), wt, b).view(B, H, W, -1)       # 1x1 heads = one GEMM
+        if defer:
+            out.deferred = DeferredHead(self, (0,), (cat,), self.head_wt, self.head_b, self.head_split[0], sum(self.head_split[:2]))
+        return out
 
-    def _merged_split(self, canvas, n, first_done=False):
+    def _merged_split(self, canvas, n, first_done=False, defer=False):
         """The same forward as n part-batches on n streams: the convolutions are bound by the matrix cores (0.8 of the fp32 MFMA peak,
         < 0.5 TB/s of HBM traffic) and everything around them — MIOpen's zero-fill of each output, the shift + ReLU pass, the pixel
         shuffles — by HBM, and within one batch they are strictly serial; two part-batches let one's passes run under the other's
@@ -411,20 +466,26 @@ class FoldedBEVBackbone:
         cur = torch.cuda.current_stream(dev)
         self._streams = _side_streams(dev, n)
         B, hb = canvas.shape[0], canvas.shape[0] // n
-        out = None
+        out, cats, wt, b = None, [], self.head_wt, self.head_b
         for i, st in enumerate(self._streams):
             st.wait_stream(cur)
             with torch.cuda.stream(st):
                 cat = self.features(canvas[i * hb:(i + 1) * hb], slot=i + 1, first_done=first_done)
+                cats.append(cat)
                 _, C, H, W = cat.shape
                 if out is None:
+                    defer = bool(defer) and self._defer_ok(cat.numel() * 4)
+                    if defer:
+                        wt, b = self.head0_wt, self.head0_b
                     with torch.cuda.stream(cur):                       # owned by the caller's stream, written by the side streams
-                        out = torch.empty((B, H, W, self.head_wt.shape[1]), dtype=torch.float32, device=dev)
+                        out = torch.empty((B, H, W, wt.shape[1]), dtype=torch.float32, device=dev)
                     st.wait_stream(cur)
                 out.record_stream(st)
-                rows_gemm(cat.permute(0, 2, 3, 1).reshape(hb * H * W, C), self.head_wt, self.head_b, out=out[i * hb:(i + 1) * hb].view(hb * H * W, -1))
+                rows_gemm(cat.permute(0, 2, 3, 1).reshape(hb * H * W, C), wt, b, out=out[i * hb:(i + 1) * hb].view(hb * H * W, -1))
         for st in self._streams:
             cur.wait_stream(st)
+        if defer:
+            out.deferred = DeferredHead(self, range(1, n + 1), cats, self.head_wt, self.head_b, self.head_split[0], sum(self.head_split[:2]))
         return out
 
     def __call__(self, canvas):

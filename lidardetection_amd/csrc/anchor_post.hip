@@ -31,6 +31,34 @@ __global__ __launch_bounds__(256) void anchor_scores_kernel(const float *__restr
     labels[i] = (unsigned char)bl;
 }
 
+// One box: ResidualCoder.decode_torch of the 7 residuals t on the anchor an, then the direction-bin correction from the nbins
+// logits d (d is not read for nbins == 0).  The one copy of this arithmetic: decode_topk_kernel (logits inside the merged head map)
+// and decode_topk_rows_kernel (compact logits of lidar_head_rows) both call it, so equal logits give equal bits.
+__device__ __forceinline__ void decode_box(const float *__restrict__ t, const float *__restrict__ d, int nbins, const float *__restrict__ an,
+                                           float dir_offset, float dir_limit_offset, float period, float *__restrict__ o) {
+    const float xa = an[0], ya = an[1], za = an[2], dxa = an[3], dya = an[4], dza = an[5], ra = an[6];
+    const float diagonal = sqrtf(dxa * dxa + dya * dya);
+    o[0] = t[0] * diagonal + xa;
+    o[1] = t[1] * diagonal + ya;
+    o[2] = t[2] * dza + za;
+    o[3] = expf(t[3]) * dxa;
+    o[4] = expf(t[4]) * dya;
+    o[5] = expf(t[5]) * dza;
+    float rg = t[6] + ra;
+    if (nbins > 0) {
+        int lab = 0;
+        float bestd = d[0];
+        for (int c = 1; c < nbins; ++c)
+            if (d[c] > bestd) { bestd = d[c]; lab = c; }
+        const float inv_period = 1.0f / period;                 // torch: tensor / python scalar = tensor * (1 / scalar)
+        const float val = rg - dir_offset;
+        const float fl = floorf(val * inv_period + dir_limit_offset);
+        const float dir_rot = val - fl * period;
+        rg = dir_rot + dir_offset + period * (float)lab;
+    }
+    o[6] = rg;
+}
+
 __global__ __launch_bounds__(256) void decode_topk_kernel(const float *__restrict__ head, int batch, long long locs_per_frame,
                                                           int row_stride, int box_off, int dir_off, int A, int nbins,
                                                           const long long *__restrict__ top_idx, int k,
@@ -43,31 +71,19 @@ __global__ __launch_bounds__(256) void decode_topk_kernel(const float *__restric
     const long long loc = idx / A;
     const int a = (int)(idx - loc * A);
     const float *row = head + ((long long)b * locs_per_frame + loc) * row_stride;
-    const float *t = row + box_off + a * 7;
-    const float *an = anchors + idx * 7;
-    const float xa = an[0], ya = an[1], za = an[2], dxa = an[3], dya = an[4], dza = an[5], ra = an[6];
-    const float diagonal = sqrtf(dxa * dxa + dya * dya);
-    float *o = boxes + j * 7;
-    o[0] = t[0] * diagonal + xa;
-    o[1] = t[1] * diagonal + ya;
-    o[2] = t[2] * dza + za;
-    o[3] = expf(t[3]) * dxa;
-    o[4] = expf(t[4]) * dya;
-    o[5] = expf(t[5]) * dza;
-    float rg = t[6] + ra;
-    if (nbins > 0) {
-        const float *d = row + dir_off + a * nbins;
-        int lab = 0;
-        float bestd = d[0];
-        for (int c = 1; c < nbins; ++c)
-            if (d[c] > bestd) { bestd = d[c]; lab = c; }
-        const float inv_period = 1.0f / period;                 // torch: tensor / python scalar = tensor * (1 / scalar)
-        const float val = rg - dir_offset;
-        const float fl = floorf(val * inv_period + dir_limit_offset);
-        const float dir_rot = val - fl * period;
-        rg = dir_rot + dir_offset + period * (float)lab;
-    }
-    o[6] = rg;
+    decode_box(row + box_off + a * 7, row + dir_off + a * nbins, nbins, anchors + idx * 7, dir_offset, dir_limit_offset, period,
+               boxes + j * 7);
+}
+
+// the same on compact logits (batch, k, 7 + nbins) = [7 residuals | nbins direction logits] of the anchors top_idx names
+__global__ __launch_bounds__(256) void decode_topk_rows_kernel(const float *__restrict__ logits, long long n, int nbins,
+                                                               const long long *__restrict__ top_idx, const float *__restrict__ anchors,
+                                                               float dir_offset, float dir_limit_offset, float period,
+                                                               float *__restrict__ boxes) {
+    const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (j >= n) return;
+    const float *t = logits + j * (7 + nbins);
+    decode_box(t, t + 7, nbins, anchors + top_idx[j] * 7, dir_offset, dir_limit_offset, period, boxes + j * 7);
 }
 
 LIDAR_EXPORT int lidar_anchor_scores(const float *head, long long n_loc, int row_stride, int cls_off, int anchors_per_loc,
@@ -100,6 +116,20 @@ LIDAR_EXPORT int lidar_decode_topk(const float *head, int batch, long long locs_
                        locs_per_frame, row_stride, box_off, dir_off, anchors_per_loc, num_dir_bins, top_idx, k, anchors, dir_offset,
                        dir_limit_offset, period, boxes);
     return lidar_check_launch("lidar_decode_topk");
+}
+
+LIDAR_EXPORT int lidar_decode_topk_rows(const float *logits, int batch, int k, int num_dir_bins, const long long *top_idx,
+                                        const float *anchors, float dir_offset, float dir_limit_offset, float period, float *boxes,
+                                        void *stream) {
+    if (batch < 0 || k < 0 || num_dir_bins < 0) return LIDAR_ERR_ARG;
+    if (batch == 0 || k == 0) return LIDAR_OK;
+    if (!logits || !top_idx || !anchors || !boxes) return LIDAR_ERR_ARG;
+    const long long n = (long long)batch * k;
+    const long long blocks = (n + 255) / 256;
+    if (blocks > 0x7fffffffll) return LIDAR_ERR_ARG;
+    hipLaunchKernelGGL(decode_topk_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, logits, n, num_dir_bins, top_idx,
+                       anchors, dir_offset, dir_limit_offset, period, boxes);
+    return lidar_check_launch("lidar_decode_topk_rows");
 }
 
 // Everything between the NMS keep lists and the detector's output in ONE launch (the reference does it per sample with index

@@ -171,14 +171,28 @@ class PointPillarKITTI(nn.Module):
             return dense(feat, vox["voxel_coords"], total)
         return pillar_ops.pillar_scatter(feat, vox["voxel_coords"], self.B, self.nx, self.ny, num_voxels_dev=total)
 
-    def backbone_head(self, canvas):
+    def backbone_head(self, canvas, defer=None):
+        """-> (head,) from the folded backbone.  By default (defer=None: on unless LIDAR_HEAD_DEFER=0, where lidar_head_rows supports
+        the head) `head` is the DEFERRED head: the (B, H, W, 18) class map, carrying the record (`head.deferred`,
+        bev_backbone.DeferredHead) from which post_process computes the box and direction logits at the NMS_PRE_MAXSIZE anchors it
+        selects, and split_heads at every anchor, with one kernel and bit-equal values.  The record reads the backbone's concat
+        buffers, which the NEXT backbone_head call overwrites: post-process (or split) a head before calling backbone_head again;
+        doing it afterwards raises LidarHipError instead of reading the new batch.  Calling backbone_head repeatedly and
+        post-processing the last result is fine.  defer=False: the full (B, H, W, 18 + 42 + 12) map, valid for as long as it lives."""
         if self.fold_bn:
-            return (self._bev_folded().merged(canvas),)  # (B, H, W, 18 + 42 + 12): consumed in place by post_process
+            if defer is None:
+                defer = anchor_post.head_rows_supported(self.conv_cls.in_channels, self.num_anchor_per_loc, self.num_dir_bins)
+            return (self._bev_folded().merged(canvas, defer=bool(defer)),)     # consumed in place by post_process
         return self.backbone_head_stock(canvas if torch.is_tensor(canvas) else canvas.dense())
 
     def split_heads(self, head):
-        """merged head (B, H, W, C) -> cls (B, N, 3), box (B, N, 7), dir (B, N, 2) as the reference's view() calls give"""
+        """merged head (B, H, W, C) -> cls (B, N, 3), box (B, N, 7), dir (B, N, 2) as the reference's view() calls give.  A deferred
+        head (backbone_head) gets its box and direction logits for every anchor from the kernel post_process uses (same bits)."""
         a = self.num_anchor_per_loc
+        rec = getattr(head, "deferred", None)
+        if rec is not None:
+            logits = rec.rows(a, self.num_dir_bins, None, "split_heads")                        # (B, N, 7 + bins)
+            return head.reshape(self.B, -1, self.num_class), logits[..., :7], logits[..., 7:]
         cls, box, dirs = torch.split(head, [a * self.num_class, a * 7, a * self.num_dir_bins], dim=-1)
         return (cls.reshape(self.B, -1, self.num_class), box.reshape(self.B, -1, 7), dirs.reshape(self.B, -1, self.num_dir_bins))
 
@@ -304,6 +318,9 @@ class PointPillarKITTI(nn.Module):
         a = self.num_anchor_per_loc
         n = head.shape[1] * head.shape[2] * a if head.dim() == 4 else head.shape[1] * a
         k = min(self.nms_pre, n)
+        rec = getattr(head, "deferred", None)     # backbone_head's class-only map: box / dir logits at the selected anchors only
+        if rec is not None and rec.stale():
+            rec.rows(a, self.num_dir_bins, None, "post_process")                                # raises: names the cause
         if anchor_post.topk_supported(n, k, self.score_thresh, hist=True):   # scores + histogram, collect, finalize: 3 launches, ties by ascending anchor index
             ws = anchor_post.topk_workspace(head.shape[0], n, head.device)
             try:
@@ -316,9 +333,13 @@ class PointPillarKITTI(nn.Module):
             masked, labels_all = anchor_post.anchor_scores(head, a, self.num_class, self.score_thresh, cls_off=0)
             top_scores, top_idx = torch.topk(masked, k, dim=1)        # sorted descending == nms_gpu's sort
             counts = (top_scores >= self.score_thresh).sum(dim=1).to(torch.int32)
-        boxes = anchor_post.decode_topk(head, top_idx, self.anchors, a, box_off=a * self.num_class,
-                                        dir_off=a * (self.num_class + 7), num_dir_bins=self.num_dir_bins,
-                                        dir_offset=self.dir_offset, dir_limit_offset=self.dir_limit_offset)
+        if rec is not None:
+            logits = rec.rows(a, self.num_dir_bins, top_idx.contiguous(), "post_process")     # (B, k, 7 + bins): csrc/head_rows.hip
+            boxes = anchor_post.decode_topk_rows(logits, top_idx, self.anchors, self.num_dir_bins, self.dir_offset, self.dir_limit_offset)
+        else:
+            boxes = anchor_post.decode_topk(head, top_idx, self.anchors, a, box_off=a * self.num_class,
+                                            dir_off=a * (self.num_class + 7), num_dir_bins=self.num_dir_bins,
+                                            dir_offset=self.dir_offset, dir_limit_offset=self.dir_limit_offset)
         post = min(self.nms_post, k)
         keep, num = iou3d_nms_cuda.nms_batch(boxes, counts, self.nms_thresh, max_keep=post)   # survivors past `post` are dropped anyway
         return anchor_post.post_nms_gather(boxes, top_scores, top_idx, labels_all, keep, num, post)   # one launch (was 13 torch kernels)

@@ -149,7 +149,7 @@ def pp_kernels(model, pts, offs):
         total = vox["voxel_offsets"][model.B:model.B + 1]
         pfn_ms, _ = _events(lambda: pillar_ops.pillar_vfe(vox["voxels"], vox["voxel_num_points"], vox["voxel_coords"], w, s, t,
                                                           model.voxel_size, model.pc_range, num_voxels_dev=total), n=20)
-        (head,) = model.backbone_head(model.vfe_scatter(vox))
+        (head,) = model.backbone_head(model.vfe_scatter(vox), defer=False)     # the full head map: decode_topk below reads it in place
         a = model.num_anchor_per_loc
         masked, _ = anchor_post.anchor_scores(head, a, model.num_class, model.score_thresh, cls_off=0)
         top_scores, top_idx = torch.topk(masked, model.nms_pre, dim=1)
