@@ -805,7 +805,8 @@ int lidar_proposal_target(const float *rois, const float *roi_scores, const long
  * Supported (lidar_augment_supported, pure host; everything else is refused with LIDAR_ERR_ARG before any launch): 3 <= C <= 8,
  * 1 <= groups <= 8, 0 <= per_group <= 64, max_gt + groups * per_group <= 512; batch >= 0 (0 launches nothing); frames of 0 points
  * and frames with gt_counts 0 are valid.  With C == 4 the point arrays, and always out_gt_boxes, must be 16-byte aligned.
- * NOT built: the `locations` / `rotations_y` multi-frame extras of the reference, and velocity columns (boxes are 7 wide). */
+ * NOT built: carrying the `locations` / `rotations_y` multi-frame extras of the reference through the augmentation (their consumers,
+ * lidar_point_targets_mf and lidar_multiframe_enlarged_boxes, are below), and velocity columns (boxes are 7 wide). */
 #define LIDAR_AUGMENT_MAX_FEATURES 8
 #define LIDAR_AUGMENT_MAX_GROUPS 8
 #define LIDAR_AUGMENT_MAX_PER_GROUP 64
@@ -930,6 +931,50 @@ int lidar_point_loss_backward(const float *point_cls_preds, const float *point_b
                               const long long *point_cls_labels, const float *point_box_labels, const float *point_part_labels,
                               long long n, int num_class, const float *weights, const float *code_weights, const float *grad_out,
                               float *d_cls_preds, float *d_box_preds, float *d_part_preds, void *ws, size_t ws_bytes, void *stream);
+
+/* ------------------------------------------------------------------ multi-frame point head and union gt boxes (training)
+ * The multi-frame supervision of tools/cfgs/livox_models/pv_rcnn_multiframe.yaml (STACK_FRAME_SIZE S stacked sweeps): every gt
+ * carries its pose in each sweep, locations (batch, m, S, 3) f32 and rotations_y (batch, m, S) f32, next to gt_boxes (batch, m, 8)
+ * f32 [box7 | class].  PointHeadSimpleMultiFrame.assign_targets / get_cls_layer_loss
+ * (pcdet/models/dense_heads/point_head_simple_multiframe.py:23-90) and the USE_MULTIFRAME_ENLARGED_GT_BOXES block of
+ * AnchorHeadSingle.forward (pcdet/models/dense_heads/anchor_head_single.py:61-89), all on the caller's stream; no host read, no
+ * allocation, no atomics, bitwise reproducible (csrc/point_head_mf.hip).
+ *   targets (ONE launch) -> point_cls_labels (n, S) i64, frame index fastest: column s is exactly what lidar_point_targets writes
+ *       for gt_boxes with columns 0:3 := locations[:, :, s] and column 6 := rotations_y[:, :, s] (fg = inside the first containing
+ *       row: 1 if num_class == 1 else (long)class; -1 for fg XOR inside any row enlarged by extra_width HOST (3); else 0; zero
+ *       padding rows take part, enlarged too; a bs_idx outside [0, batch) gives 0 in every column); point_box_idx (n, S) i32, the
+ *       owner row per frame or -1, may be NULL.  Every element is written.
+ *   loss: point_cls_preds (n, S * num_class) f32, column s * num_class + c; L = point_cls_labels (n, S).  npos = #(L > 0) over all
+ *       frames, norm = max(npos, 1), w_n = sum_s ([L_ns >= 0] / norm) (each term divided first, added in fp32 in frame order),
+ *       target t[n, s * num_class + c] = [L_ns == c + 1],
+ *       cls = point_cls_weight * sum_{n, j} focal(x_nj, t_nj; alpha 0.25, gamma 2) * w_n over ALL S * num_class columns: as in the
+ *       reference, a frame column whose label is -1 is still a negative target, weighted by the other frames' share of w_n; a
+ *       point ignored in every frame weighs 0.
+ *   forward (two launches) -> out (2) DEVICE f32: cls, npos; the workspace (lidar_point_loss_mf_ws_bytes(n)) keeps the tile
+ *       partials and the count for backward.  n 0: no kernel, out is zeroed.
+ *   backward (ONE launch): the same inputs and workspace, grad_out (1) DEVICE f32 -> d_cls_preds (n, S * num_class).
+ *   lidar_multiframe_enlarged_boxes (ONE launch, one thread per gt row) -> gt_boxes_enlarged (batch, m, 8): the reference as it
+ *       runs.  Its line 78 writes rotations_y into the LAST column, for 8-column boxes the class, which boxes_to_corners_3d never
+ *       reads: every frame's corners use the gt's own heading, rotations_y has no effect and is no argument here.  Columns 0:3 and
+ *       5:8 are the gt's; column 3 (4) is the extent in x (y) of all 8 S corners in the gt's local frame (corners, minus the gt
+ *       centre, rotated by -gt[6], max - min).  gt_dim must be 8: with more columns the reference's [:, -2] is not the heading.
+ * Supported (lidar_point_head_mf_supported, pure host; everything else is refused with LIDAR_ERR_ARG before any launch):
+ * 0 <= n <= 2^20, 1 <= batch <= 64, 0 <= m <= 128, 1 <= S <= 8, 1 <= num_class <= 4 (at most 32 logit columns).
+ * NOT built: REG_TRACKING_INFO of ProposalTargetLayer and the RoI loss, and the multi-frame extras of lidar_augment. */
+#define LIDAR_POINT_HEAD_MF_MAX_FRAMES 8
+#define LIDAR_POINT_HEAD_MF_MAX_CLASS 4
+int lidar_point_head_mf_supported(long long n, int batch, int m, int stack_frames, int num_class);
+int lidar_point_targets_mf(const float *points, long long n, const float *gt_boxes, const float *locations, const float *rotations_y,
+                           int batch, int m, int stack_frames, const float *extra_width, int num_class,
+                           long long *point_cls_labels, int *point_box_idx, void *stream);
+size_t lidar_point_loss_mf_ws_bytes(long long n);
+int lidar_point_loss_mf_forward(const float *point_cls_preds, const long long *point_cls_labels, long long n, int stack_frames,
+                                int num_class, float point_cls_weight, float *out, void *ws, size_t ws_bytes, void *stream);
+int lidar_point_loss_mf_backward(const float *point_cls_preds, const long long *point_cls_labels, long long n, int stack_frames,
+                                 int num_class, float point_cls_weight, const float *grad_out, float *d_cls_preds, void *ws,
+                                 size_t ws_bytes, void *stream);
+int lidar_multiframe_enlarged_boxes(const float *gt_boxes, const float *locations, int batch, int m, int gt_dim, int stack_frames,
+                                    float *gt_boxes_enlarged, void *stream);
 
 /* ------------------------------------------------------------------ fused optimiser step (training)
  * What follows loss.backward() in the reference's loop (tools/train_utils/train_utils.py:36-42) for OPTIMIZER: adam_onecycle:

@@ -182,6 +182,12 @@ SIGNATURES = {
     "lidar_point_loss_ws_bytes": (sz, [C.c_longlong]),
     "lidar_point_loss_forward": (i32, [vp, vp, vp, vp, vp, vp, C.c_longlong, i32, vp, vp, vp, vp, sz, vp]),
     "lidar_point_loss_backward": (i32, [vp, vp, vp, vp, vp, vp, C.c_longlong, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "lidar_point_head_mf_supported": (i32, [C.c_longlong, i32, i32, i32, i32]),
+    "lidar_point_targets_mf": (i32, [vp, C.c_longlong, vp, vp, vp, i32, i32, i32, vp, i32, vp, vp, vp]),
+    "lidar_point_loss_mf_ws_bytes": (sz, [C.c_longlong]),
+    "lidar_point_loss_mf_forward": (i32, [vp, vp, C.c_longlong, i32, i32, f32, vp, vp, sz, vp]),
+    "lidar_point_loss_mf_backward": (i32, [vp, vp, C.c_longlong, i32, i32, f32, vp, vp, vp, sz, vp]),
+    "lidar_multiframe_enlarged_boxes": (i32, [vp, vp, i32, i32, i32, i32, vp, vp]),
     "lidar_optim_plan": (C.c_longlong, [vp, i32, vp, vp, C.c_longlong]),
     "lidar_optim_workspace_bytes": (sz, [C.c_longlong]),
     "lidar_optim_grad_norm": (i32, [vp, i32, vp, vp, C.c_longlong, f32, vp, vp, sz, vp]),

@@ -19,7 +19,8 @@
 // The (N, C) logits and all three gradient outputs go through LDS so that global accesses are contiguous over the tile; box and
 // part rows are read by the positive rows only (a few per cent of the points), directly.
 //
-// The element math is loss_dev.h's, the ordered sums common.h's block_sum.
+// The element math is loss_dev.h's, the ordered sums common.h's block_sum; the staged gt row, the frame walk's range and the tile
+// copies are point_head_dev.h's, shared with point_head_mf.hip.
 // cls: sigmoid_focal; the one-hot column of label c > 0 is c - 1; rows with label -1 weigh 0.
 // box: smooth_l1 over the 8 codes, positives only.
 // part: bce_logits, positives only (the deviation from binary_cross_entropy that roi_loss.hip documents for its cls term).
@@ -28,13 +29,9 @@
 // 0 <= n_mean <= 8, gt rows of exactly 8 columns [box7 | class].
 #include "common.h"
 #include "loss_dev.h"
-#include "pt_in_box_dev.h"
+#include "point_head_dev.h"
 #include <math.h>
 
-#define PH_THREADS 256
-#define PH_MAX_N (1 << 20)
-#define PH_MAX_B 64
-#define PH_MAX_M 128
 #define PH_MAX_C 8
 #define PH_MAX_MEAN 8
 
@@ -42,12 +39,6 @@ struct PHTargetParams {
     float extra[3];
     float mean[PH_MAX_MEAN * 3];
     int n, batch, m, num_class, n_mean, ret_box, ret_part;
-};
-
-struct PHGt {
-    BoxCS b;               // the gt box: centre, dims, cos / sin of -rz
-    float ex, ey, ez;      // enlarged dims (float32 sums, as enlarge_box3d forms them)
-    float rz, cls;
 };
 
 __global__ __launch_bounds__(PH_THREADS) void point_targets_kernel(PHTargetParams p, const float *__restrict__ points,
@@ -64,21 +55,12 @@ __global__ __launch_bounds__(PH_THREADS) void point_targets_kernel(PHTargetParam
     int frame = -1;                                   // -1: past the end, or a bs_idx that names no frame (the row keeps label 0)
     if (i < p.n) {
         const float *q = points + (size_t)i * 4;
-        const float bs = q[0];
         x = q[1]; y = q[2]; z = q[3];
-        if (bs >= 0.0f && bs < (float)p.batch && bs == (float)(int)bs) frame = (int)bs;
+        frame = ph_frame_of(q[0], p.batch);
     }
     // the range of frames this workgroup has to visit
-    int lo = frame >= 0 ? frame : p.batch, hi = frame;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        lo = min(lo, __shfl_xor(lo, d, 64));
-        hi = max(hi, __shfl_xor(hi, d, 64));
-    }
-    if (lane_id() == 0) { s_lo[t >> 6] = lo; s_hi[t >> 6] = hi; }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < PH_THREADS / 64; ++k) { lo = min(lo, s_lo[k]); hi = max(hi, s_hi[k]); }
+    int lo, hi;
+    ph_frame_range(frame, p.batch, s_lo, s_hi, lo, hi);
 
     int owner = -1;
     bool ext = false;
@@ -86,14 +68,7 @@ __global__ __launch_bounds__(PH_THREADS) void point_targets_kernel(PHTargetParam
     float g[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};      // the owner's gt row
     for (int f = lo; f <= hi; ++f) {                  // uniform over the workgroup
         if (!__syncthreads_or(frame == f)) continue;  // also: everyone is done with the previous frame's rows
-        for (int k = t; k < p.m; k += PH_THREADS) {
-            const float *row = gt + ((size_t)f * p.m + k) * 8;
-            PHGt r;
-            r.b = make_boxcs(row);
-            r.ex = row[3] + p.extra[0]; r.ey = row[4] + p.extra[1]; r.ez = row[5] + p.extra[2];
-            r.rz = row[6]; r.cls = row[7];
-            s_gt[k] = r;
-        }
+        for (int k = t; k < p.m; k += PH_THREADS) s_gt[k] = ph_stage_gt(gt + ((size_t)f * p.m + k) * 8, p.extra);
         __syncthreads();
         if (frame == f) {
             for (int k = 0; k < p.m; ++k) {
@@ -103,11 +78,7 @@ __global__ __launch_bounds__(PH_THREADS) void point_targets_kernel(PHTargetParam
                     owner = k; lx = ax; ly = ay;
                     g[0] = r.b.cx; g[1] = r.b.cy; g[2] = r.b.cz; g[3] = r.b.dx; g[4] = r.b.dy; g[5] = r.b.dz; g[6] = r.rz; g[7] = r.cls;
                 }
-                if (!ext) {
-                    BoxCS e = r.b;
-                    e.dx = r.ex; e.dy = r.ey; e.dz = r.ez;
-                    ext = pt_in_box(e, x, y, z, ax, ay);
-                }
+                if (!ext) ext = pt_in_box(ph_enlarged(r), x, y, z, ax, ay);
                 if (owner >= 0 && ext) break;
             }
         }
@@ -176,19 +147,6 @@ static inline size_t ph_ws_layout(int tiles, PHWs *w, char *base) {
     p = c.take(sizeof(int) * (size_t)tiles);       if (w) w->npos = (int *)p;
     p = c.take(sizeof(int));                       if (w) w->count = (int *)p;
     return c.off;
-}
-
-// the rows [row0, row0 + PH_THREADS) x width floats of a row-major matrix -> s (contiguous global reads)
-__device__ __forceinline__ void ph_tile_load(float *s, const float *__restrict__ src, long long row0, int n, int width) {
-    const long long base = row0 * width;
-    const int cnt = (int)min((long long)PH_THREADS * width, (long long)n * width - base);
-    for (int k = threadIdx.x; k < cnt; k += PH_THREADS) s[k] = src[base + k];
-}
-
-__device__ __forceinline__ void ph_tile_store(const float *s, float *__restrict__ dst, long long row0, int n, int width) {
-    const long long base = row0 * width;
-    const int cnt = (int)min((long long)PH_THREADS * width, (long long)n * width - base);
-    for (int k = threadIdx.x; k < cnt; k += PH_THREADS) dst[base + k] = s[k];
 }
 
 __global__ __launch_bounds__(PH_THREADS) void point_loss_tile_kernel(PHLossParams p, const float *__restrict__ cls_preds,
