@@ -9,6 +9,12 @@
  *
  * Each declaration cites the reference interface it replaces (paths under /root/reference/).
  * The Python-side binding a maintainer adds is shown in INTEGRATION.md.
+ *
+ * This text is also read by a program: lidardetection_amd/_lib.py derives its ctypes table and its LIDAR_* limits from it, and
+ * csrc/common.h includes it, so every definition is compiled against its declaration.  Keep to what that parser maps without
+ * guessing: parameters and returns of type void, int, float, double, size_t, long long (or a fixed-width / unsigned integer) by
+ * value, pointers to them of any depth and constness; no struct by value, array, function-pointer or variadic parameter; an
+ * object-like `#define LIDAR_<NAME>` is an integer expression of literals, parentheses, unary minus, <<, * and +.
  */
 #ifndef LIDAR_HIP_H
 #define LIDAR_HIP_H
@@ -151,6 +157,7 @@ int lidar_pillar_scatter(const float *pillar_features, const void *coords, int c
  * stats (272 doubles: the moment sums, mean, inverse std, N), scale_shift (2 * cout) and batch_stats (3 * cout: batch mean, biased
  * variance, unbiased variance -- the caller applies the running-statistics update).  Backward: grad_out (V, cout) -> d_weight
  * (cout, nf), d_gamma, d_beta (cout).  No float atomics: both are bitwise reproducible.  ws: lidar_pfn_train_workspace_bytes. */
+#define LIDAR_PFN_TRAIN_STATS_DOUBLES 272
 size_t lidar_pfn_train_workspace_bytes(int num_voxels, int num_features, int cout, int with_distance);
 int lidar_pfn_train_forward(const float *voxels, const void *num_points, const void *coords, int num_voxels, const int *num_voxels_dev,
                             int max_points, int num_features, const float *weight, const float *gamma, const float *beta, int cout,
@@ -638,6 +645,8 @@ int lidar_decode_topk(const float *head, int batch, long long locs_per_frame, in
  *   lidar_decode_topk_rows     lidar_decode_topk reading such compact logits (batch, k, 7 + num_dir_bins) instead of the head map:
  *                              the same device function, bit-equal boxes for bit-equal logits. */
 #define LIDAR_HEAD_ROWS_MAX_C 1024
+#define LIDAR_HEAD_ROWS_MAX_ANCHORS 8
+#define LIDAR_HEAD_ROWS_MAX_DIR_BINS 4
 int lidar_head_rows_supported(int C, int anchors_per_loc, int num_dir_bins, long long part_bytes);
 int lidar_head_rows(const float *part0, const float *part1, int n_parts, int frames_per_part, long long locs_per_frame, int C,
                     const float *head_wt, int ldw, const float *head_b, int box_off, int dir_off, int anchors_per_loc, int num_dir_bins,
@@ -1079,6 +1088,9 @@ int lidar_rotate_iou_eval(const float *boxes, int n, const float *query_boxes, i
 #define LIDAR_KITTI_EVAL_CLS_OTHER 7
 #define LIDAR_KITTI_EVAL_MAX_GT 1024
 #define LIDAR_KITTI_EVAL_MAX_DT 1024
+#define LIDAR_KITTI_EVAL_MAX_FRAMES (1 << 20)
+#define LIDAR_KITTI_EVAL_MAX_TOTAL_GT (1ll << 20)
+#define LIDAR_KITTI_EVAL_MAX_TOTAL_DT (1ll << 22)
 #define LIDAR_KITTI_EVAL_MAX_CLASS 8
 #define LIDAR_KITTI_EVAL_MAX_DIFF 3
 #define LIDAR_KITTI_EVAL_MAX_OVERLAP 16

@@ -3,213 +3,115 @@
 Deliberately no fallback: if the shared library is missing or a symbol is absent we raise, so a
 silent eager/PyTorch path can never stand in for the HIP path.
 """
+import ast
 import ctypes as C
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("LIDAR_HIP_SO") or os.path.join(_HERE, "csrc", "liblidar_hip.so")   # env override: A/B builds (tools/)
-
-vp, i32, f32, sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
-
-# name -> (restype, argtypes); must cover every function declared in include/lidar_hip.h
-SIGNATURES = {
-    "lidar_voxelize_workspace_bytes": (sz, [i32, i32, i32]),
-    "lidar_voxelize_workspace_init": (i32, [vp, sz, i32, i32, i32, vp]),
-    "lidar_voxelize": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp]),
-    "lidar_voxelize_hostoff": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp]),
-    "lidar_voxelize_error_flag": (i32, [vp, sz, i32, i32, i32]),
-    "lidar_timer_create": (vp, []),
-    "lidar_timer_destroy": (None, [vp]),
-    "lidar_voxelize_time_next": (None, [vp]),
-    "lidar_timer_elapsed_ms": (C.c_float, [vp]),
-    "lidar_timer_parts_ms": (i32, [vp, vp]),
-    "lidar_voxelize_set_error_mirror": (i32, [vp, sz, i32, i32, i32, vp, vp]),
-    "lidar_pillar_vfe": (i32, [vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, i32, vp, vp, i32, i32, i32, vp, vp]),
-    "lidar_mean_vfe": (i32, [vp, vp, i32, i32, i32, i32, vp, vp]),
-    "lidar_pillar_scatter_workspace_bytes": (sz, [i32, i32, i32]),
-    "lidar_pillar_scatter": (i32, [vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, vp, vp, sz, vp]),
-    "lidar_pillar_scatter_update": (i32, [vp, vp, i32, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
-    "lidar_pillar_conv_table_workspace_bytes": (sz, [i32, i32, i32]),
-    "lidar_pillar_conv_table": (i32, [vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp]),
-    "lidar_pfn_train_workspace_bytes": (sz, [i32, i32, i32, i32]),
-    "lidar_pfn_train_forward": (i32, [vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, i32, f32, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp,
-                                      vp, vp, sz, vp]),
-    "lidar_pfn_train_backward": (i32, [vp, vp, vp, i32, vp, i32, i32, vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp,
-                                       vp, vp, sz, vp]),
-    "lidar_pillar_scatter_backward": (i32, [vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, vp, vp]),
-    "lidar_bn_relu_train_workspace_bytes": (sz, [C.c_longlong, i32]),
-    "lidar_bn_relu_train_forward": (i32, [i32, vp, vp, vp, vp, C.c_longlong, vp, vp, f32, vp, i32, i32, vp, vp, vp, vp, sz, vp]),
-    "lidar_bn_relu_train_backward": (i32, [i32, vp, vp, vp, vp, C.c_longlong, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
-    "lidar_bn_add_relu_train_forward": (i32, [vp, i32, vp, i32, i32, C.c_longlong, vp, vp, f32, vp, i32, vp, vp, vp, vp, sz, vp]),
-    "lidar_bn_add_relu_train_backward": (i32, [vp, i32, vp, i32, i32, C.c_longlong, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, sz, vp]),
-    "lidar_iou_workspace_bytes": (sz, [i32, i32]),
-    "lidar_boxes_pairwise_bev": (i32, [vp, i32, vp, i32, i32, vp, vp, sz, vp]),
-    "lidar_nms_workspace_bytes": (sz, [i32, i32]),
-    "lidar_nms_batch": (i32, [vp, vp, i32, i32, f32, i32, vp, vp, vp, sz, vp]),
-    "lidar_nms_batch_limited": (i32, [vp, vp, i32, i32, f32, i32, i32, vp, vp, vp, sz, vp]),
-    "lidar_nms_mask_ptr": (vp, [vp, i32, i32]),
-    "lidar_ball_query_stack": (i32, [i32, i32, f32, i32, vp, vp, vp, vp, vp, vp]),
-    "lidar_ball_query_stack2": (i32, [i32, i32, f32, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp]),
-    "lidar_ball_query_grid_workspace_bytes": (sz, [i32, i32]),
-    "lidar_ball_query_stack_grid": (i32, [i32, i32, i32, f32, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
-    "lidar_group_points_stack": (i32, [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
-    "lidar_group_rows_stack": (i32, [i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
-    "lidar_group_rows_affine_stack": (i32, [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
-    "lidar_sa_layer2_max_supported": (i32, [i32, i32, i32]),
-    "lidar_sa_layer2_max_stack": (i32, [i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-    "lidar_group_points_grad_stack": (i32, [i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
-    "lidar_sa_train_supported": (i32, [i32, i32]),
-    "lidar_sa_gather_train_forward": (i32, [i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
-    "lidar_sa_pair_keys": (i32, [i32, i32, i32, i32, vp, vp, vp, vp, vp]),
-    "lidar_sa_row_start": (i32, [C.c_longlong, i32, vp, vp, vp]),
-    "lidar_sa_gather_train_backward": (i32, [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
-    "lidar_bn_relu_max_train_workspace_bytes": (sz, [i32, i32, i32]),
-    "lidar_bn_relu_max_train_forward": (i32, [vp, i32, i32, i32, vp, vp, f32, vp, vp, vp, vp, vp, vp, sz, vp]),
-    "lidar_bn_relu_max_train_backward": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
-    "lidar_furthest_point_sampling": (i32, [i32, i32, i32, vp, vp, vp, vp]),
-    "lidar_three_nn_stack": (i32, [i32, i32, vp, vp, vp, vp, vp, vp, vp]),
-    "lidar_three_interpolate_stack": (i32, [i32, i32, vp, vp, vp, vp, vp]),
-    "lidar_three_interpolate_grad_stack": (i32, [i32, i32, vp, vp, vp, vp, vp]),
-    "lidar_ball_query_batch": (i32, [i32, i32, i32, f32, i32, vp, vp, vp, vp]),
-    "lidar_group_points_batch": (i32, [i32, i32, i32, i32, i32, vp, vp, vp, vp]),
-    "lidar_group_points_grad_batch": (i32, [i32, i32, i32, i32, i32, vp, vp, vp, vp]),
-    "lidar_gather_points_batch": (i32, [i32, i32, i32, i32, vp, vp, vp, vp]),
-    "lidar_gather_points_grad_batch": (i32, [i32, i32, i32, i32, vp, vp, vp, vp]),
-    "lidar_three_nn_batch": (i32, [i32, i32, i32, vp, vp, vp, vp, vp]),
-    "lidar_three_interpolate_batch": (i32, [i32, i32, i32, i32, vp, vp, vp, vp, vp]),
-    "lidar_three_interpolate_grad_batch": (i32, [i32, i32, i32, i32, vp, vp, vp, vp, vp]),
-    "lidar_roiaware_pool3d_forward": (i32, [i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp]),
-    "lidar_roiaware_pool3d_backward": (i32, [i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp]),
-    "lidar_points_in_boxes": (i32, [i32, i32, i32, vp, vp, vp, vp]),
-    "lidar_roipoint_pool3d_forward": (i32, [i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
-    "lidar_spconv_hash_capacity": (sz, [i32]),
-    "lidar_spconv_build_hash": (i32, [vp, i32, i32, i32, i32, vp, sz, vp]),
-    "lidar_spconv_subm_table": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp, vp]),
-    "lidar_spconv_conv_table_workspace_bytes": (sz, [i32, i32, i32, i32, i32, i32, i32]),
-    "lidar_spconv_conv_outputs": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp, sz, vp]),
-    "lidar_spconv_conv_tables": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
-    "lidar_spconv_grid_init": (i32, [vp, sz, vp]),
-    "lidar_spconv_grid_rows": (i32, [vp, i32, vp, i32, i32, i32, i32, vp, i32, vp]),
-    "lidar_spconv_grid_table": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp]),
-    "lidar_spconv_grid_table_t": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp]),
-    "lidar_spconv_grid_pad_rows": (i32, [vp, vp, i32, vp]),
-    "lidar_spconv_transpose_table": (i32, [vp, i32, i32, i32, vp, vp]),
-    "lidar_spconv_grid_outputs_workspace_bytes": (sz, [i32, i32]),
-    "lidar_spconv_grid_outputs": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
-    "lidar_spconv_implicit_gemm": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
-    "lidar_spconv_implicit_gemm_fused": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp]),
-    "lidar_spconv_row_masks": (i32, [vp, i32, i32, vp, vp]),
-    "lidar_spconv_mask_group_workspace_bytes": (sz, [i32]),
-    "lidar_spconv_mask_group_init": (i32, [vp, sz, vp]),
-    "lidar_spconv_mask_group": (i32, [vp, i32, i32, vp, vp, vp, sz, vp]),
-    "lidar_spconv_sorted_gemm_supported": (i32, [i32, i32, i32]),
-    "lidar_spconv_implicit_gemm_sorted": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp]),
-    "lidar_spconv_packed_floats": (sz, [i32, i32, i32]),
-    "lidar_spconv_pack_weights": (i32, [vp, i32, i32, i32, vp, vp]),
-    "lidar_spconv_implicit_gemm_sorted_packed": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp]),
-    "lidar_spconv_wgrad": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp]),
-    "lidar_spconv_wgrad_mfma_supported": (i32, [i32, i32, i32]),
-    "lidar_spconv_wgrad_workspace_bytes": (sz, [i32, i32, i32, i32]),
-    "lidar_spconv_wgrad_mfma": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, sz, vp]),
-    "lidar_sparse_to_dense_workspace_bytes": (sz, [i32, i32, i32, i32]),
-    "lidar_sparse_to_dense": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp]),
-    "lidar_sparse_to_bev_nhwc": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp]),
-    "lidar_sparse_to_bev_nhwc_backward": (i32, [vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
-    "lidar_bias_act_nhwc": (i32, [vp, vp, C.c_longlong, i32, i32, vp, i32, i32, vp]),
-    "lidar_bias_act_upsample_nhwc": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, vp]),
-    "lidar_dense_gemm_bias_act": (i32, [vp, C.c_longlong, i32, vp, i32, vp, i32, vp, i32, vp, sz, vp]),
-    "lidar_dense_gemm_export_choices": (i32, [vp, i32]),
-    "lidar_dense_gemm_import_choices": (i32, [vp, i32]),
-    "lidar_wino_packed_floats": (sz, [i32, i32]),
-    "lidar_wino_supported": (i32, [i32, i32]),
-    "lidar_wino_pack_weights": (i32, [vp, i32, i32, vp, vp]),
-    "lidar_wino_conv3x3_nhwc": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, i32, vp, i32, i32, vp]),
-    "lidar_wino43_packed_floats": (sz, [i32, i32]),
-    "lidar_wino43_supported": (i32, [i32, i32]),
-    "lidar_wino43_pack_weights": (i32, [vp, i32, i32, vp, vp]),
-    "lidar_wino43_conv3x3_nhwc": (i32, [vp, i32, i32, i32, i32, i32, vp, vp, i32, i32, vp, i32, i32, vp]),
-    "lidar_wino43s_packed_floats": (sz, [i32, i32]),
-    "lidar_wino43s_supported": (i32, [i32, i32]),
-    "lidar_wino43s_pack_weights": (i32, [vp, i32, i32, vp, vp]),
-    "lidar_wino43s_conv3x3_nhwc": (i32, [vp, i32, i32, i32, i32, i32, vp, vp, i32, i32, vp, i32, i32, vp]),
-    "lidar_wino43_wgrad_supported": (i32, [i32, i32]),
-    "lidar_wino43_wgrad_workspace_bytes": (sz, [i32, i32, i32, i32, i32]),
-    "lidar_wino43_wgrad_nhwc": (i32, [vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp]),
-    "lidar_wino_conv3x3_grouped_nhwc": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, i32, vp]),
-    "lidar_wino_conv3x3_grouped_compact_nhwc": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, i32, i32, vp]),
-    "lidar_deconv_packed_floats": (sz, [i32, i32]),
-    "lidar_deconv_supported": (i32, [i32, i32, i32]),
-    "lidar_deconv_pack_weights": (i32, [vp, i32, i32, vp, vp]),
-    "lidar_deconv_gemm_nhwc": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, vp, i32, i32, vp]),
-    "lidar_deconv_train_supported": (i32, [i32, i32, i32]),
-    "lidar_deconv_wgrad_workspace_bytes": (sz, [i32, i32, i32, i32, i32, i32]),
-    "lidar_deconv_dgrad_nhwc": (i32, [vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp]),
-    "lidar_deconv_wgrad_nhwc": (i32, [vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp]),
-    "lidar_anchor_scores": (i32, [vp, C.c_longlong, i32, i32, i32, i32, f32, vp, vp, vp]),
-    "lidar_decode_topk": (i32, [vp, i32, C.c_longlong, i32, i32, i32, i32, i32, vp, i32, vp, f32, f32, f32, vp, vp]),
-    "lidar_topk_workspace_bytes": (sz, [i32, C.c_longlong]),
-    "lidar_topk_workspace_init": (i32, [vp, sz, i32, C.c_longlong, vp]),
-    "lidar_head_rows_supported": (i32, [i32, i32, i32, C.c_longlong]),
-    "lidar_head_rows": (i32, [vp, vp, i32, i32, C.c_longlong, i32, vp, i32, vp, i32, i32, i32, i32, vp, i32, C.c_longlong, vp, vp]),
-    "lidar_decode_topk_rows": (i32, [vp, i32, i32, i32, vp, vp, f32, f32, f32, vp, vp]),
-    "lidar_anchor_scores_hist": (i32, [vp, i32, C.c_longlong, i32, i32, i32, i32, f32, vp, vp, vp, sz, vp]),
-    "lidar_topk_desc": (i32, [vp, i32, C.c_longlong, i32, f32, f32, i32, vp, vp, vp, vp, sz, vp]),
-    "lidar_post_nms_gather": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, C.c_longlong, i32, i32, vp, vp, vp, vp, vp]),
-    "lidar_anchor_assign_workspace_bytes": (sz, [i32, i32, i32]),
-    "lidar_anchor_assign": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, C.c_longlong, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp,
-                                  vp, vp, vp, sz, vp]),
-    "lidar_atss_assign_supported": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32]),
-    "lidar_atss_assign_workspace_bytes": (sz, [i32, i32, i32, i32]),
-    "lidar_atss_assign": (i32, [vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
-    "lidar_proposal_target_supported": (i32, [i32, i32, i32, i32]),
-    "lidar_proposal_target": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, f32, f32, f32, f32, f32, vp, vp,
-                                    vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-    "lidar_augment_supported": (i32, [i32, i32, i32, i32]),
-    "lidar_augment_workspace_bytes": (sz, [i32, i32, i32, i32]),
-    "lidar_augment": (i32, [vp, vp, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp,
-                            vp, vp, vp, i32, i32, C.c_longlong, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
-    "lidar_anchor_loss_workspace_bytes": (sz, [i32, vp, i32]),
-    "lidar_anchor_loss_forward": (i32, [vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, C.c_longlong, i32, i32, i32, vp, vp, i32,
-                                        vp, vp, sz, vp]),
-    "lidar_anchor_loss_backward": (i32, [vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, C.c_longlong, i32, i32, i32, vp, vp, i32,
-                                         vp, vp, vp, vp, vp, sz, vp]),
-    "lidar_roi_loss_supported": (i32, [i32, i32, i32, i32, i32, i32]),
-    "lidar_roi_loss_workspace_bytes": (sz, [i32, i32]),
-    "lidar_roi_loss_forward": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, vp, vp, sz, vp]),
-    "lidar_roi_loss_backward": (i32, [i32, i32, vp, vp, i32, vp, vp, vp, vp, sz, vp]),
-    "lidar_point_head_supported": (i32, [C.c_longlong, i32, i32, i32, i32, i32]),
-    "lidar_point_targets": (i32, [vp, C.c_longlong, vp, i32, i32, i32, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp]),
-    "lidar_point_loss_ws_bytes": (sz, [C.c_longlong]),
-    "lidar_point_loss_forward": (i32, [vp, vp, vp, vp, vp, vp, C.c_longlong, i32, vp, vp, vp, vp, sz, vp]),
-    "lidar_point_loss_backward": (i32, [vp, vp, vp, vp, vp, vp, C.c_longlong, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
-    "lidar_point_head_mf_supported": (i32, [C.c_longlong, i32, i32, i32, i32]),
-    "lidar_point_targets_mf": (i32, [vp, C.c_longlong, vp, vp, vp, i32, i32, i32, vp, i32, vp, vp, vp]),
-    "lidar_point_loss_mf_ws_bytes": (sz, [C.c_longlong]),
-    "lidar_point_loss_mf_forward": (i32, [vp, vp, C.c_longlong, i32, i32, f32, vp, vp, sz, vp]),
-    "lidar_point_loss_mf_backward": (i32, [vp, vp, C.c_longlong, i32, i32, f32, vp, vp, vp, sz, vp]),
-    "lidar_multiframe_enlarged_boxes": (i32, [vp, vp, i32, i32, i32, i32, vp, vp]),
-    "lidar_optim_plan": (C.c_longlong, [vp, i32, vp, vp, C.c_longlong]),
-    "lidar_optim_workspace_bytes": (sz, [C.c_longlong]),
-    "lidar_optim_grad_norm": (i32, [vp, i32, vp, vp, C.c_longlong, f32, vp, vp, sz, vp]),
-    "lidar_optim_adam_step": (i32, [vp, i32, vp, vp, C.c_longlong, vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
-                                    C.c_longlong, i32, vp]),
-    "lidar_rotate_iou_eval": (i32, [vp, i32, vp, i32, i32, vp, vp]),
-    "lidar_kitti_eval_supported": (i32, [i32, C.c_longlong, C.c_longlong, i32, i32, i32, i32, i32]),
-    "lidar_kitti_eval_workspace_bytes": (sz, [i32, C.c_longlong, C.c_longlong, i32, i32, i32, i32, i32]),
-    "lidar_kitti_eval_overlaps": (i32, [i32, i32, vp, vp, vp, vp, vp, i32, C.c_longlong, C.c_longlong, C.c_longlong, i32, i32, vp, vp]),
-    "lidar_kitti_eval_class": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, C.c_longlong, C.c_longlong, C.c_longlong, i32, i32,
-                                     vp, i32, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
-    "lidar_boxes_iou_bev_cpu":(i32, [vp, i32, vp, i32, vp]),
-    "lidar_points_in_boxes_cpu": (i32, [vp, i32, vp, i32, vp]),
-    "lidar_voxelize_cpu_scratch_bytes": (sz, [i32]),
-    "lidar_voxelize_cpu": (i32, [vp, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp, sz]),
-}
-
-_lib = None
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "lidar_hip.h")
 
 
 class LidarHipError(RuntimeError):
     pass
+
+
+# by-value C types of the ABI; a pointer to any of them, of any depth and constness, is a c_void_p
+_CTYPES = {"void": None, "int": C.c_int, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t, "long long": C.c_longlong,
+           "char": C.c_char, "signed char": C.c_byte, "unsigned char": C.c_ubyte, "unsigned": C.c_uint, "unsigned int": C.c_uint,
+           "unsigned long long": C.c_ulonglong, "uint32_t": C.c_uint32, "int64_t": C.c_int64}
+_QUALIFIERS = {"const", "volatile", "restrict", "__restrict__"}
+_INT_OPS = {ast.LShift: int.__lshift__, ast.Mult: int.__mul__, ast.Add: int.__add__}
+
+
+def _ctype(text, decl, named):
+    """ctypes of one parameter (`named`: an identifier may follow the type) or of a return type, as written in C"""
+    if "[" in text:
+        raise LidarHipError(f"{decl}: array parameter `{text.strip()}`")
+    tok = [t for t in re.findall(r"\w+|\S", text) if t not in _QUALIFIERS]
+    pointer = "*" in tok
+    base = tok[:tok.index("*")] if pointer else tok
+    rest = [t for t in tok[len(base):] if t != "*"]                     # behind the stars: nothing, or the parameter's name
+    if not pointer and named and len(base) > 1 and " ".join(base) not in _CTYPES:
+        base, rest = base[:-1], base[-1:]
+    if len(rest) > named or not all(re.fullmatch(r"[A-Za-z_]\w*", t) for t in rest):
+        raise LidarHipError(f"{decl}: cannot read `{text.strip()}`")
+    name = " ".join(base)
+    if name not in _CTYPES or (named and not pointer and name == "void"):
+        what = "by-value struct" if not pointer and base[:1] in (["struct"], ["union"]) else "unknown base type"
+        raise LidarHipError(f"{decl}: {what} `{name}` in `{text.strip()}`")
+    return C.c_void_p if pointer else _CTYPES[name]
+
+
+def _int_expr(text, name):
+    """value of a constant expression of integer literals (decimal / hex, u / l / ll suffixes), parentheses, unary minus, `<<`, `*`
+    and `+`.  Python's grammar gives these the precedence C does; only these node kinds are evaluated, nothing is eval()ed"""
+    def value(n):
+        if isinstance(n, ast.Constant) and type(n.value) is int:
+            return n.value
+        if isinstance(n, ast.UnaryOp) and isinstance(n.op, ast.USub):
+            return -value(n.operand)
+        if isinstance(n, ast.BinOp) and type(n.op) in _INT_OPS:
+            return _INT_OPS[type(n.op)](value(n.left), value(n.right))
+        raise ValueError(n)
+    try:
+        return value(ast.parse(re.sub(r"\b(0[xX][0-9a-fA-F]+|\d+)[uUlL]+\b", r"\1", text), mode="eval").body)
+    except (SyntaxError, ValueError):
+        raise LidarHipError(f"#define {name}: `{text}` is not an integer expression this parser reads") from None
+
+
+def parse_header(text):
+    """include/lidar_hip.h -> (signatures, limits): signatures[name] = (restype, argtypes) of every function the header declares,
+    limits[name] = value of every object-like `#define LIDAR_<NAME> <integer expression>`.  Strict: what it cannot map exactly
+    (an unknown type, a struct by value, an array or function-pointer parameter, a variadic list, two differing declarations of
+    one name) raises LidarHipError naming the declaration."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S).replace("\\\n", " ")
+    signatures, limits, code = {}, {}, []
+    for line in text.split("\n"):
+        if not line.lstrip().startswith("#"):
+            code.append(line)
+            continue
+        m = re.match(r"\s*#\s*define\s+(LIDAR_\w+)(?!\()\s+(\S.*)", line)     # not function-like, not the bare include guard
+        value = m and _int_expr(m.group(2).strip(), m.group(1))
+        if m and limits.setdefault(m.group(1), value) != value:
+            raise LidarHipError(f"#define {m.group(1)}: defined twice with different values")
+    for decl in re.sub(r'extern\s+"C"\s*\{|^\s*\}', " ", "\n".join(code), flags=re.M).split(";"):
+        decl = " ".join(decl.split())
+        if not decl:
+            continue
+        m = re.fullmatch(r"(.*?)\b([A-Za-z_]\w*)\s*\((.*)\)", decl)
+        if not m or not m.group(1).strip():
+            raise LidarHipError(f"cannot read the declaration `{decl}`")
+        ret, name, args = m.group(1), m.group(2), m.group(3).strip()
+        for mark, what in (("...", "variadic parameter list"), ("(", "function-pointer parameter")):
+            if mark in args:
+                raise LidarHipError(f"{name}: {what}")
+        if not args:
+            raise LidarHipError(f"{name}: empty parameter list; write (void)")
+        sig = (_ctype(ret, name, False), [] if args == "void" else [_ctype(a, name, True) for a in args.split(",")])
+        if signatures.setdefault(name, sig) != sig:
+            raise LidarHipError(f"{name}: declared twice with different types")
+    return signatures, limits
+
+
+if not os.path.exists(HEADER_PATH):
+    raise LidarHipError(f"{HEADER_PATH} is missing: the ctypes signatures and the LIDAR_* limits are read from it; there is no second copy")
+with open(HEADER_PATH) as _f:
+    # name -> (restype, argtypes) of every function the header declares, and name -> value of its LIDAR_* constants
+    SIGNATURES, LIMITS = parse_header(_f.read())
+
+_lib = None
+
+
+def _bind(path):
+    """load the library at `path` and give every declared function its types"""
+    so = C.CDLL(path)
+    for name, (res, args) in SIGNATURES.items():
+        fn = getattr(so, name)  # AttributeError if the symbol is not exported
+        fn.restype = res
+        fn.argtypes = args
+    return so
 
 
 def lib():
@@ -219,11 +121,7 @@ def lib():
             raise LidarHipError(
                 f"{SO_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
-        _lib = C.CDLL(SO_PATH)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(_lib, name)  # AttributeError if the symbol is not exported
-            fn.restype = res
-            fn.argtypes = args
+        _lib = _bind(SO_PATH)
     return _lib
 
 
@@ -232,12 +130,7 @@ def load_variant(path):
     csrc/build.py:VARIANTS).  The product path never calls this."""
     if not os.path.exists(path):
         raise LidarHipError(f"{path} is missing: build it with lidardetection_amd/csrc/build.py (build_variants)")
-    v = C.CDLL(path)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(v, name)
-        fn.restype = res
-        fn.argtypes = args
-    return v
+    return _bind(path)
 
 
 def check(status, what):

@@ -14,8 +14,10 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import LIMITS
 
-MAX_FEATURES, MAX_GROUPS, MAX_PER_GROUP, MAX_BOXES = 8, 8, 64, 512      # include/lidar_hip.h: LIDAR_AUGMENT_*
+MAX_FEATURES, MAX_GROUPS = LIMITS["LIDAR_AUGMENT_MAX_FEATURES"], LIMITS["LIDAR_AUGMENT_MAX_GROUPS"]
+MAX_PER_GROUP, MAX_BOXES = LIMITS["LIDAR_AUGMENT_MAX_PER_GROUP"], LIMITS["LIDAR_AUGMENT_MAX_BOXES"]
 
 
 def fakelidar_to_lidar(boxes):

@@ -84,7 +84,7 @@ def _lt_gemm(a_ptr, M, K, w_kn, bias, relu, d_ptr, ldd, device):
     ws = workspace.get("dense_gemm", 32 << 20, device)
     st = _lib.lib().lidar_dense_gemm_bias_act(a_ptr, M, K, _lib.ptr(w_kn), w_kn.shape[1], _lib.ptr(bias), int(bool(relu)), d_ptr, ldd,
                                               _lib.ptr(ws), ws.numel(), _lib.stream())
-    if st == -4:                                   # LIDAR_ERR_UNSUPPORTED
+    if st == _lib.LIMITS["LIDAR_ERR_UNSUPPORTED"]:
         return False
     _lib.check(st, "lidar_dense_gemm_bias_act")
     return True

@@ -27,7 +27,6 @@
 // as numpy / torch cast them before combining them with a float32 array.
 #include "iou3d_dev.h"
 #include "pt_in_box_dev.h"
-#include "../../include/lidar_hip.h"
 
 #define AUG_TPB 128          // aug_frame_kernel
 #define AUG_ROWS 256         // rows per block of the streaming kernels == their threads per block

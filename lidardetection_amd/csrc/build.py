@@ -10,6 +10,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SO = os.path.join(HERE, "liblidar_hip.so")
+ABI_HEADER = os.path.join(os.path.dirname(os.path.dirname(HERE)), "include", "lidar_hip.h")      # common.h includes it
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "-fvisibility=hidden",
          "-Wall", "-Wno-unused-function"]
@@ -23,9 +24,13 @@ def sources():
     return sorted(glob.glob(os.path.join(HERE, "*.hip")))
 
 
+def headers():
+    return glob.glob(os.path.join(HERE, "*.h")) + [ABI_HEADER]
+
+
 def build(force=False, verbose=False):
     srcs = sources()
-    deps = srcs + glob.glob(os.path.join(HERE, "*.h")) + [os.path.abspath(__file__)]
+    deps = srcs + headers() + [os.path.abspath(__file__)]
     if not force and os.path.exists(SO) and all(os.path.getmtime(SO) >= os.path.getmtime(d) for d in deps):
         return SO
     objs = []
@@ -80,7 +85,7 @@ def build_variants(force=False, verbose=False, names=None):
     for name, (src, extra) in todo.items():
         so = variant_path(name)
         s = os.path.join(HERE, src)
-        deps = [s] + glob.glob(os.path.join(HERE, "*.h")) + [os.path.abspath(__file__), SO]
+        deps = [s] + headers() + [os.path.abspath(__file__), SO]
         if not force and os.path.exists(so) and all(os.path.getmtime(so) >= os.path.getmtime(d) for d in deps):
             outs.append(so)
             continue

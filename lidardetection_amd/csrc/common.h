@@ -3,12 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
-
-#define LIDAR_OK 0
-#define LIDAR_ERR_ARG (-1)
-#define LIDAR_ERR_LAUNCH (-2)
-#define LIDAR_ERR_WORKSPACE (-3)
-#define LIDAR_ERR_UNSUPPORTED (-4)   // an optional library path is not available here: the caller keeps its other path
+#include "../../include/lidar_hip.h"   // the ABI: every LIDAR_EXPORT definition is compiled against its declaration; LIDAR_* codes, limits
 
 #define LIDAR_EXPORT extern "C" __attribute__((visibility("default")))
 

@@ -25,7 +25,6 @@
 // order in fp64, rounds once to fp32 and writes torch's layout (the pattern of csrc/wino43_wgrad.hip).  No float atomics, no host read:
 // bitwise reproducible and graph-capturable.  dw is overwritten, never read.
 #include "common.h"
-#include "../../include/lidar_hip.h"       // LIDAR_DECONV_TRAIN_*: the declared range
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 

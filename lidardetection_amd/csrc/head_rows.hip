@@ -22,9 +22,9 @@
 
 #define HR_THREADS 1024
 #define HR_WAVES (HR_THREADS / 64)
-#define HR_MAX_C 1024
-#define HR_MAX_A 8
-#define HR_MAX_BINS 4
+#define HR_MAX_C LIDAR_HEAD_ROWS_MAX_C
+#define HR_MAX_A LIDAR_HEAD_ROWS_MAX_ANCHORS
+#define HR_MAX_BINS LIDAR_HEAD_ROWS_MAX_DIR_BINS
 #define HR_LDS_MAX (128 * 1024)          // weight slices up to here are staged in LDS
 
 struct HrArgs {

@@ -17,17 +17,19 @@
 
 #include <math.h>
 
-#define KE_MAX_ROWS 1024          // gt rows and dt rows of one frame (LIDAR_KITTI_EVAL_MAX_GT / _MAX_DT)
-#define KE_MAX_CLASS 8
-#define KE_MAX_DIFF 3
-#define KE_MAX_OVERLAP 16
-#define KE_MAX_FRAMES (1 << 20)
-#define KE_MAX_TOTAL_GT (1ll << 20)
-#define KE_MAX_TOTAL_DT (1ll << 22)
-#define KE_PTS 41                 // N_SAMPLE_PTS
-#define KE_GT_COLS 14             // bbox 0..3, location 4..6, dimensions 7..9, rotation_y 10, alpha 11, occluded 12, truncated 13
-#define KE_DT_COLS 13             // the same first twelve, score 12
-#define KE_CLS_DONTCARE 6
+// short names of the header's constants (include/lidar_hip.h states the values and the row layouts)
+#define KE_MAX_GT LIDAR_KITTI_EVAL_MAX_GT             // gt rows of one frame
+#define KE_MAX_DT LIDAR_KITTI_EVAL_MAX_DT             // dt rows of one frame
+#define KE_MAX_CLASS LIDAR_KITTI_EVAL_MAX_CLASS
+#define KE_MAX_DIFF LIDAR_KITTI_EVAL_MAX_DIFF
+#define KE_MAX_OVERLAP LIDAR_KITTI_EVAL_MAX_OVERLAP
+#define KE_MAX_FRAMES LIDAR_KITTI_EVAL_MAX_FRAMES
+#define KE_MAX_TOTAL_GT LIDAR_KITTI_EVAL_MAX_TOTAL_GT
+#define KE_MAX_TOTAL_DT LIDAR_KITTI_EVAL_MAX_TOTAL_DT
+#define KE_PTS LIDAR_KITTI_EVAL_PTS                   // N_SAMPLE_PTS
+#define KE_GT_COLS LIDAR_KITTI_EVAL_GT_COLS
+#define KE_DT_COLS LIDAR_KITTI_EVAL_DT_COLS
+#define KE_CLS_DONTCARE LIDAR_KITTI_EVAL_CLS_DONTCARE
 
 namespace {
 
@@ -240,7 +242,7 @@ struct KeData {
 };
 
 __global__ __launch_bounds__(64) void ke_pass1_kernel(KeCfg cfg, KeFrames F, KeData d, double *__restrict__ matched) {
-    __shared__ unsigned s_mask[(KE_MAX_ROWS / 32) * 64];
+    __shared__ unsigned s_mask[(KE_MAX_DT / 32) * 64];
     const KeFrame fr = ke_frame(F, (int)blockIdx.x);
     const int c = (int)blockIdx.y * 64 + lane_id();
     if (c >= cfg.C * cfg.D * cfg.K || fr.ng == 0) return;
@@ -254,7 +256,7 @@ __global__ __launch_bounds__(64) void ke_pass1_kernel(KeCfg cfg, KeFrames F, KeD
 __global__ __launch_bounds__(64) void ke_pass2_kernel(KeCfg cfg, KeFrames F, KeData d, const double *__restrict__ thresholds,
                                                       const int *__restrict__ num_thresholds, int aos, int *__restrict__ part_cnt,
                                                       double *__restrict__ part_sim) {
-    __shared__ unsigned s_mask[(KE_MAX_ROWS / 32) * 64];
+    __shared__ unsigned s_mask[(KE_MAX_DT / 32) * 64];
     const int f = (int)blockIdx.x, c = (int)blockIdx.y, t = lane_id();
     if (t >= num_thresholds[c]) return;
     const KeFrame fr = ke_frame(F, f);
@@ -358,7 +360,7 @@ __global__ __launch_bounds__(64) void ke_curves_kernel(int frames, int aos, cons
 
 int ke_bounds_ok(int frames, long long total_gt, long long total_dt, int max_gt, int max_dt) {
     return frames >= 0 && frames <= KE_MAX_FRAMES && total_gt >= 0 && total_gt <= KE_MAX_TOTAL_GT && total_dt >= 0 &&
-           total_dt <= KE_MAX_TOTAL_DT && max_gt >= 0 && max_gt <= KE_MAX_ROWS && max_dt >= 0 && max_dt <= KE_MAX_ROWS;
+           total_dt <= KE_MAX_TOTAL_DT && max_gt >= 0 && max_gt <= KE_MAX_GT && max_dt >= 0 && max_dt <= KE_MAX_DT;
 }
 
 long long ke_pow2(long long n) {

@@ -18,9 +18,9 @@
 // multiply-adds.
 #include "common.h"
 
-#define OPT_CHUNK 1024
+#define OPT_CHUNK LIDAR_OPTIM_CHUNK
 #define OPT_THREADS 256
-#define OPT_ENTRY 6
+#define OPT_ENTRY LIDAR_OPTIM_ENTRY
 
 struct OptEntry {
     float *p;
@@ -108,7 +108,7 @@ __device__ __forceinline__ void opt_update(float &p, float &g, float &m, float &
     v = k.beta2 * v + (k.w2 * g) * g;           // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
     const float denom = sqrtf(v) / bc2_sqrt + k.eps;
     p = p + (-step_size) * (m / denom);         // param.addcdiv_(exp_avg, denom, value=-step_size)
-    if (k.flags & 2) g = 0.0f;
+    if (k.flags & LIDAR_OPTIM_ZERO_GRAD) g = 0.0f;
 }
 
 __global__ void __launch_bounds__(OPT_THREADS)
@@ -154,7 +154,7 @@ optim_adam_chunks_kernel(const OptEntry *__restrict__ table, int n_tensors, cons
         *reinterpret_cast<float4 *>(p + base) = P;
         *reinterpret_cast<float4 *>(m + base) = M;
         *reinterpret_cast<float4 *>(v + base) = V;
-        if (k.flags & 3) *reinterpret_cast<float4 *>(g + base) = G;
+        if (k.flags & (LIDAR_OPTIM_WRITE_CLIPPED | LIDAR_OPTIM_ZERO_GRAD)) *reinterpret_cast<float4 *>(g + base) = G;
     } else {
         for (int j = 0; j < 4; ++j) {
             const int i = base + j;
@@ -162,7 +162,7 @@ optim_adam_chunks_kernel(const OptEntry *__restrict__ table, int n_tensors, cons
             float P = p[i], G = g[i], M = m[i], V = v[i];
             opt_update(P, G, M, V, coef, k, step_size, bc2_sqrt);
             p[i] = P, m[i] = M, v[i] = V;
-            if (k.flags & 3) g[i] = G;
+            if (k.flags & (LIDAR_OPTIM_WRITE_CLIPPED | LIDAR_OPTIM_ZERO_GRAD)) g[i] = G;
         }
     }
 }
@@ -221,7 +221,7 @@ LIDAR_EXPORT int lidar_optim_adam_step(const long long *table, int n_tensors, co
                                        long long n_chunks, const float *norm_out, double lr, double beta1, double beta2, double eps,
                                        double decay, long long t, int flags, void *stream) {
     if (int e = opt_check_map(table, n_tensors, chunk_tensor, chunk_index, n_chunks)) return e;
-    if (!norm_out || t < 1 || flags < 0 || flags > 2) return LIDAR_ERR_ARG;
+    if (!norm_out || t < 1 || flags < 0 || flags > LIDAR_OPTIM_ZERO_GRAD) return LIDAR_ERR_ARG;
     if (n_chunks == 0) return LIDAR_OK;
     OptScalars k;
     k.decay = (float)decay;

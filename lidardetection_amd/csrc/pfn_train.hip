@@ -25,7 +25,7 @@
 #define PT_ST_MU 136
 #define PT_ST_INV 200
 #define PT_ST_N 264
-#define PT_STATS_DOUBLES 272
+#define PT_STATS_DOUBLES LIDAR_PFN_TRAIN_STATS_DOUBLES
 
 struct PfnTrainParams {
     float vx, vy, vz, xo, yo, zo;

@@ -32,8 +32,8 @@
 #include "point_head_dev.h"
 #include <math.h>
 
-#define PH_MAX_C 8
-#define PH_MAX_MEAN 8
+#define PH_MAX_C LIDAR_POINT_HEAD_MAX_CLASS
+#define PH_MAX_MEAN LIDAR_POINT_HEAD_MAX_MEAN
 
 struct PHTargetParams {
     float extra[3];

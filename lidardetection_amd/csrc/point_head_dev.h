@@ -7,9 +7,9 @@
 #include "pt_in_box_dev.h"
 
 #define PH_THREADS 256
-#define PH_MAX_N (1 << 20)
-#define PH_MAX_B 64
-#define PH_MAX_M 128
+#define PH_MAX_N LIDAR_POINT_HEAD_MAX_POINTS
+#define PH_MAX_B LIDAR_POINT_HEAD_MAX_BATCH
+#define PH_MAX_M LIDAR_POINT_HEAD_MAX_GT
 
 struct PHGt {
     BoxCS b;               // the gt box: centre, dims, cos / sin of -rz

@@ -31,8 +31,8 @@
 #include "point_head_dev.h"
 #include <math.h>
 
-#define PHMF_MAX_S 8
-#define PHMF_MAX_C 4
+#define PHMF_MAX_S LIDAR_POINT_HEAD_MF_MAX_FRAMES
+#define PHMF_MAX_C LIDAR_POINT_HEAD_MF_MAX_CLASS
 #define PHMF_MAX_W (PHMF_MAX_S * PHMF_MAX_C)
 
 struct PHMFTargetParams {

@@ -29,7 +29,6 @@
 // to an fp32 tensor; FG - BG of the roi_iou label and the hard-bg quota int(n * HARD_BG_RATIO) are Python double arithmetic and come
 // from the host.  fp32 expressions keep the reference's op order (-ffp-contract=off).
 #include "iou3d_dev.h"
-#include "../../include/lidar_hip.h"
 
 #define PT_TPB 256
 #define PT_GT_CHUNK 64

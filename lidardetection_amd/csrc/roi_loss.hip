@@ -24,8 +24,8 @@
 #include <math.h>
 
 #define RL_THREADS 1024
-#define RL_MAX_P 512
-#define RL_MAX_ROWS 65536
+#define RL_MAX_P LIDAR_ROI_LOSS_MAX_SAMPLES
+#define RL_MAX_ROWS LIDAR_ROI_LOSS_MAX_ROWS
 #define RL_BWD_THREADS 256
 
 struct RLParams {

@@ -9,12 +9,12 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import LIMITS
 
 CLASS_NAMES = ["car", "pedestrian", "cyclist", "van", "person_sitting", "truck"]    # clean_data's list, lower-cased as it compares
-CLS_DONTCARE, CLS_OTHER = 6, 7          # LIDAR_KITTI_EVAL_CLS_*
-GT_COLS, DT_COLS = 14, 13               # LIDAR_KITTI_EVAL_GT_COLS / _DT_COLS
-MAX_GT = MAX_DT = 1024                  # rows of one frame
-MAX_CLASS, MAX_DIFF, MAX_OVERLAP, PTS = 8, 3, 16, 41
+CLS_DONTCARE, CLS_OTHER, GT_COLS, DT_COLS, MAX_GT, MAX_DT, MAX_CLASS, MAX_DIFF, MAX_OVERLAP, PTS = (
+    LIMITS["LIDAR_KITTI_EVAL_" + k] for k in ("CLS_DONTCARE", "CLS_OTHER", "GT_COLS", "DT_COLS", "MAX_GT", "MAX_DT", "MAX_CLASS",
+                                              "MAX_DIFF", "MAX_OVERLAP", "PTS"))
 _ID_NAMES = CLASS_NAMES + ["DontCare", "other"]
 
 

@@ -16,11 +16,9 @@ import torch
 from torch import nn
 
 from . import _lib
-from ._lib import LidarHipError
+from ._lib import LIMITS, LidarHipError
 
-CHUNK = 1024            # LIDAR_OPTIM_CHUNK
-_ENTRY = 6              # LIDAR_OPTIM_ENTRY
-WRITE_CLIPPED, ZERO_GRAD = 1, 2
+CHUNK, _ENTRY, WRITE_CLIPPED, ZERO_GRAD = (LIMITS["LIDAR_OPTIM_" + k] for k in ("CHUNK", "ENTRY", "WRITE_CLIPPED", "ZERO_GRAD"))
 _BN_TYPES = (nn.BatchNorm1d, nn.BatchNorm2d, nn.BatchNorm3d, nn.SyncBatchNorm)
 
 

@@ -2,6 +2,7 @@
 import torch
 
 from . import _lib, bn_train, workspace
+from ._lib import LIMITS
 
 
 def fold_bn(gamma, beta, mean, var, eps):
@@ -116,7 +117,7 @@ class PillarMap:
 
 
 # ------------------------------------------------------------------ training (csrc/pfn_train.hip)
-_STATS_DOUBLES = 272      # lidar_pfn_train_forward's `stats` (include/lidar_hip.h)
+_STATS_DOUBLES = LIMITS["LIDAR_PFN_TRAIN_STATS_DOUBLES"]      # lidar_pfn_train_forward's `stats`
 
 
 def pfn_train_supported(num_features, max_points, cout):

@@ -11,10 +11,9 @@ from dataclasses import dataclass
 import torch
 
 from . import _lib
-from ._lib import cfg_get
+from ._lib import LIMITS, cfg_get
 
-# include/lidar_hip.h: LIDAR_POINT_HEAD_*
-MAX_POINTS, MAX_BATCH, MAX_GT, MAX_CLASS, MAX_MEAN = 1 << 20, 64, 128, 8, 8
+MAX_POINTS, MAX_BATCH, MAX_GT, MAX_CLASS, MAX_MEAN = (LIMITS["LIDAR_POINT_HEAD_MAX_" + k] for k in ("POINTS", "BATCH", "GT", "CLASS", "MEAN"))
 CODE_SIZE = 8
 
 

@@ -10,10 +10,10 @@ Outputs and the workspace come from torch's caching allocator; nothing synchroni
 import torch
 
 from . import _lib
+from ._lib import LIMITS
 from .point_head import MAX_BATCH, MAX_GT, MAX_POINTS, PointHeadSpec, spec_from_cfg  # noqa: F401  (re-exported)
 
-# include/lidar_hip.h: LIDAR_POINT_HEAD_MF_*
-MAX_FRAMES, MAX_CLASS = 8, 4
+MAX_FRAMES, MAX_CLASS = LIMITS["LIDAR_POINT_HEAD_MF_MAX_FRAMES"], LIMITS["LIDAR_POINT_HEAD_MF_MAX_CLASS"]
 
 
 def supported(n, batch, m, stack_frame_size, num_class=1):

@@ -11,8 +11,10 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import LIMITS
 
-MAX_ROIS, MAX_GT, MAX_SAMPLES, MAX_DIM = 1024, 512, 512, 16      # include/lidar_hip.h: LIDAR_PROPOSAL_TARGET_*
+MAX_ROIS, MAX_GT = LIMITS["LIDAR_PROPOSAL_TARGET_MAX_ROIS"], LIMITS["LIDAR_PROPOSAL_TARGET_MAX_GT"]
+MAX_SAMPLES, MAX_DIM = LIMITS["LIDAR_PROPOSAL_TARGET_MAX_SAMPLES"], LIMITS["LIDAR_PROPOSAL_TARGET_MAX_DIM"]
 CLS_SCORE_TYPES = {"cls": 0, "roi_iou": 1}
 
 

@@ -10,9 +10,9 @@ from dataclasses import dataclass
 import torch
 
 from . import _lib
-from ._lib import cfg_get
+from ._lib import LIMITS, cfg_get
 
-MAX_SAMPLES, MAX_ROWS = 512, 65536      # include/lidar_hip.h: LIDAR_ROI_LOSS_*
+MAX_SAMPLES, MAX_ROWS = LIMITS["LIDAR_ROI_LOSS_MAX_SAMPLES"], LIMITS["LIDAR_ROI_LOSS_MAX_ROWS"]
 
 
 @dataclass(frozen=True)

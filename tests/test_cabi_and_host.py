@@ -33,6 +33,53 @@ def test_header_symbols_exported_and_bound():
     _lib.lib()  # resolves + types every symbol
 
 
+def test_bound_types_are_the_parsed_header():
+    """every function of the loaded library carries exactly the types parse_header reads from the header, and LIMITS its constants"""
+    sigs, limits = _lib.parse_header(open(os.path.join(ROOT, "include", "lidar_hip.h")).read())
+    assert sorted(sigs) == _declared() and sigs == _lib.SIGNATURES and limits == _lib.LIMITS
+    L = _lib.lib()
+    for n, (res, args) in sigs.items():
+        fn = getattr(L, n)
+        assert fn.restype is res and list(fn.argtypes) == args, n
+
+
+vp, i32, i64, f32, f64, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_float, ctypes.c_double, ctypes.c_size_t
+# typed by hand from the header's text, one for each kind of type the parser maps: the parser cannot be wrong and these still hold
+PINNED = {
+    "lidar_voxelize_workspace_bytes": (sz, [i32, i32, i32]),                                  # size_t return
+    "lidar_timer_destroy": (None, [vp]),                                                      # void return
+    "lidar_timer_create": (vp, []),                                                           # pointer return, (void) list
+    "lidar_nms_mask_ptr": (vp, [vp, i32, i32]),                                               # const pointer return
+    "lidar_timer_elapsed_ms": (f32, [vp]),                                                    # float return
+    "lidar_optim_plan": (i64, [vp, i32, vp, vp, i64]),                                        # long long return
+    "lidar_optim_adam_step": (i32, [vp, i32, vp, vp, i64, vp, f64, f64, f64, f64, f64, i64, i32, vp]),      # double parameters
+    "lidar_ball_query_stack2": (i32, [i32, i32, f32, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp]),           # float parameters
+    "lidar_head_rows": (i32, [vp, vp, i32, i32, i64, i32, vp, i32, vp, i32, i32, i32, i32, vp, i32, i64, vp, vp]),
+    "lidar_bn_relu_train_workspace_bytes": (sz, [i64, i32]),
+    "lidar_bn_relu_train_forward": (i32, [i32, vp, vp, vp, vp, i64, vp, vp, f32, vp, i32, i32, vp, vp, vp, vp, sz, vp]),   # void *const *x
+    "lidar_voxelize_cpu": (i32, [vp, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp, sz]),    # size_t last, no stream
+}
+# the two longest lists: length, and where their arguments are not pointers
+PINNED_LONG = {
+    "lidar_augment": (39, {2: i32, 3: i32, 6: i32, 7: i32, 12: i32, 13: i32, 15: i32, 16: i32, 27: i32, 28: i32, 29: i64, 30: i32, 37: sz}),
+    "lidar_kitti_eval_class": (32, {0: i32, 10: i32, 11: i64, 12: i64, 13: i64, 14: i32, 15: i32, 17: i32, 19: i32, 21: i32, 22: i32,
+                                    30: sz}),
+}
+
+
+def test_signatures_pinned_by_hand():
+    for n, sig in PINNED.items():
+        assert _lib.SIGNATURES[n] == sig, n
+    for n, (count, scalars) in PINNED_LONG.items():
+        res, args = _lib.SIGNATURES[n]
+        assert res is i32 and len(args) == count, n
+        assert {i: a for i, a in enumerate(args) if a is not vp} == scalars, n
+    assert {k: _lib.LIMITS[k] for k in ("LIDAR_OK", "LIDAR_ERR_ARG", "LIDAR_ERR_LAUNCH", "LIDAR_ERR_WORKSPACE", "LIDAR_ERR_UNSUPPORTED")} == {
+        "LIDAR_OK": 0, "LIDAR_ERR_ARG": -1, "LIDAR_ERR_LAUNCH": -2, "LIDAR_ERR_WORKSPACE": -3, "LIDAR_ERR_UNSUPPORTED": -4}
+    assert _lib.LIMITS["LIDAR_POINT_HEAD_MAX_POINTS"] == 1 << 20 and _lib.LIMITS["LIDAR_KITTI_EVAL_MAX_TOTAL_DT"] == 1 << 22
+    assert _lib.LIMITS["LIDAR_PFN_TRAIN_STATS_DOUBLES"] == 272 and "LIDAR_HIP_H" not in _lib.LIMITS
+
+
 def test_workspace_queries_are_pure_host():
     L = _lib.lib()
     assert L.lidar_voxelize_workspace_bytes(16, 20000, 16000) > 16 * 20000 * 4

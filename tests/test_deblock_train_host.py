@@ -25,10 +25,7 @@ LIB3 = ("library", "library", "library")
 
 def _declared_range():
     """LIDAR_DECONV_TRAIN_* as include/lidar_hip.h declares them"""
-    import re
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    txt = open(os.path.join(root, "include", "lidar_hip.h")).read()
-    return {k: int(v) for k, v in re.findall(r"#define LIDAR_DECONV_TRAIN_(\w+) (\d+)", txt)}
+    return {k[len("LIDAR_DECONV_TRAIN_"):]: v for k, v in _lib.LIMITS.items() if k.startswith("LIDAR_DECONV_TRAIN_")}
 
 
 def test_supported_range_edges():

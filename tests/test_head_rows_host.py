@@ -1,8 +1,6 @@
 """Host-side checks (no GPU) of csrc/head_rows.hip and the rows decode of csrc/anchor_post.hip: the support predicate over its
 declared ranges and just outside them, and status codes instead of launches for bad or empty arguments."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 
@@ -18,9 +16,8 @@ def _buf(n, fill=7.0):
 
 def test_supported_predicate_over_the_declared_ranges():
     ok = _lib.lib().lidar_head_rows_supported
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    txt = open(os.path.join(root, "include", "lidar_hip.h")).read()
-    assert re.findall(r"#define LIDAR_HEAD_ROWS_MAX_C (\d+)", txt) == ["1024"]
+    assert _lib.LIMITS["LIDAR_HEAD_ROWS_MAX_C"] == 1024
+    assert (_lib.LIMITS["LIDAR_HEAD_ROWS_MAX_ANCHORS"], _lib.LIMITS["LIDAR_HEAD_ROWS_MAX_DIR_BINS"]) == (8, 4)
     # C: multiples of 4 from 4 to 1024
     assert ok(4, 6, 2, 0) == 1 and ok(384, 6, 2, 0) == 1 and ok(1024, 6, 2, 0) == 1
     assert ok(1028, 6, 2, 0) == 0 and ok(6, 6, 2, 0) == 0 and ok(0, 6, 2, 0) == 0 and ok(-4, 6, 2, 0) == 0 and ok(2, 6, 2, 0) == 0

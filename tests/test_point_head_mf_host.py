@@ -95,8 +95,7 @@ def test_supported_predicate_at_each_bound():
         for v in bad:
             assert not point_head_mf.supported(**dict(ok, **{k: v})), (k, v)
     assert (point_head_mf.MAX_FRAMES, point_head_mf.MAX_CLASS) == (8, 4)
-    txt = open(os.path.join(os.path.dirname(GOLDEN), os.pardir, "include", "lidar_hip.h")).read()
-    assert "#define LIDAR_POINT_HEAD_MF_MAX_FRAMES 8" in txt and "#define LIDAR_POINT_HEAD_MF_MAX_CLASS 4" in txt
+    assert _lib.LIMITS["LIDAR_POINT_HEAD_MF_MAX_FRAMES"] == 8 and _lib.LIMITS["LIDAR_POINT_HEAD_MF_MAX_CLASS"] == 4
     assert point_head_mf.workspace_bytes(-1) == 0 and point_head_mf.workspace_bytes(0) > 0      # N = 0 still holds the count
     assert point_head_mf.workspace_bytes(257) > 0 and point_head_mf.workspace_bytes((1 << 20) + 1) == 0
 
