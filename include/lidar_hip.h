@@ -814,8 +814,27 @@ int lidar_proposal_target(const float *rois, const float *roi_scores, const long
  * Supported (lidar_augment_supported, pure host; everything else is refused with LIDAR_ERR_ARG before any launch): 3 <= C <= 8,
  * 1 <= groups <= 8, 0 <= per_group <= 64, max_gt + groups * per_group <= 512; batch >= 0 (0 launches nothing); frames of 0 points
  * and frames with gt_counts 0 are valid.  With C == 4 the point arrays, and always out_gt_boxes, must be 16-byte aligned.
- * NOT built: carrying the `locations` / `rotations_y` multi-frame extras of the reference through the augmentation (their consumers,
- * lidar_point_targets_mf and lidar_multiframe_enlarged_boxes, are below), and velocity columns (boxes are 7 wide). */
+ * NOT built: velocity columns (boxes are 7 wide).
+ *
+ * lidar_augment_mf: the same call with the multi-frame extras of the reference carried along (database_sampler.py:165-177,
+ * augmentor_utils.py:24-28, :51-55, :80-84, :105-107, data_processor.py:29-32, dataset.py:139-142): every gt has a pose in each of
+ * the S = stack_frames stacked sweeps.  The same kernels run; the thread of aug_frame_kernel that owns a box row also owns its S poses
+ * and writes them at the box's compacted rank.  points, point_offsets, gt_boxes, gt_counts and sample_valid come out bitwise as from
+ * lidar_augment.  All DEVICE f32, 4-byte aligned:
+ *   gt_locations (batch, max_gt, S, 3), gt_rotations_y (batch, max_gt, S): rows past gt_counts are ignored; db_locations (n_obj, S, 3),
+ *   db_rotations_y (n_obj, S): the database objects' poses in the absolute frame of db_boxes.
+ *   -> out_locations (batch, max_gt + groups * per_group, S, 3), out_rotations_y (batch, max_gt + groups * per_group, S): row r is
+ *   the pose of row r of out_gt_boxes; every element is written, rows at and past out_gt_counts[b] are zero.
+ * Per row and sweep, fp32 in the reference's order.  A pasted sample: z -= mv (the road-plane shift of its box); with sample_rot a:
+ * rotations_y += a, location -= centre, turned by a with the [cos, sin] the object's points get, += centre (centre: the sample's box
+ * xyz after the road plane).  Every kept row: the world flips (flip x: y and rotations_y negated; flip y: x negated, rotations_y =
+ * -(rotations_y + pi)), the world rotation's matrix and rotations_y += rot, scaling of the location.  rotations_y is NOT folded by
+ * limit_period (the reference folds the boxes' heading only).  A pose row is kept iff its box is: the poses are not range-tested.
+ * Declared divergence: a class-id-0 row is dropped from the boxes AND from both pose arrays.  The reference masks gt_boxes with
+ * gt_boxes_mask but concatenates the samples' poses onto its unmasked `locations` (add_sampled_boxes_to_scene) and masks only boxes
+ * and names in DataAugmentor.forward, after which its pose rows no longer line up with its box rows; that defect is not reproduced.
+ * Supported (lidar_augment_mf_supported): what lidar_augment_supported accepts and 1 <= stack_frames <= 8; NULL or misaligned pose
+ * arrays are refused with LIDAR_ERR_ARG before any launch; batch == 0 launches nothing.  The workspace is lidar_augment's. */
 #define LIDAR_AUGMENT_MAX_FEATURES 8
 #define LIDAR_AUGMENT_MAX_GROUPS 8
 #define LIDAR_AUGMENT_MAX_PER_GROUP 64
@@ -830,6 +849,17 @@ int lidar_augment(const float *points, const int *point_offsets, int n_points, i
                   int remove_outside_boxes, int min_num_corners, long long obj_rows_bound, int cap, float *out_points,
                   int *out_offsets, float *out_gt_boxes, int *out_gt_counts, int *sample_valid, void *ws, size_t ws_bytes,
                   void *stream);
+#define LIDAR_AUGMENT_MF_MAX_FRAMES 8
+int lidar_augment_mf_supported(int num_features, int max_gt, int groups, int per_group, int stack_frames);
+int lidar_augment_mf(const float *points, const int *point_offsets, int n_points, int num_features, const float *gt_boxes,
+                     const int *gt_counts, int batch, int max_gt, const float *db_points, const int *db_offsets, const float *db_boxes,
+                     const int *db_cls, int n_obj, int db_rows, const int *cand, int groups, int per_group, const int *flip_x,
+                     const int *flip_y, const float *rot, const float *rot_cs, const float *scale, const float *sample_rot,
+                     const float *plane, const float *remove_extra_width, const float *collide_extra_width, const float *pc_range,
+                     int remove_outside_boxes, int min_num_corners, long long obj_rows_bound, int cap, const float *gt_locations,
+                     const float *gt_rotations_y, const float *db_locations, const float *db_rotations_y, int stack_frames,
+                     float *out_points, int *out_offsets, float *out_gt_boxes, int *out_gt_counts, int *sample_valid,
+                     float *out_locations, float *out_rotations_y, void *ws, size_t ws_bytes, void *stream);
 
 /* ------------------------------------------------------------------ anchor-head RPN loss (training), forward + backward
  * AnchorHeadTemplate.get_loss / AnchorHeadMulti.get_loss for a whole batch and every head, no host synchronisation, no float atomics
@@ -969,7 +999,8 @@ int lidar_point_loss_backward(const float *point_cls_preds, const float *point_b
  *       centre, rotated by -gt[6], max - min).  gt_dim must be 8: with more columns the reference's [:, -2] is not the heading.
  * Supported (lidar_point_head_mf_supported, pure host; everything else is refused with LIDAR_ERR_ARG before any launch):
  * 0 <= n <= 2^20, 1 <= batch <= 64, 0 <= m <= 128, 1 <= S <= 8, 1 <= num_class <= 4 (at most 32 logit columns).
- * NOT built: REG_TRACKING_INFO of ProposalTargetLayer and the RoI loss, and the multi-frame extras of lidar_augment. */
+ * The poses these take come out of lidar_augment_mf during training (same layout: zero rows past the count).
+ * NOT built: REG_TRACKING_INFO of ProposalTargetLayer and the RoI loss. */
 #define LIDAR_POINT_HEAD_MF_MAX_FRAMES 8
 #define LIDAR_POINT_HEAD_MF_MAX_CLASS 4
 int lidar_point_head_mf_supported(long long n, int batch, int m, int stack_frames, int num_class);

@@ -9,6 +9,10 @@ sees": GT sampling (pcdet/datasets/augmentor/database_sampler.py), random world 
   TrainAugmentor   draws the per-frame flips, angle and scale on the host, allocates the outputs from torch's caching allocator,
                    launches on the current stream and never synchronises
 
+Multi-frame models (tools/cfgs/livox_models/pv_rcnn_multiframe.yaml): a GtDatabase built with locations / rotations_y and a call given
+locations= / rotations_y= go through lidar_augment_mf, which moves every gt's pose in each stacked sweep with its box (the reference's
+database_sampler.py:165-177, augmentor_utils.py, data_processor.py:29-32); the result feeds lidardetection_amd/point_head_mf.py.
+
 The kernels draw nothing; every random number comes from a generator (or from arrays) the caller passes."""
 import numpy as np
 import torch
@@ -18,6 +22,7 @@ from ._lib import LIMITS
 
 MAX_FEATURES, MAX_GROUPS = LIMITS["LIDAR_AUGMENT_MAX_FEATURES"], LIMITS["LIDAR_AUGMENT_MAX_GROUPS"]
 MAX_PER_GROUP, MAX_BOXES = LIMITS["LIDAR_AUGMENT_MAX_PER_GROUP"], LIMITS["LIDAR_AUGMENT_MAX_BOXES"]
+MAX_FRAMES = LIMITS["LIDAR_AUGMENT_MF_MAX_FRAMES"]
 
 
 def fakelidar_to_lidar(boxes):
@@ -32,9 +37,12 @@ class GtDatabase:
     """points (P, C) f32: every object's points, object-local as the reference's .bin files store them; offsets (n_obj + 1);
     boxes (n_obj, 7); cls (n_obj) 1-based class ids; difficulty / num_points_in_gt (n_obj) for the PREPARE filters (defaults: 0 and
     the object's point count).  fakelidar=True (DATABASE_WITH_FAKELIDAR): the boxes are converted once, here; the reference moves
-    the object points to the unconverted (bottom) centre, so the stored points are lowered by h / 2 to keep that placement."""
+    the object points to the unconverted (bottom) centre, so the stored points are lowered by h / 2 to keep that placement.
+    locations (n_obj, S, 3), rotations_y (n_obj, S): every object's pose in each of the S stacked sweeps of the multi-frame models,
+    in the frame of `boxes` as they are kept here (both or neither; db.S is 0 without them)."""
 
-    def __init__(self, points, offsets, boxes, cls, difficulty=None, num_points_in_gt=None, fakelidar=False, device="cuda"):
+    def __init__(self, points, offsets, boxes, cls, difficulty=None, num_points_in_gt=None, fakelidar=False, device="cuda",
+                 locations=None, rotations_y=None):
         points = np.ascontiguousarray(points, np.float32)
         offsets = np.ascontiguousarray(offsets, np.int64)
         boxes = np.ascontiguousarray(boxes, np.float32)
@@ -48,6 +56,17 @@ class GtDatabase:
             _lib.fail("augment", "database offsets must ascend from 0 to the number of points")
         if np.any(cls < 1):
             _lib.fail("augment", "database class ids are 1-based")
+        if (locations is None) != (rotations_y is None):
+            _lib.fail("augment", "database locations and rotations_y come together: one of them is missing")
+        self.S = 0
+        if locations is not None:
+            locations, rotations_y = np.ascontiguousarray(locations, np.float32), np.ascontiguousarray(rotations_y, np.float32)
+            if locations.ndim != 3 or locations.shape[0] != n or locations.shape[2] != 3 or rotations_y.shape != locations.shape[:2]:
+                _lib.fail("augment", f"database locations must be ({n}, S, 3) and rotations_y ({n}, S), got {locations.shape} and "
+                          f"{rotations_y.shape}")
+            self.S = int(locations.shape[1])
+            if not 1 <= self.S <= MAX_FRAMES:
+                _lib.fail("augment", f"1 <= stacked sweeps S <= {MAX_FRAMES}, got database locations {locations.shape}")
         if fakelidar:
             points = points.copy()
             points[:, 2] -= np.repeat(boxes[:, 5] / 2, np.diff(offsets))
@@ -64,6 +83,8 @@ class GtDatabase:
         self.offsets = torch.from_numpy(offsets.astype(np.int32)).to(dev)
         self.boxes = torch.from_numpy(boxes).to(dev)
         self.cls = torch.from_numpy(cls).to(dev)
+        self.locations = None if locations is None else torch.from_numpy(locations).to(dev)
+        self.rotations_y = None if rotations_y is None else torch.from_numpy(rotations_y).to(dev)
 
     def indices_of_class(self, cls_id, removed_difficulty=(), min_points=0):
         """database indices of one class, in database order, after filter_by_difficulty (database_sampler.py:50-60) and
@@ -185,13 +206,18 @@ class TrainAugmentor:
         return d
 
     def __call__(self, points, point_offsets, gt_boxes, gt_counts, cand, rng=None, planes=None, shuffle=False, flip_x=None,
-                 flip_y=None, rot=None, scale=None, sample_rot=None, shuffle_keys=None, host_offsets=None, cap=None):
+                 flip_y=None, rot=None, scale=None, sample_rot=None, shuffle_keys=None, host_offsets=None, cap=None, locations=None,
+                 rotations_y=None):
         """points (sum N, C) f32, point_offsets (B + 1) i32, gt_boxes (B, M, 8) f32 [box | class id], gt_counts (B) i32: device
         tensors.  cand (B, G, S) int32 HOST array (DbSampler.sample).  rng: the generator the draws come from; flip_x, flip_y, rot,
         scale (B), sample_rot (B, G, S) given explicitly (host arrays) replace their draws.  planes (B, 4): road_plane_lidar per
         frame.  -> dict: points (cap, C), point_offsets (B + 1), gt_boxes (B, M + G * S, 8), gt_counts (B), sample_valid (B, G, S)
         device tensors, n_max (host int: a bound on one output frame's points) — ready for PointPillarKITTI.train_loss(points,
-        point_offsets, gt_boxes) with host_offsets=None.  Rows of `points` at and past point_offsets[B] are unspecified."""
+        point_offsets, gt_boxes) with host_offsets=None.  Rows of `points` at and past point_offsets[B] are unspecified.
+        locations (B, M, F, 3), rotations_y (B, M, F) f32 device tensors (both or neither; the database must carry poses of the
+        same F): the gts' poses in each stacked sweep.  They follow their boxes through every step (lidar_augment_mf) and the dict
+        gains locations (B, M + G * S, F, 3) and rotations_y (B, M + G * S, F), zero past gt_counts — what
+        point_head_mf.assign_point_targets_mf and enlarged_gt_boxes take."""
         db = self.db
         if points.dim() != 2 or points.dtype != torch.float32:
             _lib.fail("augment", f"points must be float32 (sum N, C), got {points.dtype} {tuple(points.shape)}")
@@ -206,6 +232,19 @@ class TrainAugmentor:
         M = int(gt_boxes.shape[1])
         if tuple(gt_counts.shape) != (B,) or gt_counts.dtype != torch.int32:
             _lib.fail("augment", f"gt_counts must be int32 ({B},), got {gt_counts.dtype} {tuple(gt_counts.shape)}")
+        if (locations is None) != (rotations_y is None):
+            _lib.fail("augment", "locations and rotations_y come together: one of them is missing")
+        F = 0
+        if locations is not None:
+            if (locations.dim() != 4 or tuple(locations.shape[:2]) != (B, M) or locations.shape[3] != 3 or
+                    tuple(rotations_y.shape) != tuple(locations.shape[:3]) or locations.dtype != torch.float32 or
+                    rotations_y.dtype != torch.float32):
+                _lib.fail("augment", f"locations must be float32 ({B}, {M}, S, 3) and rotations_y float32 ({B}, {M}, S), got {locations.dtype} "
+                          f"{tuple(locations.shape)} and {rotations_y.dtype} {tuple(rotations_y.shape)}")
+            F = int(locations.shape[2])
+            if db.S != F or not 1 <= F <= MAX_FRAMES:
+                _lib.fail("augment", f"locations {tuple(locations.shape)} need a database with poses of the same 1 <= S <= {MAX_FRAMES}; "
+                          f"the database's locations are {None if db.locations is None else tuple(db.locations.shape)}")
         cand = np.asarray(cand)
         if cand.ndim != 3 or cand.shape[0] != B or cand.shape[1] != self.G or not np.issubdtype(cand.dtype, np.integer):
             _lib.fail("augment", f"cand must be an integer ({B}, {self.G}, S) host array, got {cand.dtype} {cand.shape}")
@@ -233,7 +272,7 @@ class TrainAugmentor:
             n_max = int(self.frame_points_max) + (int(per_frame.max()) if B else 0)
         else:
             n_max = int(cap)
-        _lib.require_cuda(points, point_offsets, gt_boxes, gt_counts)
+        _lib.require_cuda(points, point_offsets, gt_boxes, gt_counts, locations, rotations_y)
         draws = self.draw(B, S, rng) if rng is not None else {}
 
         def pick(name, given, shape, dtype, optional=False):
@@ -271,6 +310,9 @@ class TrainAugmentor:
             "sample_valid": torch.empty((B, self.G, S), dtype=torch.int32, device=dev),
             "n_max": n_max,
         }
+        if F:
+            out["locations"] = torch.empty((B, M + T, F, 3), dtype=torch.float32, device=dev)
+            out["rotations_y"] = torch.empty((B, M + T, F), dtype=torch.float32, device=dev)
         if B == 0:
             out["point_offsets"].zero_()
             return out
@@ -278,14 +320,19 @@ class TrainAugmentor:
         ws_bytes = int(L.lidar_augment_workspace_bytes(B, self.G, S, cap))
         if self._ws is None or self._ws.numel() < ws_bytes or self._ws.device != dev:
             self._ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-        status = L.lidar_augment(
-            _lib.ptr(points), _lib.ptr(point_offsets), n_points, C, _lib.ptr(gt_boxes), _lib.ptr(gt_counts), B, M, _lib.ptr(db.points),
-            _lib.ptr(db.offsets), _lib.ptr(db.boxes), _lib.ptr(db.cls), db.n_obj, int(db.points.shape[0]), _lib.ptr(d_cand), self.G, S,
-            _lib.ptr(d_fx), _lib.ptr(d_fy), _lib.ptr(d_rot), _lib.ptr(d_cs), _lib.ptr(d_sc), _lib.ptr(d_sr), _lib.ptr(d_pl), self._rw_h,
-            self._cw_h, self._range_h, int(self.remove_outside_boxes), self.min_num_corners, obj_bound, cap, _lib.ptr(out["points"]),
-            _lib.ptr(out["point_offsets"]), _lib.ptr(out["gt_boxes"]), _lib.ptr(out["gt_counts"]), _lib.ptr(out["sample_valid"]),
-            _lib.ptr(self._ws), ws_bytes, _lib.stream())
-        _lib.check(status, "lidar_augment")
+        head = (_lib.ptr(points), _lib.ptr(point_offsets), n_points, C, _lib.ptr(gt_boxes), _lib.ptr(gt_counts), B, M, _lib.ptr(db.points),
+                _lib.ptr(db.offsets), _lib.ptr(db.boxes), _lib.ptr(db.cls), db.n_obj, int(db.points.shape[0]), _lib.ptr(d_cand), self.G, S,
+                _lib.ptr(d_fx), _lib.ptr(d_fy), _lib.ptr(d_rot), _lib.ptr(d_cs), _lib.ptr(d_sc), _lib.ptr(d_sr), _lib.ptr(d_pl), self._rw_h,
+                self._cw_h, self._range_h, int(self.remove_outside_boxes), self.min_num_corners, obj_bound, cap)
+        outs = (_lib.ptr(out["points"]), _lib.ptr(out["point_offsets"]), _lib.ptr(out["gt_boxes"]), _lib.ptr(out["gt_counts"]),
+                _lib.ptr(out["sample_valid"]))
+        tail = (_lib.ptr(self._ws), ws_bytes, _lib.stream())
+        if F:
+            status = L.lidar_augment_mf(*head, _lib.ptr(locations), _lib.ptr(rotations_y), _lib.ptr(db.locations), _lib.ptr(db.rotations_y),
+                                        F, *outs, _lib.ptr(out["locations"]), _lib.ptr(out["rotations_y"]), *tail)
+            _lib.check(status, "lidar_augment_mf")
+        else:
+            _lib.check(L.lidar_augment(*head, *outs, *tail), "lidar_augment")
         if shuffle:
             if shuffle_keys is None:
                 if rng is None:

@@ -15,6 +15,8 @@
 //                      the polygon clipper of csrc/iou3d_dev.h; a candidate stays iff every IoU is exactly 0.  Then per valid sample
 //                      the road-plane height, the sample rotation and the carving box go to the workspace, and the frame's boxes
 //                      (trained input rows, then the valid samples) are world-transformed, range-masked and compacted in order.
+//                      lidar_augment_mf (template flag MF): the thread that owns a box row also moves the row's poses in the stacked
+//                      sweeps (aug_pose_row) and writes them at the box's rank; the other four kernels are the same for both.
 //   aug_plan_kernel    one workgroup: the frame's virtual rows (valid objects' points, then the scene points) are cut into blocks of
 //                      256 rows; block offsets of the frames by an exclusive scan.
 //   aug_flag_kernel    one thread per virtual row, the frame's carving boxes in LDS: keep flag (carve test for scene rows, range test
@@ -32,6 +34,7 @@
 #define AUG_ROWS 256         // rows per block of the streaming kernels == their threads per block
 #define AUG_T LIDAR_AUGMENT_MAX_BOXES
 #define AUG_REC 16           // workspace words per valid sample
+#define AUG_PI_F 3.14159265358979323846f
 
 struct AugP {
     int B, M, G, S, C, T, n_points, n_obj, db_rows, cap, nblk;
@@ -53,6 +56,13 @@ struct AugWs {
 struct AugOut {
     float *points, *gt;
     int *offsets, *gt_counts, *valid;
+};
+
+// lidar_augment_mf only: every gt's pose in each of the F stacked sweeps, carried through the last section of aug_frame_kernel
+struct AugPose {
+    const float *gt_loc, *gt_ry, *db_loc, *db_ry;
+    float *out_loc, *out_ry;
+    int F;
 };
 
 struct AugWorld {
@@ -110,13 +120,48 @@ __device__ __forceinline__ void aug_sample_box(const AugIn &in, const AugP &p, i
 
 // world flip / rotation / scaling / limit_period of a box (augmentor_utils.py, data_augmentor.py:122-124)
 __device__ __forceinline__ void aug_world_box(const AugWorld &w, float *box) {
-    const float PI_F = 3.14159265358979323846f, TWO_PI_F = 6.28318530717958647692f;
+    const float TWO_PI_F = 6.28318530717958647692f;
     if (w.fx) box[6] = -box[6];
-    if (w.fy) box[6] = -(box[6] + PI_F);
+    if (w.fy) box[6] = -(box[6] + AUG_PI_F);
     aug_world_xyz(w, box[0], box[1], box[2]);
     box[6] = box[6] + w.rot;
     if (w.has_scale) { box[3] = box[3] * w.sc; box[4] = box[4] * w.sc; box[5] = box[5] * w.sc; }
     box[6] = box[6] - floorf(box[6] / TWO_PI_F + 0.5f) * TWO_PI_F;
+}
+
+// the F poses of one kept row, written at the row's compacted rank.  i >= 0: input row i; otherwise sample k = database object c, whose
+// box centre after the road plane is ctr and which moved down by mv (database_sampler.py:165-177: z -= mv; rotations_y += a, locations
+// turned by a about the box centre with the [cos, sin] the object's points get).  Then the world flips, rotation and scaling of
+// augmentor_utils.py:24-28, :51-55, :80-84, :105-107; rotations_y is NOT folded by limit_period (data_augmentor.py:122 folds the
+// boxes' heading only)
+__device__ __forceinline__ void aug_pose_row(const AugIn &in, const AugP &p, const AugPose &ps, const AugWorld &w, int b, int i, int k,
+                                             int c, const float *ctr, float mv, int rank) {
+    const int F = ps.F;
+    const bool pasted = i < 0, srot = pasted && p.has_srot;
+    const size_t src = pasted ? (size_t)c * F : ((size_t)b * p.M + i) * F, dst = ((size_t)b * (p.M + p.T) + rank) * F;
+    const float *sl = (pasted ? ps.db_loc : ps.gt_loc) + src * 3, *sr = (pasted ? ps.db_ry : ps.gt_ry) + src;
+    float a = 0.0f, rc = 1.0f, rs = 0.0f;
+    if (srot) {
+        a = in.sample_rot[(size_t)b * p.T + k];
+        heading_cs(a, rc, rs);
+    }
+    for (int s = 0; s < F; ++s) {
+        float x = sl[s * 3], y = sl[s * 3 + 1], z = sl[s * 3 + 2], ry = sr[s];
+        if (pasted && p.has_plane) z = z - mv;
+        if (srot) {
+            ry = ry + a;
+            x = x - ctr[0]; y = y - ctr[1]; z = z - ctr[2];
+            const float nx = x * rc + y * (-rs), ny = x * rs + y * rc;
+            x = nx + ctr[0]; y = ny + ctr[1]; z = z + ctr[2];
+        }
+        if (w.fx) ry = -ry;
+        if (w.fy) ry = -(ry + AUG_PI_F);
+        aug_world_xyz(w, x, y, z);
+        ry = ry + w.rot;
+        float *ol = ps.out_loc + (dst + s) * 3;
+        ol[0] = x; ol[1] = y; ol[2] = z;
+        ps.out_ry[dst + s] = ry;
+    }
 }
 
 // corners of boxes_to_corners_3d inside the closed 3-D range
@@ -157,7 +202,9 @@ struct AugFrameLds {
     int n_exist, n_out;
 };
 
-__global__ __launch_bounds__(AUG_TPB) void aug_frame_kernel(AugIn in, AugP p, AugWs ws, AugOut o) {
+// MF: the rows' poses follow their boxes (lidar_augment_mf); without it `ps` is not read
+template <bool MF>
+__global__ __launch_bounds__(AUG_TPB) void aug_frame_kernel(AugIn in, AugP p, AugWs ws, AugOut o, AugPose ps) {
     __shared__ AugFrameLds L;
     const int b = blockIdx.x, t = threadIdx.x, wv = t >> 6;
     const int M = p.M, S = p.S, T = p.T;
@@ -273,16 +320,18 @@ __global__ __launch_bounds__(AUG_TPB) void aug_frame_kernel(AugIn in, AugP p, Au
     for (int r0 = 0; r0 < rows; r0 += AUG_TPB) {
         const int i = r0 + t;
         bool keep = false;
-        float box[8];
+        float box[8], ctr[3] = {0.0f, 0.0f, 0.0f}, mv = 0.0f;
+        int k = -1, c = -1;
         if (i < rows) {
             if (i < n) {
 #pragma unroll
                 for (int q = 0; q < 8; ++q) box[q] = gt[(size_t)i * 8 + q];
                 keep = box[7] >= 1.0f;               // class id 0: annotated, but not a trained class
             } else {
-                const int k = (int)L.exist[i] - M, c = L.cand[k];
-                float mv;
+                k = (int)L.exist[i] - M;
+                c = L.cand[k];
                 aug_sample_box(in, p, b, k, c, box, mv);
+                if (MF) { ctr[0] = box[0]; ctr[1] = box[1]; ctr[2] = box[2]; }
                 box[7] = (float)in.db_cls[c];
                 keep = true;
             }
@@ -295,9 +344,11 @@ __global__ __launch_bounds__(AUG_TPB) void aug_frame_kernel(AugIn in, AugP p, Au
         int base = L.n_out;
         for (int q = 0; q < wv; ++q) base += L.wcnt[q];
         if (keep) {
-            float *dst = og + (size_t)(base + __popcll(bal & lanemask_lt())) * 8;
+            const int rank = base + __popcll(bal & lanemask_lt());
+            float *dst = og + (size_t)rank * 8;
             *reinterpret_cast<float4 *>(dst) = make_float4(box[0], box[1], box[2], box[3]);
             *reinterpret_cast<float4 *>(dst + 4) = make_float4(box[4], box[5], box[6], box[7]);
+            if (MF) aug_pose_row(in, p, ps, w, b, i < n ? i : -1, k, c, ctr, mv, rank);
         }
         __syncthreads();
         if (t == 0) {
@@ -310,6 +361,11 @@ __global__ __launch_bounds__(AUG_TPB) void aug_frame_kernel(AugIn in, AugP p, Au
     const int n_out = L.n_out;
     if (t == 0) o.gt_counts[b] = n_out;
     for (int i = n_out * 2 + t; i < (M + T) * 2; i += AUG_TPB) reinterpret_cast<float4 *>(og)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (MF) {                                        // rows at and past the count are zero in both pose arrays
+        float *ol = ps.out_loc + (size_t)b * (M + T) * ps.F * 3, *orr = ps.out_ry + (size_t)b * (M + T) * ps.F;
+        for (int i = n_out * ps.F * 3 + t; i < (M + T) * ps.F * 3; i += AUG_TPB) ol[i] = 0.0f;
+        for (int i = n_out * ps.F + t; i < (M + T) * ps.F; i += AUG_TPB) orr[i] = 0.0f;
+    }
 }
 
 // inclusive scan over the block's AUG_ROWS threads; total: the block's sum.  s_w: AUG_ROWS / 64 ints
@@ -528,15 +584,17 @@ LIDAR_EXPORT size_t lidar_augment_workspace_bytes(int batch, int groups, int per
     return bytes;
 }
 
-LIDAR_EXPORT int lidar_augment(const float *points, const int *point_offsets, int n_points, int num_features, const float *gt_boxes,
-                               const int *gt_counts, int batch, int max_gt, const float *db_points, const int *db_offsets,
-                               const float *db_boxes, const int *db_cls, int n_obj, int db_rows, const int *cand, int groups,
-                               int per_group, const int *flip_x, const int *flip_y, const float *rot, const float *rot_cs,
-                               const float *scale, const float *sample_rot, const float *plane, const float *remove_extra_width,
-                               const float *collide_extra_width, const float *pc_range, int remove_outside_boxes, int min_num_corners,
-                               long long obj_rows_bound, int cap, float *out_points, int *out_offsets, float *out_gt_boxes,
-                               int *out_gt_counts, int *sample_valid, void *ws, size_t ws_bytes, void *stream) {
+// both entry points: `ps` NULL is lidar_augment, otherwise the poses follow the boxes through aug_frame_kernel<true>
+static int aug_run(const char *what, const AugPose *ps, const float *points, const int *point_offsets, int n_points, int num_features,
+                   const float *gt_boxes, const int *gt_counts, int batch, int max_gt, const float *db_points, const int *db_offsets,
+                   const float *db_boxes, const int *db_cls, int n_obj, int db_rows, const int *cand, int groups, int per_group,
+                   const int *flip_x, const int *flip_y, const float *rot, const float *rot_cs, const float *scale,
+                   const float *sample_rot, const float *plane, const float *remove_extra_width, const float *collide_extra_width,
+                   const float *pc_range, int remove_outside_boxes, int min_num_corners, long long obj_rows_bound, int cap,
+                   float *out_points, int *out_offsets, float *out_gt_boxes, int *out_gt_counts, int *sample_valid, void *ws,
+                   size_t ws_bytes, void *stream) {
     if (batch < 0 || !lidar_augment_supported(num_features, max_gt, groups, per_group)) return LIDAR_ERR_ARG;
+    if (ps && (ps->F < 1 || ps->F > LIDAR_AUGMENT_MF_MAX_FRAMES)) return LIDAR_ERR_ARG;
     if (n_points < 0 || n_obj < 0 || db_rows < 0 || obj_rows_bound < 0 || cap < 0 || !remove_extra_width || !pc_range) return LIDAR_ERR_ARG;
     if ((long long)n_points + obj_rows_bound > (long long)cap) return LIDAR_ERR_ARG;
     if (min_num_corners < 0 || min_num_corners > 8) return LIDAR_ERR_ARG;
@@ -549,6 +607,13 @@ LIDAR_EXPORT int lidar_augment(const float *points, const int *point_offsets, in
     if ((reinterpret_cast<uintptr_t>(out_gt_boxes) & 15) || (num_features == 4 && ((reinterpret_cast<uintptr_t>(points) & 15) ||
         (reinterpret_cast<uintptr_t>(db_points) & 15) || (reinterpret_cast<uintptr_t>(out_points) & 15))))
         return LIDAR_ERR_ARG;
+    if (ps) {
+        if (!ps->out_loc || !ps->out_ry || (max_gt && (!ps->gt_loc || !ps->gt_ry)) || (n_obj && (!ps->db_loc || !ps->db_ry)))
+            return LIDAR_ERR_ARG;
+        for (const void *q : {(const void *)ps->gt_loc, (const void *)ps->gt_ry, (const void *)ps->db_loc, (const void *)ps->db_ry,
+                              (const void *)ps->out_loc, (const void *)ps->out_ry})
+            if (reinterpret_cast<uintptr_t>(q) & 3) return LIDAR_ERR_ARG;
+    }
     const int nblk = aug_blocks(batch, cap);
     size_t need = 0;
     const AugWs w = aug_carve(ws, batch, T, nblk, &need);
@@ -567,10 +632,47 @@ LIDAR_EXPORT int lidar_augment(const float *points, const int *point_offsets, in
                    point_offsets, gt_counts, db_offsets, db_cls, cand, flip_x, flip_y};
     const AugOut o{out_points, out_gt_boxes, out_offsets, out_gt_counts, sample_valid};
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(aug_frame_kernel, dim3(batch), dim3(AUG_TPB), 0, st, in, p, w, o);
+    if (ps) hipLaunchKernelGGL(aug_frame_kernel<true>, dim3(batch), dim3(AUG_TPB), 0, st, in, p, w, o, *ps);
+    else hipLaunchKernelGGL(aug_frame_kernel<false>, dim3(batch), dim3(AUG_TPB), 0, st, in, p, w, o, AugPose{});
     hipLaunchKernelGGL(aug_plan_kernel, dim3(1), dim3(AUG_ROWS), 0, st, p, w);
     hipLaunchKernelGGL(aug_flag_kernel, dim3(nblk), dim3(AUG_ROWS), 0, st, in, p, w);
     hipLaunchKernelGGL(aug_scan_kernel, dim3(1), dim3(AUG_ROWS), 0, st, p, w);
     hipLaunchKernelGGL(aug_write_kernel, dim3(nblk), dim3(AUG_ROWS), 0, st, in, p, w, o);
-    return lidar_check_launch("lidar_augment");
+    return lidar_check_launch(what);
+}
+
+LIDAR_EXPORT int lidar_augment(const float *points, const int *point_offsets, int n_points, int num_features, const float *gt_boxes,
+                               const int *gt_counts, int batch, int max_gt, const float *db_points, const int *db_offsets,
+                               const float *db_boxes, const int *db_cls, int n_obj, int db_rows, const int *cand, int groups,
+                               int per_group, const int *flip_x, const int *flip_y, const float *rot, const float *rot_cs,
+                               const float *scale, const float *sample_rot, const float *plane, const float *remove_extra_width,
+                               const float *collide_extra_width, const float *pc_range, int remove_outside_boxes, int min_num_corners,
+                               long long obj_rows_bound, int cap, float *out_points, int *out_offsets, float *out_gt_boxes,
+                               int *out_gt_counts, int *sample_valid, void *ws, size_t ws_bytes, void *stream) {
+    return aug_run("lidar_augment", nullptr, points, point_offsets, n_points, num_features, gt_boxes, gt_counts, batch, max_gt, db_points,
+                   db_offsets, db_boxes, db_cls, n_obj, db_rows, cand, groups, per_group, flip_x, flip_y, rot, rot_cs, scale, sample_rot,
+                   plane, remove_extra_width, collide_extra_width, pc_range, remove_outside_boxes, min_num_corners, obj_rows_bound, cap,
+                   out_points, out_offsets, out_gt_boxes, out_gt_counts, sample_valid, ws, ws_bytes, stream);
+}
+
+LIDAR_EXPORT int lidar_augment_mf_supported(int num_features, int max_gt, int groups, int per_group, int stack_frames) {
+    return lidar_augment_supported(num_features, max_gt, groups, per_group) && stack_frames >= 1 &&
+           stack_frames <= LIDAR_AUGMENT_MF_MAX_FRAMES;
+}
+
+LIDAR_EXPORT int lidar_augment_mf(const float *points, const int *point_offsets, int n_points, int num_features, const float *gt_boxes,
+                                  const int *gt_counts, int batch, int max_gt, const float *db_points, const int *db_offsets,
+                                  const float *db_boxes, const int *db_cls, int n_obj, int db_rows, const int *cand, int groups,
+                                  int per_group, const int *flip_x, const int *flip_y, const float *rot, const float *rot_cs,
+                                  const float *scale, const float *sample_rot, const float *plane, const float *remove_extra_width,
+                                  const float *collide_extra_width, const float *pc_range, int remove_outside_boxes,
+                                  int min_num_corners, long long obj_rows_bound, int cap, const float *gt_locations,
+                                  const float *gt_rotations_y, const float *db_locations, const float *db_rotations_y, int stack_frames,
+                                  float *out_points, int *out_offsets, float *out_gt_boxes, int *out_gt_counts, int *sample_valid,
+                                  float *out_locations, float *out_rotations_y, void *ws, size_t ws_bytes, void *stream) {
+    const AugPose ps{gt_locations, gt_rotations_y, db_locations, db_rotations_y, out_locations, out_rotations_y, stack_frames};
+    return aug_run("lidar_augment_mf", &ps, points, point_offsets, n_points, num_features, gt_boxes, gt_counts, batch, max_gt, db_points,
+                   db_offsets, db_boxes, db_cls, n_obj, db_rows, cand, groups, per_group, flip_x, flip_y, rot, rot_cs, scale, sample_rot,
+                   plane, remove_extra_width, collide_extra_width, pc_range, remove_outside_boxes, min_num_corners, obj_rows_bound, cap,
+                   out_points, out_offsets, out_gt_boxes, out_gt_counts, sample_valid, ws, ws_bytes, stream);
 }
