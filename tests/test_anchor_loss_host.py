@@ -1,12 +1,8 @@
 """Host side of the fused anchor-head loss (lidardetection_amd/anchor_loss.py): the loss spec read from the reference's configs, the
-per-head column tables, the refusals, the workspace query, and `restated_loss` — a torch restatement of the reference's RPN loss
-written for these tests — checked against the reference's own fp64 losses and autograd gradients (tests/golden/anchor_loss_ref.npz,
+per-head column tables, the refusals, the workspace query, and `restated_loss` (tests/_anchor_loss_torch.py) — a torch restatement
+of the reference's RPN loss written for these tests — checked against the reference's own fp64 losses and autograd gradients (tests/golden/anchor_loss_ref.npz,
 written by tests/golden/make_loss_golden.py).  The GPU tests trust the restatement at sizes the fixture cannot hold only because
 it reproduces the fixture here."""
-import json
-import math
-import os
-
 import numpy as np
 import pytest
 import torch
@@ -14,8 +10,7 @@ import torch
 from lidardetection_amd import _lib, anchor_loss
 from lidardetection_amd.pcdet.utils.cfg import AttrDict
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "anchor_loss_ref.npz")
-CASES = ["kitti", "agnostic", "nodir", "kitti_multi", "nus", "multi_nosep"]
+from _anchor_loss_torch import CASES, direction_bins, load_case, per_head, restated_loss
 
 # inline copies of the DENSE_HEAD loss settings of tools/cfgs/kitti_models/pointpillar.yaml,
 # tools/cfgs/nuscenes_models/cbgs_second_multihead.yaml and tools/cfgs/kitti_models/second_multihead.yaml
@@ -31,99 +26,6 @@ SECOND_MULTIHEAD = AttrDict(USE_DIRECTION_CLASSIFIER=True, DIR_OFFSET=0.78539, D
                             USE_MULTIHEAD=True, SEPARATE_MULTIHEAD=True,
                             LOSS_CONFIG=AttrDict(LOSS_WEIGHTS={"cls_weight": 1.0, "loc_weight": 2.0, "dir_weight": 0.2,
                                                                "code_weights": [1.0] * 7}))
-
-
-# ------------------------------------------------------------------------------------------------ torch restatement
-def direction_bins(targets, anchors, dir_offset, num_bins):
-    """the direction class of every anchor, in fp32 on the targets' device; divisions by fp32 tensors (true division on every
-    device, as torch's CPU kernels divide by a Python scalar)"""
-    f = lambda v: torch.tensor(v, dtype=torch.float32, device=targets.device)   # noqa: E731
-    rot = targets[..., 6].float() + anchors[:, 6].float().unsqueeze(0)
-    v = rot - f(dir_offset)
-    two_pi = f(2 * math.pi)
-    r = v - torch.floor(v / two_pi) * two_pi
-    return torch.floor(r / f(2 * math.pi / num_bins)).long().clamp(0, num_bins - 1)
-
-
-def restated_loss(cls, box, dirs, labels, targets, anchors, spec):
-    """(cls_loss, loc_loss, dir_loss) of the reference's RPN loss, differentiable.  cls / box / dirs: per-head (B, n_h, c) tensors
-    in the heads' anchor order (dirs may be empty); labels (B, N) int; targets (B, N, code) and anchors (N, D) fp32."""
-    dt = box[0].dtype
-    B, N = labels.shape
-    lab = labels.long()
-    if spec.num_class == 1:
-        lab = torch.where(lab > 0, torch.ones_like(lab), lab)
-    pos, neg = lab > 0, lab == 0
-    # the class and box weights are fp32 tensors whatever the predictions' dtype; the direction weights take the logits' dtype
-    norm32 = pos.sum(1, keepdim=True).float().clamp(min=1.0)
-    norm = pos.sum(1, keepdim=True).to(dt).clamp(min=1.0)
-    cls_w = ((pos.float() * spec.pos_cls_weight + neg.float() * spec.neg_cls_weight) / norm32).to(dt)
-    onehot = torch.nn.functional.one_hot(lab.clamp(min=0), spec.num_class + 1)[..., 1:].to(dt)
-    sep = spec.multihead and spec.separate
-    sin_diff = not spec.multihead or len(dirs) > 0
-    cw = torch.tensor(spec.code_weights, dtype=torch.float32, device=labels.device).to(dt)   # an fp32 buffer in the reference
-    bins = direction_bins(targets, anchors, spec.dir_offset, spec.num_dir_bins) if dirs else None
-    lc = ll = ld = 0.0
-    a0 = 0
-    for h, x in enumerate(cls):
-        n = x.shape[1]
-        c0 = spec.head_class_offsets[h] if sep else 0
-        t = onehot[:, a0:a0 + n, c0:c0 + x.shape[2]]
-        p = torch.sigmoid(x)
-        focal = torch.where(t > 0, 0.25 * (1.0 - p) ** 2, 0.75 * p ** 2)
-        bce = x.clamp(min=0) - x * t + torch.log1p(torch.exp(-x.abs()))
-        lc = lc + (focal * bce * cls_w[:, a0:a0 + n, None]).sum()
-        w = (pos[:, a0:a0 + n].float() / norm32).to(dt)
-        pb, t32 = box[h], targets[:, a0:a0 + n]
-        tg = t32.to(dt)
-        if sin_diff:   # the target's sin / cos in the targets' fp32, the prediction's in its own dtype
-            s = torch.sin(pb[..., 6:7]) * torch.cos(t32[..., 6:7]).to(dt)
-            c = torch.cos(pb[..., 6:7]) * torch.sin(t32[..., 6:7]).to(dt)
-            pb = torch.cat([pb[..., :6], s, pb[..., 7:]], dim=-1)
-            tg = torch.cat([tg[..., :6], c, tg[..., 7:]], dim=-1)
-        tg = torch.where(torch.isnan(tg), pb, tg)
-        d = ((pb - tg) * cw).abs()
-        if spec.reg_loss == "WeightedSmoothL1Loss":
-            beta = 1.0 / 9.0 if dt == torch.float64 else torch.tensor(1.0 / 9.0, dtype=dt).item()
-            d = torch.where(d < beta, 0.5 * d ** 2 / beta, d - 0.5 * beta)
-        ll = ll + (d * w[..., None]).sum()
-        if dirs:
-            logp = torch.log_softmax(dirs[h], dim=-1)
-            ce = -logp.gather(-1, bins[:, a0:a0 + n, None]).squeeze(-1)
-            ld = ld + (ce * (pos[:, a0:a0 + n].to(dt) / norm)).sum()
-        a0 += n
-    zero = box[0].new_zeros(())
-    return (lc / B * spec.cls_weight, ll / B * spec.loc_weight, (ld / B * spec.dir_weight) if dirs else zero)
-
-
-def load_case(name):
-    z = np.load(GOLDEN)
-    meta = json.loads(str(z[f"{name}_meta"]))
-    get = lambda short: [torch.from_numpy(z[f"{name}_{short}_{k}"]) for k in range(32) if f"{name}_{short}_{k}" in z]  # noqa: E731
-    preds = {s: get(s) for s in ["cls", "box", "dir"]}
-    grads = {s: get("g" + s) for s in ["cls", "box", "dir"]}
-    # the exact zeros of the fp64 gradients, unpacked to the gradients' shapes
-    zeros = {s: [torch.from_numpy(np.unpackbits(z[f"{name}_z{s}_{k}"])[:g.numel()].astype(bool)).reshape(g.shape)
-                 for k, g in enumerate(grads[s])] for s in ["cls", "box", "dir"]}
-    grads["zero"] = zeros
-    arr = {k: torch.from_numpy(z[f"{name}_{k}"]) for k in ["labels", "labels_after", "targets", "anchors", "gt", "loss32", "loss64"]}
-    return meta, preds, grads, arr
-
-
-def spec_of(meta):
-    return anchor_loss.spec_from_cfg(AttrDict(meta["model_cfg"]), meta["num_class"],
-                                     meta["head_num_classes"] if meta["kind"] == "multi" else None)
-
-
-def per_head(meta, preds, B):
-    """the fixture's predictions in the reference's views -> per-head (B, n_h, c) tensors"""
-    spec = spec_of(meta)
-    code = meta["code_size"]
-    cols = list(spec.head_classes) if meta["kind"] == "multi" and spec.separate else [spec.num_class] * len(preds["cls"])
-    cls = [x.reshape(B, -1, c) for x, c in zip(preds["cls"], cols)]
-    box = [x.reshape(B, -1, code) for x in preds["box"]]
-    dirs = [x.reshape(B, -1, spec.num_dir_bins) for x in preds["dir"]]
-    return spec, cls, box, dirs
 
 
 # ------------------------------------------------------------------------------------------------ tests

@@ -8,6 +8,7 @@ import pytest
 import torch
 import torch.nn as nn
 
+from _gpu_util import rel
 from lidardetection_amd import _lib, bev_train
 from lidardetection_amd.pcdet.models.backbones_2d.base_bev_backbone import BaseBEVBackbone
 from lidardetection_amd.pointpillar import make_bev_backbone
@@ -195,11 +196,6 @@ def _fixture_model(z):
     return m
 
 
-def _rel(a, b):
-    a, b = a.detach().double(), b.detach().double()
-    return float((a - b).abs().max() / max(float(b.abs().max()), 1e-30))
-
-
 def test_fixture_keys_and_float64_replay(golden_dir):
     """the fixture is consistent with itself: this repo's module tree (stock modules, float64, CPU) run on the stored inputs gives the
     stored output and gradients"""
@@ -216,19 +212,19 @@ def test_fixture_keys_and_float64_replay(golden_dir):
     G = torch.from_numpy(z["g_code"]).double() * float(z["g_scale"])
     assert tuple(x.shape) == (2, 16, 8, 4) and tuple(G.shape) == (2, 384, 8, 4)
     y = m({"spatial_features": x})["spatial_features_2d"]
-    assert _rel(y, torch.from_numpy(z["out64"])) < 2.0 ** -22           # stored rounded to float32
+    assert rel(y, torch.from_numpy(z["out64"])) < 2.0 ** -22           # stored rounded to float32
     (y * G).sum().backward()
-    assert _rel(x.grad, torch.from_numpy(z["dx64"])) < 2.0 ** -22
+    assert rel(x.grad, torch.from_numpy(z["dx64"])) < 2.0 ** -22
     n_up = 0
     for name, mod in m.named_modules():
         if isinstance(mod, nn.BatchNorm2d):
-            assert _rel(mod.weight.grad, torch.from_numpy(z["d_gamma." + name])) < 2.0 ** -22, name
-            assert _rel(mod.bias.grad, torch.from_numpy(z["d_beta." + name])) < 2.0 ** -22, name
-            assert _rel(mod.running_mean, torch.from_numpy(z["rm1." + name])) < 2.0 ** -22, name
-            assert _rel(mod.running_var, torch.from_numpy(z["rv1." + name])) < 2.0 ** -22, name
+            assert rel(mod.weight.grad, torch.from_numpy(z["d_gamma." + name])) < 2.0 ** -22, name
+            assert rel(mod.bias.grad, torch.from_numpy(z["d_beta." + name])) < 2.0 ** -22, name
+            assert rel(mod.running_mean, torch.from_numpy(z["rm1." + name])) < 2.0 ** -22, name
+            assert rel(mod.running_var, torch.from_numpy(z["rv1." + name])) < 2.0 ** -22, name
         elif isinstance(mod, (nn.Conv2d, nn.ConvTranspose2d)):
             key = name + ".weight"
             ref = torch.from_numpy(z["dw16." + key].astype(np.float64)) * float(z["dw_scale." + key])
-            assert _rel(mod.weight.grad, ref) < 2.0 ** -10, name          # float16 storage: 11 significant bits of the largest value
+            assert rel(mod.weight.grad, ref) < 2.0 ** -10, name          # float16 storage: 11 significant bits of the largest value
             n_up += isinstance(mod, nn.ConvTranspose2d)
     assert n_up == 3

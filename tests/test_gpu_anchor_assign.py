@@ -1,177 +1,23 @@
 """Anchor target assignment on the GPU (lidardetection_amd/anchor_assign.py, csrc/anchor_assign.hip) against the reference's own
 AxisAlignedTargetAssigner (tests/golden/anchor_assign_ref.npz, written by tests/golden/make_assign_golden.py) and, at sizes the
-fixture cannot hold, against `restated_assign` below: a torch restatement of the reference algorithm (per frame and anchor class,
-the full IoU matrix, argmax on the host), trusted only after it reproduces the fixture itself.
+fixture cannot hold, against `restated_assign` (tests/_anchor_assign_torch.py): a torch restatement of the reference algorithm (per frame and
+anchor class, the full IoU matrix, argmax on the host), trusted only after it reproduces the fixture itself.
 
 Tolerances: labels and weights bit-equal; targets bit-equal except the log / sin / cos columns (1e-6 absolute)."""
-import json
-import os
-
 import numpy as np
 import pytest
 import torch
 
 from lidardetection_amd.pcdet.models.dense_heads.target_assigner.axis_aligned_target_assigner import AxisAlignedTargetAssigner
 from lidardetection_amd.pcdet.models.dense_heads.target_assigner.anchor_generator import AnchorGenerator
-from lidardetection_amd.pcdet.utils.cfg import AttrDict
+
+from _anchor_assign_torch import (Coder, assert_targets_match, kitti_production, load_case, model_cfg, restated_assign,
+                                  restatement_on_fixture)
+from _gpu_util import no_host_sync
 
 pytestmark = pytest.mark.gpu
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "anchor_assign_ref.npz")
 CASES = ["kitti", "kitti_norm", "kitti_inverted", "nus", "nus_remap"]
-
-
-class Coder:
-    """the two attributes the assigner reads off a ResidualCoder"""
-    def __init__(self, code_size=7, encode_angle_by_sincos=False):
-        self.encode_angle_by_sincos = encode_angle_by_sincos
-        self.code_size = code_size + (1 if encode_angle_by_sincos else 0)
-
-
-def load_case(name):
-    z = np.load(GOLDEN)
-    meta = json.loads(str(z[f"{name}_meta"]))
-    anchors = [torch.from_numpy(z[f"{name}_anchors_{k}"]) for k in range(meta["num_anchors"])]
-    enl = torch.from_numpy(z[f"{name}_gt_enlarged"]) if f"{name}_gt_enlarged" in z else None
-    exp = {k: torch.from_numpy(z[f"{name}_{s}"]) for k, s in
-           [("box_cls_labels", "labels"), ("box_reg_targets", "targets"), ("reg_weights", "weights")]}
-    return meta, anchors, torch.from_numpy(z[f"{name}_gt"]), enl, exp
-
-
-def model_cfg(meta, norm=None):
-    cfg = AttrDict(ANCHOR_GENERATOR_CONFIG=meta["anchor_generator_config"], USE_MULTIHEAD=meta["use_multihead"],
-                   TARGET_ASSIGNER_CONFIG=AttrDict(NAME="AxisAlignedTargetAssigner", POS_FRACTION=-1.0, SAMPLE_SIZE=512,
-                                                   NORM_BY_NUM_EXAMPLES=meta["norm_by_num_examples"] if norm is None else norm,
-                                                   MATCH_HEIGHT=False, BOX_CODER="ResidualCoder"))
-    if meta["use_multihead"]:
-        cfg["SEPERATE_MULTIHEAD" if meta["seperate_multihead"] else "SEPARATE_MULTIHEAD"] = True
-        cfg["RPN_HEAD_CFGS"] = meta["rpn_head_cfgs"]
-    return cfg
-
-
-# ------------------------------------------------------------------------------------------------ torch restatement
-def _aligned_bev(boxes):
-    h = boxes[:, 6]
-    ang = (h - torch.floor(h / np.pi + 0.5) * np.pi).abs()
-    dims = torch.where((ang < np.pi / 4)[:, None], boxes[:, [3, 4]], boxes[:, [4, 3]])
-    return torch.cat((boxes[:, 0:2] - dims / 2, boxes[:, 0:2] + dims / 2), dim=1)
-
-
-def _bev_iou(a, b):
-    ba, bb = _aligned_bev(a), _aligned_bev(b)
-    w = torch.clamp_min(torch.min(ba[:, None, 2], bb[None, :, 2]) - torch.max(ba[:, None, 0], bb[None, :, 0]), min=0)
-    h = torch.clamp_min(torch.min(ba[:, None, 3], bb[None, :, 3]) - torch.max(ba[:, None, 1], bb[None, :, 1]), min=0)
-    area_a = (ba[:, 2] - ba[:, 0]) * (ba[:, 3] - ba[:, 1])
-    area_b = (bb[:, 2] - bb[:, 0]) * (bb[:, 3] - bb[:, 1])
-    inter = w * h
-    return inter / torch.clamp_min(area_a[:, None] + area_b[None, :] - inter, min=1e-6)
-
-
-def _encode(g, a, sincos):
-    a, g = a.clone(), g.clone()
-    a[:, 3:6] = torch.clamp_min(a[:, 3:6], min=1e-5)
-    g[:, 3:6] = torch.clamp_min(g[:, 3:6], min=1e-5)
-    diag = torch.sqrt(a[:, 3:4] ** 2 + a[:, 4:5] ** 2)
-    cols = [(g[:, 0:1] - a[:, 0:1]) / diag, (g[:, 1:2] - a[:, 1:2]) / diag, (g[:, 2:3] - a[:, 2:3]) / a[:, 5:6],
-            torch.log(g[:, 3:6] / a[:, 3:6])]
-    if sincos:
-        cols += [torch.cos(g[:, 6:7]) - torch.cos(a[:, 6:7]), torch.sin(g[:, 6:7]) - torch.sin(a[:, 6:7])]
-    else:
-        cols += [g[:, 6:7] - a[:, 6:7]]
-    n_extra = min(a.shape[1], g.shape[1]) - 7
-    if n_extra > 0:
-        cols.append(g[:, 7:7 + n_extra] - a[:, 7:7 + n_extra])
-    return torch.cat(cols, dim=1)
-
-
-def restated_assign(cfg, class_names, code_size, sincos, all_anchors, gt_with_cls, gt_enlarged=None):
-    """the reference's assign_targets, restated: loops over frames and anchor classes, materialises each IoU matrix and takes
-    its argmaxes on the host (numpy: first maximum)"""
-    gen_cfg = cfg.ANCHOR_GENERATOR_CONFIG
-    names = [c["class_name"] for c in gen_cfg]
-    multihead = cfg.get("USE_MULTIHEAD", False)
-    remap = {}
-    if multihead and cfg.get("SEPERATE_MULTIHEAD", False):
-        for head in cfg.RPN_HEAD_CFGS:
-            remap.update({n: i + 1 for i, n in enumerate(head["HEAD_CLS_NAME"])})
-    norm = cfg.TARGET_ASSIGNER_CONFIG.NORM_BY_NUM_EXAMPLES
-    cls_arr = np.array(class_names)
-    out_l, out_t, out_w = [], [], []
-    for b in range(gt_with_cls.shape[0]):
-        boxes, ids = gt_with_cls[b, :, :-1], gt_with_cls[b, :, -1]
-        n = boxes.shape[0]
-        while n > 1 and boxes[n - 1].sum() == 0:
-            n -= 1
-        boxes, ids = boxes[:n], ids[:n].int()
-        enl = gt_enlarged[b, :n, :-1] if gt_enlarged is not None else None
-        per_class = []
-        for cname, cgen, anchors in zip(names, gen_cfg, all_anchors):
-            fmap = anchors.shape[:3]
-            anchors = (anchors.permute(3, 4, 0, 1, 2, 5) if multihead else anchors).contiguous().view(-1, anchors.shape[-1])
-            mask = torch.from_numpy(np.array([cls_arr[int(c) - 1] == cname for c in ids.cpu()], dtype=bool)).to(boxes.device)
-            g, gid = boxes[mask], ids[mask].clone()
-            if cname in remap and len(gid):
-                gid[:] = remap[cname]
-            na = anchors.shape[0]
-            labels = torch.full((na,), -1, dtype=torch.int32, device=anchors.device)
-            targets = anchors.new_zeros((na, code_size))
-            if len(g) == 0:
-                labels[:] = 0
-            else:
-                iou = _bev_iou(anchors[:, :7], g[:, :7])
-                arg = torch.from_numpy(iou.cpu().numpy().argmax(axis=1)).to(anchors.device)
-                amax = iou[torch.arange(na, device=anchors.device), arg]
-                gmax = torch.from_numpy(iou.cpu().numpy().max(axis=0)).to(anchors.device)
-                gmax[gmax == 0] = -1
-                forced = (iou == gmax[None, :]).any(dim=1)
-                pos = amax >= cgen["matched_threshold"]
-                labels[forced | pos] = gid[arg][forced | pos]
-                fg = labels > 0                     # the anchors whose targets are encoded: taken before the background pass
-                labels[amax < cgen["unmatched_threshold"]] = 0
-                labels[forced] = gid[arg][forced]
-                src = enl[mask] if enl is not None else g
-                targets[fg] = _encode(src[arg[fg]], anchors[fg], sincos)
-            weights = anchors.new_zeros((na,))
-            if norm:
-                cnt = int((labels >= 0).sum())
-                weights[labels > 0] = 1.0 / torch.tensor(max(cnt, 1))
-            else:
-                weights[labels > 0] = 1.0
-            per_class.append((labels, targets, weights, fmap))
-        if multihead:
-            out_l.append(torch.cat([p[0] for p in per_class]))
-            out_t.append(torch.cat([p[1] for p in per_class]))
-            out_w.append(torch.cat([p[2] for p in per_class]))
-        else:
-            fmap = per_class[0][3]
-            out_l.append(torch.cat([p[0].view(*fmap, -1) for p in per_class], dim=-1).view(-1))
-            out_t.append(torch.cat([p[1].view(*fmap, -1, code_size) for p in per_class], dim=-2).view(-1, code_size))
-            out_w.append(torch.cat([p[2].view(*fmap, -1) for p in per_class], dim=-1).view(-1))
-    return {"box_cls_labels": torch.stack(out_l), "box_reg_targets": torch.stack(out_t), "reg_weights": torch.stack(out_w)}
-
-
-def assert_targets_match(got, exp, sincos):
-    got = {k: v.cpu() for k, v in got.items()}
-    exp = {k: v.cpu() for k, v in exp.items()}
-    for k in exp:
-        assert got[k].shape == exp[k].shape and got[k].dtype == exp[k].dtype, (k, got[k].shape, exp[k].shape)
-    assert torch.equal(got["box_cls_labels"], exp["box_cls_labels"]), \
-        f"{int((got['box_cls_labels'] != exp['box_cls_labels']).sum())} labels differ"
-    assert torch.equal(got["reg_weights"], exp["reg_weights"])
-    code = exp["box_reg_targets"].shape[-1]
-    approx = [3, 4, 5] + ([6, 7] if sincos else [])
-    exact = [q for q in range(code) if q not in approx]
-    gt_, et = got["box_reg_targets"], exp["box_reg_targets"]
-    assert torch.equal(gt_[..., exact], et[..., exact]), f"exact target columns differ: {(gt_[..., exact] - et[..., exact]).abs().max()}"
-    assert (gt_[..., approx] - et[..., approx]).abs().max() <= 1e-6
-
-
-def restatement_on_fixture(name, device):
-    meta, anchors, gt, enl, exp = load_case(name)
-    got = restated_assign(model_cfg(meta), meta["class_names"], meta["code_size"] + int(meta["encode_angle_by_sincos"]),
-                          meta["encode_angle_by_sincos"], [a.to(device) for a in anchors], gt.to(device),
-                          enl.to(device) if enl is not None else None)
-    assert_targets_match(got, exp, meta["encode_angle_by_sincos"])
 
 
 # ------------------------------------------------------------------------------------------------ tests
@@ -197,26 +43,6 @@ def test_anchor_generator_matches_fixture_anchors(name, dev):
     assert per_loc == [2] * meta["num_anchors"]
     for g, a in zip(got, anchors):                  # the fixture's anchors carry the head's zero columns past 7
         assert torch.equal(g.cpu(), a[..., :7]) and not a[..., 7:].any()
-
-
-def kitti_production(dev, batch=16, seed=5, max_gt=60):
-    meta = load_case("kitti")[0]
-    gen = AnchorGenerator(meta["pc_range"], meta["anchor_generator_config"])
-    anchors, _ = gen.generate_anchors([[216, 248]] * 3, device=dev)            # PointPillar-KITTI: 216 x 248 x 6 anchors
-    r = np.random.default_rng(seed)
-    sizes = [c["anchor_sizes"][0] for c in meta["anchor_generator_config"]]
-    gt = np.zeros((batch, max_gt, 8), np.float32)
-    flat = torch.cat([a.reshape(-1, 7) for a in anchors]).cpu().numpy()
-    for b in range(batch):
-        n = int(r.integers(0, max_gt + 1))
-        for j in range(n):
-            c = int(r.integers(1, 4))
-            if j % 7 == 3:      # exactly on an anchor: ties at the gt max
-                gt[b, j] = [*flat[int(r.integers(0, len(flat)))], c]
-            else:
-                gt[b, j] = [r.uniform(0, 69), r.uniform(-39, 39), r.uniform(-2, 0), *(np.array(sizes[c - 1]) * r.uniform(0.7, 1.3, 3)),
-                            r.uniform(-np.pi, np.pi), c]
-    return meta, anchors, torch.from_numpy(gt).to(dev)
 
 
 def test_production_size_kitti(dev):
@@ -253,11 +79,8 @@ def test_no_host_sync_and_deterministic(dev):
     meta, anchors, gt = kitti_production(dev, batch=4, seed=8)
     a = AxisAlignedTargetAssigner(model_cfg(meta), meta["class_names"], Coder())
     torch.cuda.synchronize()
-    torch.cuda.set_sync_debug_mode("error")
-    try:
+    with no_host_sync():
         r1 = a.assign_targets(anchors, gt)
         r2 = a.assign_targets(anchors, gt)
-    finally:
-        torch.cuda.set_sync_debug_mode(0)
     for k in r1:
         assert torch.equal(r1[k], r2[k]), k

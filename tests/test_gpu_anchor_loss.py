@@ -1,12 +1,9 @@
 """The fused anchor-head loss on the GPU (lidardetection_amd/anchor_loss.py, csrc/anchor_loss.hip) against the reference's own
 get_loss (tests/golden/anchor_loss_ref.npz, written by tests/golden/make_loss_golden.py: fp32 and fp64 losses, fp64 autograd
-gradients) and, at production size, against `restated_loss` (tests/test_anchor_loss_host.py), a torch restatement that must first
-reproduce the fixture on the CPU.
+gradients) and, at production size, against `restated_loss` (tests/_anchor_loss_torch.py), a torch restatement that must first
+reproduce the fixture on the CPU (tests/test_anchor_loss_host.py).
 
 Tolerances: losses 1e-5 relative; gradients 1e-5 x max |gradient| of their tensor, and exactly 0 where the reference's is."""
-import importlib.util
-import os
-
 import numpy as np
 import pytest
 import torch
@@ -14,20 +11,11 @@ import torch
 from lidardetection_amd import anchor_loss
 from lidardetection_amd.pcdet.utils.cfg import AttrDict
 
+import _anchor_loss_torch as H
+from _anchor_loss_torch import DEV, nus_case, pp_case
+from _gpu_util import no_host_sync
+
 pytestmark = pytest.mark.gpu
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-def _host_module():
-    spec = importlib.util.spec_from_file_location("_anchor_loss_host_tests", os.path.join(HERE, "test_anchor_loss_host.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-H = _host_module()
-DEV = torch.device("cuda:0")
 
 
 def _fixture_inputs(name):
@@ -139,41 +127,6 @@ def test_mirror_recomputes_for_new_or_modified_tensors():
 
 
 # ------------------------------------------------------------------------------------------------ production size
-def _pp_case(B=16, seed=0):
-    from lidardetection_amd.pointpillar import PointPillarKITTI
-    torch.manual_seed(seed)
-    m = PointPillarKITTI.__new__(PointPillarKITTI)   # only what rpn_loss reads: no backbone, no voxeliser
-    torch.nn.Module.__init__(m)
-    m.nx, m.ny, m.num_class, m.pc_range = 432, 496, 3, [0.0, -39.68, -3.0, 69.12, 39.68, 1.0]
-    m.anchors = torch.zeros(1, 7, device=DEV)
-    head = m._loss_head()
-    gt = _random_gts(head.loss_anchors(), B, 60, seed)
-    t = head.assign_targets(gt)
-    N = t['box_cls_labels'].shape[1]
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    cls = (torch.randn(B, 248, 216, 18, generator=g) * 2 - 2).to(DEV)
-    box = (torch.randn(B, 248, 216, 42, generator=g) * 0.5).to(DEV)
-    dirs = torch.randn(B, 248, 216, 12, generator=g).to(DEV)
-    assert N == 321408
-    return m, head, t, [cls], [box], [dirs], gt
-
-
-def _random_gts(anchors, B, M, seed):
-    """(B, M, 8) KITTI gts on random anchors (jittered, so they match), of the anchor's class ([y, x, class, rot] order); frame 0
-    has none, the others 0..M"""
-    r = np.random.default_rng(seed)
-    a = anchors.cpu().numpy()
-    gt = np.zeros((B, M, 8), np.float32)
-    for b in range(1, B):
-        n = int(r.integers(0, M + 1))
-        idx = r.integers(0, a.shape[0], n)
-        gt[b, :n, :7] = a[idx, :7]
-        gt[b, :n, :2] += r.uniform(-0.2, 0.2, (n, 2))
-        gt[b, :n, 6] = r.uniform(-np.pi, np.pi, n)
-        gt[b, :n, 7] = 1 + (idx % 6) // 2
-    return torch.from_numpy(gt).to(DEV)
-
-
 def _check_against_restated(spec, cls, box, dirs, labels, targets, anchors, cols):
     B = labels.shape[0]
     nh = len(cls)
@@ -197,47 +150,14 @@ def _check_against_restated(spec, cls, box, dirs, labels, targets, anchors, cols
 
 
 def test_production_pointpillar_kitti_bs16():
-    m, head, t, cls, box, dirs, _ = _pp_case()
+    m, head, t, cls, box, dirs, _ = pp_case()
     labels, targets = t['box_cls_labels'], t['box_reg_targets']
     assert (labels > 0).sum().item() > 100 and (labels[0] > 0).sum().item() == 0
     _check_against_restated(head.loss_spec, cls, box, dirs, labels, targets, head.loss_anchors(), [3])
 
 
-def _nus_case(B=4, seed=1):
-    from lidardetection_amd.second_multihead import NUS_CLASSES, NUS_HEADS, SECONDMultiHeadNuScenes
-    m = SECONDMultiHeadNuScenes.__new__(SECONDMultiHeadNuScenes)
-    torch.nn.Module.__init__(m)
-    m.grid, m.pc_range = [1024, 1024, 40], [-51.2, -51.2, -5.0, 51.2, 51.2, 3.0]
-    m.head_anchors = [torch.zeros(1, 7, device=DEV)]
-    head = m._loss_head()
-    anchors = head.loss_anchors()
-    r = np.random.default_rng(seed)
-    a = anchors.cpu().numpy()
-    per_class = [int(np.prod(x.shape[:-1])) for x in head.anchors]
-    starts = np.cumsum([0] + per_class)
-    gt = np.zeros((B, 60, 10), np.float32)
-    for b in range(B):
-        n = int(r.integers(20, 61))
-        cls_ids = r.integers(1, 11, n)
-        idx = np.array([r.integers(starts[c - 1], starts[c]) for c in cls_ids])
-        gt[b, :n, :7] = a[idx, :7]
-        gt[b, :n, :2] += r.uniform(-0.2, 0.2, (n, 2))
-        gt[b, :n, 6] = r.uniform(-np.pi, np.pi, n)
-        gt[b, :n, 7:9] = r.normal(0, 2, (n, 2))
-        gt[b, :n:4, 7:9] = np.nan                               # NuScenes velocities that are missing
-        gt[b, :n, 9] = cls_ids
-    gt = torch.from_numpy(gt).to(DEV)
-    t = head.assign_targets(gt)
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    names = [c[0] for c in NUS_CLASSES]
-    n_h = [sum(per_class[names.index(name)] for name in h) for h in NUS_HEADS]
-    cls = [(torch.randn(B, n, len(h), generator=g) * 2 - 2).to(DEV) for n, h in zip(n_h, NUS_HEADS)]
-    box = [(torch.randn(B, n, 10, generator=g) * 0.5).to(DEV) for n in n_h]
-    return m, head, t, cls, box, gt
-
-
 def test_production_second_multihead_nuscenes_bs4():
-    m, head, t, cls, box, _ = _nus_case()
+    m, head, t, cls, box, _ = nus_case()
     labels, targets = t['box_cls_labels'], t['box_reg_targets']
     assert torch.isnan(targets).any() and (labels > 0).sum().item() > 100
     _check_against_restated(head.loss_spec, cls, box, [], labels, targets, head.loss_anchors(), [c.shape[-1] for c in cls])
@@ -250,10 +170,10 @@ def test_rpn_loss_hooks_train_the_stock_heads():
     torch.manual_seed(0)
     B = 2
     pp = PointPillarKITTI(batch_size=B, device=DEV, fold_bn=False).train()
-    _, _, _, _, _, _, gt = _pp_case(B=B, seed=5)
+    _, _, _, _, _, _, gt = pp_case(B=B, seed=5)
     canvas = torch.randn(B, 64, pp.ny, pp.nx, device=DEV).contiguous(memory_format=torch.channels_last)
     sec = SECONDMultiHeadNuScenes(batch_size=B, device=DEV).train()
-    _, _, _, _, _, ngt = _nus_case(B=B, seed=6)
+    _, _, _, _, _, ngt = nus_case(B=B, seed=6)
     spatial = torch.randn(B, 512, 128, 128, device=DEV).contiguous(memory_format=torch.channels_last)
     for model, run, gts in [(pp, lambda: pp.backbone_head_stock(canvas), gt),
                             (sec, lambda: sec.heads_reference_layout(spatial), ngt)]:
@@ -283,20 +203,17 @@ def test_rpn_loss_hooks_train_the_stock_heads():
 
 
 def test_sync_free_and_bitwise_deterministic():
-    m, head, _, cls, box, dirs, gt = _pp_case(B=16, seed=2)
+    m, head, _, cls, box, dirs, gt = pp_case(B=16, seed=2)
     spec, anchors = head.loss_spec, head.loss_anchors()
     runs = []
     torch.cuda.synchronize()
     for _ in range(2):
         leaves = [x.clone().requires_grad_() for x in cls + box + dirs]
-        torch.cuda.set_sync_debug_mode("error")
-        try:
+        with no_host_sync():
             t = head.assign_targets(gt)
             losses = anchor_loss.anchor_head_loss(leaves[0], leaves[1], leaves[2], t['box_cls_labels'], t['box_reg_targets'],
                                                   anchors, spec)
             sum(losses).backward()
-        finally:
-            torch.cuda.set_sync_debug_mode(0)
         runs.append([x.detach().clone() for x in losses] + [x.grad.clone() for x in leaves])
     for a, b in zip(*runs):
         assert torch.equal(a.reshape(-1).view(torch.int32), b.reshape(-1).view(torch.int32))

@@ -17,6 +17,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from _gpu_util import release_memory  # noqa: F401  (release_memory: an autouse fixture)
 from lidardetection_amd import _lib, wino
 from lidardetection_amd import bev_backbone as bb
 from test_bev_kernel_args_host import DECONV_LIMIT, F43_IN_LIMIT, F43_OUT_LIMIT
@@ -26,15 +27,6 @@ DEV = torch.device("cuda:0")
 SENTINEL = 777.0
 BAR = 1e-4
 CL = torch.channels_last
-
-
-@pytest.fixture(autouse=True, scope="module")
-def _release_memory():
-    yield
-    import gc
-    gc.collect()
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
 
 
 def _cus():

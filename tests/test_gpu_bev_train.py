@@ -11,6 +11,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from _gpu_util import no_host_sync, pp_inputs, rel, release_memory  # noqa: F401  (release_memory: an autouse fixture)
 from lidardetection_amd import bev_train, wino
 from lidardetection_amd.pcdet.models.backbones_2d.base_bev_backbone import BaseBEVBackbone
 from lidardetection_amd.pointpillar import make_bev_backbone
@@ -26,20 +27,6 @@ class _Cfg(dict):
 
 
 FIXTURE_CFG = _Cfg(LAYER_NUMS=[1, 1], LAYER_STRIDES=[2, 2], NUM_FILTERS=[64, 32], UPSAMPLE_STRIDES=[1, 2], NUM_UPSAMPLE_FILTERS=[64, 64])
-
-
-@pytest.fixture(autouse=True, scope="module")
-def _release_memory():
-    yield
-    import gc
-    gc.collect()
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
-
-
-def _rel(a, b):
-    a, b = a.detach().double(), b.detach().double()
-    return float((a - b).abs().max() / max(float(b.abs().max()), 1e-30))
 
 
 # The noise floor of the comparisons with the stock modules: the stock step rerun on inputs perturbed by NOISE (relative).  The
@@ -88,7 +75,7 @@ def test_bn_relu_kernels_match_float64(shapes):
     y = bev_train.bn_relu_train(zs, bns)
     assert y.is_contiguous(memory_format=CL) and y.shape[1] == sum(s[1] for s in shapes)
     ref, st = _ref_bn_relu([z.detach() for z in zs], bns)
-    assert _rel(y, ref) < 1e-5
+    assert rel(y, ref) < 1e-5
     G = _randn(y.shape, 7).contiguous(memory_format=CL)
     (y * G).sum().backward()
     z64 = [z.detach().double().requires_grad_() for z in zs]
@@ -97,9 +84,9 @@ def test_bn_relu_kernels_match_float64(shapes):
     ref = torch.cat([torch.relu(F.batch_norm(z, None, None, g, b, True, 0.0, bn.eps)) for z, g, b, bn in zip(z64, g64, b64, bns)], 1)
     (ref * G.double()).sum().backward()
     for z, r in zip(zs, z64):
-        assert _rel(z.grad, r.grad) < 1e-5
+        assert rel(z.grad, r.grad) < 1e-5
     for bn, g, b in zip(bns, g64, b64):
-        assert _rel(bn.weight.grad, g.grad) < 1e-5 and _rel(bn.bias.grad, b.grad) < 1e-5
+        assert rel(bn.weight.grad, g.grad) < 1e-5 and rel(bn.bias.grad, b.grad) < 1e-5
     for z, bn, sb, (mu, var) in zip(zs, bns, stock, st):
         sb(z.detach())                                               # torch's own running update on the same input
         torch.testing.assert_close(bn.running_mean, sb.running_mean, rtol=1e-6, atol=1e-7)
@@ -108,9 +95,9 @@ def test_bn_relu_kernels_match_float64(shapes):
         n = z.numel() // z.shape[1]
         _, _, _, bstats = bev_train.bn_relu_forward([z.detach()], bn.weight.detach(), bn.bias.detach(), bn.eps)
         c = z.shape[1]
-        assert _rel(bstats[:c], mu) < 1e-6 or float((bstats[:c].double() - mu).abs().max()) < 1e-7
-        assert _rel(bstats[c:2 * c], var) < 1e-6
-        assert _rel(bstats[2 * c:], var * n / (n - 1)) < 1e-6
+        assert rel(bstats[:c], mu) < 1e-6 or float((bstats[:c].double() - mu).abs().max()) < 1e-7
+        assert rel(bstats[c:2 * c], var) < 1e-6
+        assert rel(bstats[2 * c:], var * n / (n - 1)) < 1e-6
 
 
 def test_bn_relu_channel_slices_in_and_out():
@@ -120,7 +107,7 @@ def test_bn_relu_channel_slices_in_and_out():
     out = torch.full((2, 256, 9, 13), 7.0, device=DEV).contiguous(memory_format=CL)
     y, stats, ss, _ = bev_train.bn_relu_forward([z], bn.weight.detach(), bn.bias.detach(), bn.eps, out=out, out_offset=64)
     ref, _ = _ref_bn_relu([z], [bn])
-    assert y is out and _rel(out[:, 64:192], ref) < 1e-5
+    assert y is out and rel(out[:, 64:192], ref) < 1e-5
     assert bool((out[:, :64] == 7.0).all()) and bool((out[:, 192:] == 7.0).all())          # nothing outside the slice is touched
     gpar = _randn((2, 300, 9, 13), 4).contiguous(memory_format=CL)
     g = gpar[:, 100:228]                                             # the gradient read from a slice of a wider map too
@@ -128,8 +115,8 @@ def test_bn_relu_channel_slices_in_and_out():
     z64 = z.double().requires_grad_()
     w64, b64 = bn.weight.detach().double().requires_grad_(), bn.bias.detach().double().requires_grad_()
     (torch.relu(F.batch_norm(z64, None, None, w64, b64, True, 0.0, bn.eps)) * g.double()).sum().backward()
-    assert dz.shape == z.shape and _rel(dz, z64.grad) < 1e-5
-    assert _rel(dg, w64.grad) < 1e-5 and _rel(db, b64.grad) < 1e-5
+    assert dz.shape == z.shape and rel(dz, z64.grad) < 1e-5
+    assert rel(dg, w64.grad) < 1e-5 and rel(db, b64.grad) < 1e-5
 
 
 @pytest.mark.parametrize("cin,cout,hw,force_f23", [(64, 64, (30, 26), False), (128, 128, (17, 23), False), (64, 128, (20, 20), False),
@@ -145,9 +132,9 @@ def test_wino_conv_layer_forward_and_input_grad(monkeypatch, cin, cout, hw, forc
     x64, w64 = x.detach().double().requires_grad_(), w.detach().double().requires_grad_()
     z64 = F.conv2d(x64, w64, None, 1, 1)
     (z64 * G.double()).sum().backward()
-    assert _rel(z, z64) < 1e-4
-    assert _rel(x.grad, x64.grad) < 1e-4
-    assert _rel(w.grad, w64.grad) < 1e-4
+    assert rel(z, z64) < 1e-4
+    assert rel(x.grad, x64.grad) < 1e-4
+    assert rel(w.grad, w64.grad) < 1e-4
 
 
 def _fixture_model(z):
@@ -167,20 +154,20 @@ def test_backbone_matches_reference_fixture(golden_dir):
     x = (torch.from_numpy(z["x_code"]).float() * float(z["x_scale"])).to(DEV).contiguous(memory_format=CL).requires_grad_()
     G = (torch.from_numpy(z["g_code"]).float() * float(z["g_scale"])).to(DEV).contiguous(memory_format=CL)
     y = m({"spatial_features": x})["spatial_features_2d"]            # the mirror routes train-mode channels-last maps to TrainBEVBackbone
-    assert _rel(y, torch.from_numpy(z["out64"]).to(DEV)) < 1e-5
+    assert rel(y, torch.from_numpy(z["out64"]).to(DEV)) < 1e-5
     (y * G).sum().backward()
-    assert _rel(x.grad, torch.from_numpy(z["dx64"]).to(DEV)) < 1e-4
+    assert rel(x.grad, torch.from_numpy(z["dx64"]).to(DEV)) < 1e-4
     for name, mod in m.named_modules():
         if isinstance(mod, nn.BatchNorm2d):
-            assert _rel(mod.weight.grad, torch.from_numpy(z["d_gamma." + name]).to(DEV)) < 1e-4, name
-            assert _rel(mod.bias.grad, torch.from_numpy(z["d_beta." + name]).to(DEV)) < 1e-4, name
+            assert rel(mod.weight.grad, torch.from_numpy(z["d_gamma." + name]).to(DEV)) < 1e-4, name
+            assert rel(mod.bias.grad, torch.from_numpy(z["d_beta." + name]).to(DEV)) < 1e-4, name
             torch.testing.assert_close(mod.running_mean, torch.from_numpy(z["rm1." + name]).to(DEV), rtol=1e-5, atol=1e-6)
             torch.testing.assert_close(mod.running_var, torch.from_numpy(z["rv1." + name]).to(DEV), rtol=1e-5, atol=1e-6)
             assert int(mod.num_batches_tracked) == 1
         elif isinstance(mod, (nn.Conv2d, nn.ConvTranspose2d)):
             key = name + ".weight"
             ref = torch.from_numpy(z["dw16." + key].astype(np.float32)).to(DEV) * float(z["dw_scale." + key])
-            assert _rel(mod.weight.grad, ref) < 2e-3, name                 # float16 storage
+            assert rel(mod.weight.grad, ref) < 2e-3, name                 # float16 storage
 
 
 def _three(make, seed):
@@ -222,16 +209,16 @@ def test_widths_match_stock_train_modules(which):
     ys = _stock_forward(stock, xs[1])
     noise = 1 + NOISE * _randn(shape, 42)
     yn = _stock_forward(noisy, (xs[2] * noise).contiguous(memory_format=CL))
-    assert _rel(yf, ys) < 1e-4
+    assert rel(yf, ys) < 1e-4
     G = _randn(yf.shape, 43).contiguous(memory_format=CL)
     for y in (yf, ys, yn):
         (y * G).sum().backward()
-    floor = _rel(xs[2].grad, xs[1].grad)
-    assert _rel(xs[0].grad, xs[1].grad) < max(1e-4, 10 * floor)
+    floor = rel(xs[2].grad, xs[1].grad)
+    assert rel(xs[0].grad, xs[1].grad) < max(1e-4, 10 * floor)
     pf, ps, pn = dict(fused.named_parameters()), dict(stock.named_parameters()), dict(noisy.named_parameters())
     bad = {}
     for k in ps:
-        err, fl = _rel(pf[k].grad, ps[k].grad), _rel(pn[k].grad, ps[k].grad)
+        err, fl = rel(pf[k].grad, ps[k].grad), rel(pn[k].grad, ps[k].grad)
         if not err < max(1e-4, 10 * fl):
             bad[k] = (err, fl)
     assert not bad, bad
@@ -242,30 +229,10 @@ def test_widths_match_stock_train_modules(which):
             assert int(bf) == int(bs) == 1
 
 
-def _pp_inputs(B, seed):
-    from lidardetection_amd import synth
-    frames = [synth.cloud_ring(2300 + seed + i) for i in range(B)]
-    pts = torch.from_numpy(np.concatenate(frames)).to(DEV)
-    offs = torch.tensor(np.cumsum([0] + [len(f) for f in frames]), dtype=torch.int32, device=DEV)
-    r = np.random.default_rng(seed)
-    gt = np.zeros((B, 12, 8), np.float32)
-    for b in range(B):
-        n = 8
-        gt[b, :n, 0] = r.uniform(5, 60, n)
-        gt[b, :n, 1] = r.uniform(-30, 30, n)
-        gt[b, :n, 2] = r.uniform(-1.5, -0.5, n)
-        cls = r.integers(1, 4, n)
-        size = np.array([[3.9, 1.6, 1.56], [0.8, 0.6, 1.73], [1.76, 0.6, 1.73]], np.float32)[cls - 1]
-        gt[b, :n, 3:6] = size * r.uniform(0.9, 1.1, (n, 1))
-        gt[b, :n, 6] = r.uniform(-np.pi, np.pi, n)
-        gt[b, :n, 7] = cls
-    return pts, offs, torch.from_numpy(gt).to(DEV)
-
-
 def test_train_loss_fused_matches_stock_and_refolds():
     from lidardetection_amd import pillar_ops
     from lidardetection_amd.pointpillar import PointPillarKITTI
-    pts, offs, gt = _pp_inputs(2, 5)
+    pts, offs, gt = pp_inputs(2, 5, 2300)
     models = []
     for _ in range(3):
         torch.manual_seed(6)
@@ -287,9 +254,9 @@ def test_train_loss_fused_matches_stock_and_refolds():
     for ll in (lf, ls, ln):
         sum(ll).backward()
     pf, ps, pn = dict(fused.named_parameters()), dict(stock.named_parameters()), dict(noisy.named_parameters())
-    errs = {k: _rel(p.grad, ps[k].grad) for k, p in pf.items() if p.grad is not None}
+    errs = {k: rel(p.grad, ps[k].grad) for k, p in pf.items() if p.grad is not None}
     assert len(errs) == len(ps)
-    bad = {k: (v, _rel(pn[k].grad, ps[k].grad)) for k, v in errs.items() if not v < max(1e-4, 10 * _rel(pn[k].grad, ps[k].grad))}
+    bad = {k: (v, rel(pn[k].grad, ps[k].grad)) for k, v in errs.items() if not v < max(1e-4, 10 * rel(pn[k].grad, ps[k].grad))}
     assert not bad, bad
     for (k, bf), bs in zip(fused.named_buffers(), stock.buffers()):
         if "running" in k:
@@ -324,17 +291,13 @@ def test_sync_free_and_bitwise_deterministic():
         bns = [copy.deepcopy(b) for b in bn_base]
         x, xc = x0.clone().requires_grad_(), x0.clone().requires_grad_()
         tb = bev_train.TrainBEVBackbone(mods[0], mods[1])
-        if rep > 0:
-            torch.cuda.set_sync_debug_mode("error")
-        try:
+        with no_host_sync(rep > 0):
             y = tb(x)
             (y * G).sum().backward()
             z1 = bev_train.conv3x3_train(xc, w1)
             a = bev_train.bn_relu_train(z1, bns[0])
             yc = bev_train.bn_relu_train([bev_train.conv3x3_train(a, w2), z1], bns[1:])
             (yc * Gc).sum().backward()
-        finally:
-            torch.cuda.set_sync_debug_mode(0)
         outs.append([yc.detach(), xc.grad] + [t for b in bns for t in (b.running_mean, b.running_var, b.weight.grad, b.bias.grad)])
         assert y.shape == G.shape and x.grad is not None
     for a, b in zip(outs[1], outs[2]):

@@ -13,6 +13,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from _gpu_util import no_host_sync, pp_inputs, rel, release
 from lidardetection_amd import _lib, bev_train, workspace
 from lidardetection_amd.pcdet.models.backbones_2d.base_bev_backbone import BaseBEVBackbone
 from lidardetection_amd.pointpillar import make_bev_backbone
@@ -37,16 +38,7 @@ FIXTURE_CFG = _Cfg(LAYER_NUMS=[0, 0, 0], LAYER_STRIDES=[1, 2, 2], NUM_FILTERS=[1
 @pytest.fixture(autouse=True, scope="module")
 def _release_memory():
     yield
-    import gc
-    gc.collect()
-    torch.cuda.synchronize()
-    workspace.drop("deconv_wgrad")
-    torch.cuda.empty_cache()
-
-
-def _rel(a, b):
-    a, b = a.detach().double(), b.detach().double()
-    return float((a - b).abs().max() / max(float(b.abs().max()), 1e-30))
+    release("deconv_wgrad")
 
 
 def _within_bar(got, want):
@@ -280,19 +272,19 @@ def test_backbone_matches_reference_fixture(golden_dir, monkeypatch):
     x = x0.clone().requires_grad_()
     y = tb(x)
     assert calls.take() == {"deconv_forward_gemm": 2, "deconv_dgrad": 0, "deconv_wgrad": 0}
-    assert _rel(y, torch.from_numpy(z["out64"]).to(DEV)) < 1e-5
+    assert rel(y, torch.from_numpy(z["out64"]).to(DEV)) < 1e-5
     (y * G).sum().backward()
     assert calls.take() == {"deconv_forward_gemm": 0, "deconv_dgrad": 3, "deconv_wgrad": 3}      # six gradient kernel calls per step
-    assert _rel(x.grad, torch.from_numpy(z["dx64"]).to(DEV)) < 1e-4
+    assert rel(x.grad, torch.from_numpy(z["dx64"]).to(DEV)) < 1e-4
     n_up = 0
     for name, mod in m.named_modules():
         if isinstance(mod, nn.BatchNorm2d):
-            assert _rel(mod.weight.grad, torch.from_numpy(z["d_gamma." + name]).to(DEV)) < 1e-4, name
-            assert _rel(mod.bias.grad, torch.from_numpy(z["d_beta." + name]).to(DEV)) < 1e-4, name
+            assert rel(mod.weight.grad, torch.from_numpy(z["d_gamma." + name]).to(DEV)) < 1e-4, name
+            assert rel(mod.bias.grad, torch.from_numpy(z["d_beta." + name]).to(DEV)) < 1e-4, name
         elif isinstance(mod, (nn.Conv2d, nn.ConvTranspose2d)):
             key = name + ".weight"
             ref = torch.from_numpy(z["dw16." + key].astype(np.float32)).to(DEV) * float(z["dw_scale." + key])
-            assert _rel(mod.weight.grad, ref) < 2e-3, name               # float16 storage
+            assert rel(mod.weight.grad, ref) < 2e-3, name               # float16 storage
             n_up += isinstance(mod, nn.ConvTranspose2d)
     assert n_up == 3
     # the default option runs none of the kernels
@@ -301,32 +293,12 @@ def test_backbone_matches_reference_fixture(golden_dir, monkeypatch):
     assert calls.take() == {"deconv_forward_gemm": 0, "deconv_dgrad": 0, "deconv_wgrad": 0}
 
 
-def _pp_inputs(B, seed):
-    from lidardetection_amd import synth
-    frames = [synth.cloud_ring(2300 + seed + i) for i in range(B)]
-    pts = torch.from_numpy(np.concatenate(frames)).to(DEV)
-    offs = torch.tensor(np.cumsum([0] + [len(f) for f in frames]), dtype=torch.int32, device=DEV)
-    r = np.random.default_rng(seed)
-    gt = np.zeros((B, 12, 8), np.float32)
-    for b in range(B):
-        n = 8
-        gt[b, :n, 0] = r.uniform(5, 60, n)
-        gt[b, :n, 1] = r.uniform(-30, 30, n)
-        gt[b, :n, 2] = r.uniform(-1.5, -0.5, n)
-        cls = r.integers(1, 4, n)
-        size = np.array([[3.9, 1.6, 1.56], [0.8, 0.6, 1.73], [1.76, 0.6, 1.73]], np.float32)[cls - 1]
-        gt[b, :n, 3:6] = size * r.uniform(0.9, 1.1, (n, 1))
-        gt[b, :n, 6] = r.uniform(-np.pi, np.pi, n)
-        gt[b, :n, 7] = cls
-    return pts, offs, torch.from_numpy(gt).to(DEV)
-
-
 def test_train_loss_gemm_matches_library_option(monkeypatch):
     """the criterion of test_train_loss_fused_matches_stock_and_refolds: every gradient within 10 x the step's own spread under
     2^-17 input noise (the "library" step rerun on a perturbed canvas)"""
     from lidardetection_amd import pillar_ops
     from lidardetection_amd.pointpillar import PointPillarKITTI
-    pts, offs, gt = _pp_inputs(2, 5)
+    pts, offs, gt = pp_inputs(2, 5, 2300)
     models = []
     for _ in range(3):
         torch.manual_seed(6)
@@ -348,9 +320,9 @@ def test_train_loss_gemm_matches_library_option(monkeypatch):
         sum(losses).backward()
     assert calls.take() == {"deconv_forward_gemm": 0, "deconv_dgrad": 0, "deconv_wgrad": 0}
     pg, pl, pn = dict(new.named_parameters()), dict(lib.named_parameters()), dict(noisy.named_parameters())
-    errs = {k: _rel(p.grad, pl[k].grad) for k, p in pg.items() if p.grad is not None and bool(torch.isfinite(p.grad).all())}
+    errs = {k: rel(p.grad, pl[k].grad) for k, p in pg.items() if p.grad is not None and bool(torch.isfinite(p.grad).all())}
     assert len(errs) == len(pl)                                         # every parameter received a finite gradient
-    bad = {k: (v, _rel(pn[k].grad, pl[k].grad)) for k, v in errs.items() if not v < max(1e-4, 10 * _rel(pn[k].grad, pl[k].grad))}
+    bad = {k: (v, rel(pn[k].grad, pl[k].grad)) for k, v in errs.items() if not v < max(1e-4, 10 * rel(pn[k].grad, pl[k].grad))}
     assert not bad, bad
     tb = new.__dict__["_bev_train_wino_gemm"]                            # the cached backbone is keyed by both options
     assert tb.deblock_conv_routes() == [("library", "gemm", "gemm"), ("gemm", "gemm", "gemm"), ("gemm", "gemm", "gemm")]
@@ -367,12 +339,8 @@ def test_sync_free():
         mods = copy.deepcopy(base)
         x = x0.clone().requires_grad_()
         tb = bev_train.TrainBEVBackbone(mods[0], mods[1], wgrad="wino", deblock="gemm")
-        if rep > 0:
-            torch.cuda.set_sync_debug_mode("error")
-        try:
+        with no_host_sync(rep > 0):
             (tb(x) * G).sum().backward()
-        finally:
-            torch.cuda.set_sync_debug_mode(0)
         assert x.grad is not None
     for p in mods.parameters():
         assert p.grad is not None and bool(torch.isfinite(p.grad).all())

@@ -16,6 +16,7 @@ import pytest
 import torch
 from torch.nn.utils import clip_grad_norm_
 
+from _gpu_util import no_host_sync
 import _optim_model as om
 from lidardetection_amd import optim, synth
 
@@ -286,8 +287,7 @@ def test_no_host_synchronisation(gold):
         p.grad = a
     opt.step()                                              # warm-up: code objects, the first table upload
     torch.cuda.synchronize()
-    torch.cuda.set_sync_debug_mode("error")
-    try:
+    with no_host_sync():
         opt.step()
         opt.zero_grad()
         opt.step(zero_grad=True)
@@ -298,8 +298,6 @@ def test_no_host_synchronisation(gold):
         norm = opt.step()
         assert opt._sig != sig
         opt.zero_grad(set_to_none=True)
-    finally:
-        torch.cuda.set_sync_debug_mode(0)
     assert torch.isfinite(norm).item() and all(p.grad is None for p in params)
 
 
@@ -353,11 +351,8 @@ def _three_train_steps(fused, stock, pts, offs, gt):
     for it in range(3):
         lr, mom = optim.one_cycle(it, 10)
         opt.lr, opt.mom = lr, mom
-        torch.cuda.set_sync_debug_mode("error" if it == 2 else 0)    # once everything is warm: no host synchronisation
-        try:
+        with no_host_sync(it == 2):    # once everything is warm: no host synchronisation
             out = fused.train_step(pts, offs, gt, opt)
-        finally:
-            torch.cuda.set_sync_debug_mode(0)
         assert len(out) == 4 and all(t.is_cuda and not t.requires_grad for t in out)
         adam.zero_grad()
         losses = stock.train_loss(pts, offs, gt)

@@ -7,28 +7,16 @@ import os
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
 from lidardetection_amd import pillar_ops, synth
 from lidardetection_amd.pcdet.models.backbones_2d.map_to_bev.bev_maps import PointPillarScatter
-from lidardetection_amd.pcdet.models.backbones_3d.vfe.encoders import PillarVFE
 from lidardetection_amd.pcdet.utils.cfg import AttrDict
-from lidardetection_amd.voxelizer import BatchVoxelizer
+
+from _gpu_util import no_host_sync, rel, release_memory  # noqa: F401  (release_memory: an autouse fixture)
+from _pp_train_torch import DEV, bs16_voxels, pp_inputs, stock_loss, vfe
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
 CASES = ("kitti", "nus", "kitti_dist")
-
-
-@pytest.fixture(autouse=True, scope="module")
-def _release_memory():
-    """the float64 comparisons hold tens of GB: hand the cached blocks back, so that later test files start from the same
-    allocator state as without this one"""
-    yield
-    import gc
-    gc.collect()
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
 
 
 def _load(golden_dir, case):
@@ -39,10 +27,6 @@ def _load(golden_dir, case):
 def _t(a, dtype=None):
     t = torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
     return t if dtype is None else t.to(dtype)
-
-
-def _rel(a, b):
-    return float((a.double() - b.double()).abs().max() / max(float(b.double().abs().max()), 1e-30))
 
 
 def _canvas_grad(grad_pf, coords, B, C, nx, ny, channels_last, seed=0):
@@ -66,7 +50,7 @@ def test_kernels_match_reference_fixture(golden_dir, case):
     B = int(d["batch_size"])
     out, mean, var = pillar_ops.pillar_vfe_train(vox, num, coords, w, gamma, beta, rm, rv, d["voxel_size"], d["pc_range"],
                                                  with_distance=bool(d["with_distance"]), num_batches_tracked=nbt, return_stats=True)
-    assert _rel(out, _t(d["out64"])) < 1e-5
+    assert rel(out, _t(d["out64"])) < 1e-5
     torch.testing.assert_close(mean.double(), _t(d["mean64"]), rtol=1e-6, atol=1e-6 * float(np.abs(d["mean64"]).max()))
     torch.testing.assert_close(var.double(), _t(d["var64"]), rtol=1e-6, atol=0)
     torch.testing.assert_close(rm.double(), _t(d["rm1"]), rtol=1e-6, atol=1e-7)
@@ -78,7 +62,7 @@ def test_kernels_match_reference_fixture(golden_dir, case):
         G = _canvas_grad(_t(d["grad_pf"]), coords, B, out.shape[1], nx, ny, channels_last)
         (canvas * G).sum().backward(retain_graph=True)
         for name, p in (("d_weight", w), ("d_gamma", gamma), ("d_beta", beta)):
-            assert _rel(p.grad, _t(d[name + "64"])) < 1e-5, (name, channels_last)
+            assert rel(p.grad, _t(d[name + "64"])) < 1e-5, (name, channels_last)
     pillar_ops.pillar_vfe_train(vox, num, coords, w, gamma, beta, rm, rv, d["voxel_size"], d["pc_range"],
                                 with_distance=bool(d["with_distance"]), num_batches_tracked=nbt)
     torch.testing.assert_close(rm.double(), _t(d["rm2"]), rtol=1e-6, atol=1e-7)
@@ -86,41 +70,13 @@ def test_kernels_match_reference_fixture(golden_dir, case):
     assert int(nbt) == int(d["nbt2"]) == 2
 
 
-def _pp_cfg(**kw):
-    return AttrDict(dict(USE_NORM=True, WITH_DISTANCE=False, USE_ABSLOTE_XYZ=True, NUM_FILTERS=[64], **kw))
-
-
-def _bs16_voxels(B=16, seed=0):
-    frames = [synth.cloud_ring(2000 + seed + i) if i % 2 else synth.cloud_uniform(1000 + seed + i) for i in range(B)]
-    pts = torch.from_numpy(np.concatenate(frames)).to(DEV)
-    offs = torch.tensor(np.cumsum([0] + [len(f) for f in frames]), dtype=torch.int32, device=DEV)
-    vz = BatchVoxelizer(synth.PP_VOXEL, synth.PP_RANGE, 32, 16000)
-    vox = vz(pts, offs, max(len(f) for f in frames), compact=True)
-    nv = int(vox["voxel_offsets"][B])
-    for k, fill in (("voxels", float("nan")), ("voxel_coords", -7), ("voxel_num_points", -3)):
-        vox[k][nv:] = fill                           # rows past the device count: neither read nor counted
-    return vox, nv
-
-
-def _vfe(seed=0):
-    torch.manual_seed(seed)
-    m = PillarVFE(_pp_cfg(), 4, synth.PP_VOXEL, synth.PP_RANGE).to(DEV)
-    with torch.no_grad():
-        bn = m.pfn_layers[0].norm
-        bn.weight.uniform_(0.3, 1.5)
-        bn.weight[::5] *= -1
-        bn.bias.normal_(0, 0.3)
-        bn.running_var.uniform_(0.8, 1.2)
-    return m.train()
-
-
 def test_production_size_against_the_torch_path_in_float64():
-    vox, nv = _bs16_voxels()
+    vox, nv = bs16_voxels()
     assert nv > 100000
     total = vox["voxel_offsets"][16:17]
-    m = _vfe()
+    m = vfe()
     layer = m.pfn_layers[0]
-    ref = _vfe()
+    ref = vfe()
     ref.double()
     g = torch.randn(vox["voxels"].shape[0], 64, device=DEV)
     out = pillar_ops.pillar_vfe_train(vox["voxels"], vox["voxel_num_points"], vox["voxel_coords"], layer.linear.weight, layer.norm.weight,
@@ -132,7 +88,7 @@ def test_production_size_against_the_torch_path_in_float64():
               "voxel_coords": vox["voxel_coords"][:nv]})
     want = bd["pillar_features"]
     (want * g[:nv].double()).sum().backward()
-    assert _rel(out[:nv], want) < 1e-5
+    assert rel(out[:nv], want) < 1e-5
     rl = ref.pfn_layers[0]
     torch.testing.assert_close(layer.norm.running_mean.double(), rl.norm.running_mean, rtol=1e-6, atol=1e-6)
     torch.testing.assert_close(layer.norm.running_var.double(), rl.norm.running_var, rtol=1e-6, atol=0)
@@ -140,17 +96,17 @@ def test_production_size_against_the_torch_path_in_float64():
     # fp32 rows against fp64 ones: a near-tie between two points of a pillar (or a ReLU edge) may select differently at this
     # size, moving one pillar's contribution; 1e-4 of the largest gradient leaves room for a few of them
     for a, b in ((layer.linear.weight, rl.linear.weight), (layer.norm.weight, rl.norm.weight), (layer.norm.bias, rl.norm.bias)):
-        assert _rel(a.grad, b.grad) < 1e-4
+        assert rel(a.grad, b.grad) < 1e-4
 
 
 def test_mirror_dispatch(monkeypatch):
-    vox, nv = _bs16_voxels(B=2, seed=7)
+    vox, nv = bs16_voxels(B=2, seed=7)
     bd = lambda v: {"voxels": v, "voxel_num_points": vox["voxel_num_points"][:nv], "voxel_coords": vox["voxel_coords"][:nv]}  # noqa: E731
     calls = []
     train_fn, eval_fn = pillar_ops.pillar_vfe_train, pillar_ops.pillar_vfe
     monkeypatch.setattr(pillar_ops, "pillar_vfe_train", lambda *a, **k: calls.append("train") or train_fn(*a, **k))
     monkeypatch.setattr(pillar_ops, "pillar_vfe", lambda *a, **k: calls.append("eval") or eval_fn(*a, **k))
-    m = _vfe()
+    m = vfe()
     v = vox["voxels"][:nv].contiguous()
     out = m(bd(v))["pillar_features"]
     assert calls == ["train"] and out.requires_grad
@@ -165,7 +121,7 @@ def test_mirror_dispatch(monkeypatch):
     from lidardetection_amd.pointpillar import PointPillarKITTI
     pp = PointPillarKITTI(batch_size=2, device=DEV)
     before = [t.clone() for t in pp._pfn_folded()]
-    pts, offs, gt = _pp_inputs(2, 3)
+    pts, offs, gt = pp_inputs(2, 3)
     pp.train()
     sum(pp.train_loss(pts, offs, gt)).backward()
     pp.eval()
@@ -178,7 +134,7 @@ def test_mirror_dispatch(monkeypatch):
 
 @pytest.mark.parametrize("channels_last", [False, True])
 def test_scatter_autograd_matches_index_assign(channels_last):
-    vox, nv = _bs16_voxels(B=2, seed=3)
+    vox, nv = bs16_voxels(B=2, seed=3)
     coords = vox["voxel_coords"]
     total = vox["voxel_offsets"][2:3]
     V = coords.shape[0]
@@ -205,86 +161,30 @@ def test_scatter_autograd_matches_index_assign(channels_last):
 
 
 def test_sync_free_and_bitwise_deterministic():
-    vox, nv = _bs16_voxels(seed=5)
+    vox, nv = bs16_voxels(seed=5)
     total = vox["voxel_offsets"][16:17]
     G = torch.randn(16, 64, 496, 432, device=DEV).contiguous(memory_format=torch.channels_last)
     runs = []
     torch.cuda.synchronize()
     for _ in range(2):
-        m = _vfe(seed=1)
+        m = vfe(seed=1)
         layer = m.pfn_layers[0]
-        torch.cuda.set_sync_debug_mode("error")
-        try:
+        with no_host_sync():
             out = pillar_ops.pillar_vfe_train(vox["voxels"], vox["voxel_num_points"], vox["voxel_coords"], layer.linear.weight,
                                               layer.norm.weight, layer.norm.bias, layer.norm.running_mean, layer.norm.running_var,
                                               synth.PP_VOXEL, synth.PP_RANGE, num_batches_tracked=layer.norm.num_batches_tracked,
                                               num_voxels_dev=total)
             canvas = pillar_ops.pillar_scatter_train(out, vox["voxel_coords"], 16, 432, 496, num_voxels_dev=total, channels_last=True)
             (canvas * G).sum().backward()
-        finally:
-            torch.cuda.set_sync_debug_mode(0)
         runs.append([out.detach().clone(), layer.norm.running_mean.clone(), layer.norm.running_var.clone(),
                      layer.linear.weight.grad.clone(), layer.norm.weight.grad.clone(), layer.norm.bias.grad.clone()])
     for a, b in zip(*runs):
         assert torch.equal(a.reshape(-1).view(torch.int32), b.reshape(-1).view(torch.int32))
 
 
-def _pp_inputs(B, seed):
-    from lidardetection_amd.pointpillar import PointPillarKITTI  # noqa: F401
-    frames = [synth.cloud_ring(2100 + seed + i) for i in range(B)]
-    pts = torch.from_numpy(np.concatenate(frames)).to(DEV)
-    offs = torch.tensor(np.cumsum([0] + [len(f) for f in frames]), dtype=torch.int32, device=DEV)
-    r = np.random.default_rng(seed)
-    gt = np.zeros((B, 12, 8), np.float32)
-    for b in range(B):
-        n = 8
-        gt[b, :n, 0] = r.uniform(5, 60, n)
-        gt[b, :n, 1] = r.uniform(-30, 30, n)
-        gt[b, :n, 2] = r.uniform(-1.5, -0.5, n)
-        cls = r.integers(1, 4, n)
-        size = np.array([[3.9, 1.6, 1.56], [0.8, 0.6, 1.73], [1.76, 0.6, 1.73]], np.float32)[cls - 1]
-        gt[b, :n, 3:6] = size * r.uniform(0.9, 1.1, (n, 1))
-        gt[b, :n, 6] = r.uniform(-np.pi, np.pi, n)
-        gt[b, :n, 7] = cls
-    return pts, offs, torch.from_numpy(gt).to(DEV)
-
-
-def _stock_loss(m, pts, offs, gt, dt=torch.float64, perturb=0.0):
-    """the same training step on the stock torch PFN (the mirror's formulation) and torch index-assign scatter.  The PFN runs in
-    float64 (dt): in float32 its weight gradient sum(dz x) over ~10^6 rows cancels (sum dz = 0 under BatchNorm, |x| ~ 70 m) to a relative
-    error of ~1e-3, which is the torch path's error, not the kernels' (they accumulate in fp64)."""
-    with torch.no_grad():
-        vox = m.voxelizer(pts, offs, m.n_max, compact=True)
-    nv = int(vox["voxel_offsets"][m.B])
-    v, num, coords = vox["voxels"][:nv].to(dt), vox["voxel_num_points"][:nv], vox["voxel_coords"][:nv]
-    xyz = v[:, :, :3]
-    mean = xyz.sum(dim=1, keepdim=True) / num.to(dt).view(-1, 1, 1)
-    vs = torch.tensor(m.voxel_size, device=DEV, dtype=dt)
-    centre = coords[:, [3, 2, 1]].to(dt) * vs + (vs / 2 + torch.tensor(m.pc_range[:3], device=DEV, dtype=dt))
-    x = torch.cat([v, xyz - mean, xyz - centre.unsqueeze(1)], dim=-1)
-    x = x * (torch.arange(v.shape[1], device=DEV).view(1, -1) < num.view(-1, 1)).unsqueeze(-1).to(dt)
-    n = m.pfn_norm
-    z = F.linear(x, m.pfn_linear.weight.to(dt))
-    rm, rv = n.running_mean.to(dt, copy=True), n.running_var.to(dt, copy=True)
-    y = F.batch_norm(z.transpose(1, 2), rm, rv, n.weight.to(dt), n.bias.to(dt), True, n.momentum, n.eps).transpose(1, 2)
-    with torch.no_grad():
-        n.running_mean.copy_(rm)
-        n.running_var.copy_(rv)
-        n.num_batches_tracked.add_(1)
-    feat = torch.relu(y).amax(dim=1).float()
-    if perturb:                                      # relative noise of the size of fp32 rounding (the test's noise floor)
-        g = torch.Generator(device="cpu").manual_seed(1)
-        feat = feat * (1 + perturb * torch.randn(feat.shape, generator=g)).to(DEV)
-    flat = feat.new_zeros((m.B, 64, m.ny * m.nx))
-    c = coords.long()
-    flat[c[:, 0], :, c[:, 2] * m.nx + c[:, 3]] = feat
-    canvas = flat.view(m.B, 64, m.ny, m.nx).contiguous(memory_format=torch.channels_last)
-    return m.rpn_loss(m.backbone_head_stock(canvas), gt)
-
-
 def test_train_loss_end_to_end_matches_stock_torch():
     from lidardetection_amd.pointpillar import PointPillarKITTI
-    pts, offs, gt = _pp_inputs(2, 11)
+    pts, offs, gt = pp_inputs(2, 11)
     models = []
     for _ in range(3):
         torch.manual_seed(4)
@@ -293,7 +193,7 @@ def test_train_loss_end_to_end_matches_stock_torch():
     with pytest.raises(pillar_ops._lib.LidarHipError):
         PointPillarKITTI(batch_size=2, device=DEV).train_loss(pts, offs, gt)      # eval mode: refused
     lf = fused.train_loss(pts, offs, gt)
-    ls = _stock_loss(stock, pts, offs, gt)
+    ls = stock_loss(stock, pts, offs, gt)
     for a, b in zip(lf, ls):
         torch.testing.assert_close(a, b, rtol=1e-4, atol=1e-6)
     sum(lf).backward()
@@ -301,10 +201,10 @@ def test_train_loss_end_to_end_matches_stock_torch():
     # The stock step once more with its pillar features perturbed by fp32-rounding-sized noise (2^-24 relative): how far apart two
     # float32 backbones with train-mode BatchNorm put the gradients when their inputs differ only in the last bits.  (Their
     # convolution weight gradients are BatchNorm-normalised sums over the whole map: they cancel, and differ at ~1e-3 relative.)
-    sum(_stock_loss(noisy, pts, offs, gt, perturb=2.0 ** -24)).backward()
+    sum(stock_loss(noisy, pts, offs, gt, perturb=2.0 ** -24)).backward()
     named, noise = dict(stock.named_parameters()), dict(noisy.named_parameters())
-    errs = {name: _rel(p.grad, named[name].grad) for name, p in fused.named_parameters() if p.grad is not None}
-    floor = {name: _rel(noise[name].grad, named[name].grad) for name in named}
+    errs = {name: rel(p.grad, named[name].grad) for name, p in fused.named_parameters() if p.grad is not None}
+    floor = {name: rel(noise[name].grad, named[name].grad) for name in named}
     assert len(errs) == len(named)
     bad = {k: (v, floor[k]) for k, v in errs.items() if not v < max(1e-4, 10 * floor[k])}
     assert not bad, bad

@@ -14,10 +14,10 @@ import numpy as np
 import pytest
 import torch
 
+from _gpu_util import no_host_sync
 import _point_head_np as ph
 from test_point_head_host import case_loss_inputs, make_head
 from lidardetection_amd import _lib, point_head
-from lidardetection_amd.pcdet.utils.cfg import AttrDict
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -28,10 +28,6 @@ TERMS = ("cls", "box", "part")
 @pytest.fixture(scope="module")
 def fx():
     return np.load(os.path.join(GOLDEN, "point_head_ref.npz"))
-
-
-def to_cfg(d):
-    return AttrDict({k: to_cfg(v) for k, v in d.items()}) if isinstance(d, dict) else d
 
 
 def _spec(name):
@@ -277,13 +273,10 @@ def test_no_host_synchronisation(fx, dev):
     x, b, p, tt = _loss_inputs(name, fx, dev, t)
     up = torch.tensor(UP, device=dev)
     torch.cuda.synchronize()
-    torch.cuda.set_sync_debug_mode("error")
-    try:
+    with no_host_sync():
         t2 = point_head.assign_point_targets(pts, gt, spec, True, True)
         cls, box, part, stats = point_head.point_head_loss(x, b, p, tt, spec)
         (up[0] * cls + up[1] * box + up[2] * part).backward()
-    finally:
-        torch.cuda.set_sync_debug_mode("default")
     assert torch.equal(t2["point_cls_labels"], t["point_cls_labels"]) and x.grad is not None and b.grad is not None and p.grad is not None
 
 

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+from _gpu_util import no_host_sync
 import _point_head_mf_np as mf
 from test_gpu_point_head import Guarded
 from test_point_head_mf_host import case_inputs, make_head
@@ -216,14 +217,11 @@ def test_inputs_are_never_written_and_no_host_synchronisation(fx, dev):
     x.grad = None
     up = torch.tensor(UP, device=dev)
     torch.cuda.synchronize()
-    torch.cuda.set_sync_debug_mode("error")
-    try:
+    with no_host_sync():
         t2 = point_head_mf.assign_point_targets_mf(pts, gt, loc, rot, spec)
         cls, stats = point_head_mf.point_head_loss_mf(x, t2, spec, 2)
         (up * cls).backward()
         e = point_head_mf.enlarged_gt_boxes(gt, loc, rot)
-    finally:
-        torch.cuda.set_sync_debug_mode("default")
     assert torch.equal(t2["point_cls_labels_stacked"], t["point_cls_labels_stacked"]) and x.grad is not None and e.shape == gt.shape
     assert all(torch.equal(a, b) for a, b in zip(keep, (pts, gt, loc, rot, x.detach())))
 

@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 import torch
 
+from _gpu_util import rel, release_memory  # noqa: F401  (release_memory: an autouse fixture)
 from lidardetection_amd import _lib, optim, sa_train, synth
 from lidardetection_amd.pvrcnn import PVRCNNKitti
 
@@ -12,20 +13,6 @@ DEV = torch.device("cuda:0")
 CL = torch.channels_last
 NOISE = 2.0 ** -17        # the noise floor of tests/test_gpu_second_train.py's fused-against-stock comparison
 ROIS = 16
-
-
-@pytest.fixture(autouse=True, scope="module")
-def _release_memory():
-    yield
-    import gc
-    gc.collect()
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
-
-
-def _rel(a, b):
-    a, b = a.detach().double().cpu(), b.detach().double().cpu()
-    return float((a - b).abs().max() / max(float(b.abs().max()), 1e-30)) if b.numel() else 0.0
 
 
 def _inputs(B, seed):
@@ -106,9 +93,9 @@ def test_pvrcnn_train_loss_fused_matches_stock(dev, monkeypatch):
     for ll in (lf, ls, ln):
         sum(ll).backward()
     pf, ps, pn = dict(fused.named_parameters()), dict(stock.named_parameters()), dict(noisy.named_parameters())
-    errs = {k: _rel(p.grad, ps[k].grad) for k, p in pf.items() if p.grad is not None}
+    errs = {k: rel(p.grad, ps[k].grad, empty_ok=True) for k, p in pf.items() if p.grad is not None}
     assert len(errs) == len([k for k, p in ps.items() if p.grad is not None]) == len(ps)
-    floors = {k: _rel(pn[k].grad, ps[k].grad) for k in errs}
+    floors = {k: rel(pn[k].grad, ps[k].grad, empty_ok=True) for k in errs}
     worst = max(errs, key=lambda k: errs[k] / max(1e-4, 10 * floors[k]))
     print("worst", worst, f"{errs[worst]:.1e}", "floor", f"{floors[worst]:.1e}")
     for k in sorted(errs, key=lambda k: -errs[k])[:8]:
@@ -117,7 +104,7 @@ def test_pvrcnn_train_loss_fused_matches_stock(dev, monkeypatch):
     assert not bad, bad
     for (k, bf), bs in zip(fused.named_buffers(), stock.buffers()):
         if "running" in k:      # the gradients' criterion: the stock step's own spread under the perturbation is the floor
-            assert _rel(bf, bs) < max(1e-4, 10 * _rel(dict(noisy.named_buffers())[k], bs)), k
+            assert rel(bf, bs, empty_ok=True) < max(1e-4, 10 * rel(dict(noisy.named_buffers())[k], bs, empty_ok=True)), k
         elif "num_batches" in k:
             assert int(bf) == int(bs) == 1
 

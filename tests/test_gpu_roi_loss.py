@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 import torch
 
+from _gpu_util import no_host_sync
 import _roi_loss_torch as rlt
 from lidardetection_amd import _lib, roi_loss
 from lidardetection_amd.pcdet.models.roi_heads.roi_head_template import RoIHeadTemplate
@@ -229,12 +230,9 @@ def test_sync_free_and_bitwise_deterministic(files, dev):
     torch.cuda.synchronize()
     for _ in range(2):
         leaves = [v.detach().clone().requires_grad_() for v in (x, r)]
-        torch.cuda.set_sync_debug_mode("error")
-        try:
+        with no_host_sync():
             cls, reg, cor, stats = roi_loss.roi_head_loss(leaves[0], leaves[1], td, spec)
             (cls + reg + cor).backward()
-        finally:
-            torch.cuda.set_sync_debug_mode(0)
         runs.append([stats.clone()] + [v.grad.clone() for v in leaves])
     for a, b in zip(*runs):
         assert torch.equal(a.reshape(-1).view(torch.int32), b.reshape(-1).view(torch.int32))

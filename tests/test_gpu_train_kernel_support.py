@@ -14,6 +14,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from _gpu_util import rel, release_memory  # noqa: F401  (release_memory: an autouse fixture)
 from lidardetection_amd import _lib, pillar_ops
 from lidardetection_amd.pcdet.models.backbones_3d.vfe.encoders import PillarVFE
 from lidardetection_amd.pcdet.utils.cfg import AttrDict
@@ -22,20 +23,6 @@ from test_gpu_wino_wgrad import BAR, _ref64
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 SENTINEL = 777.0
-
-
-@pytest.fixture(autouse=True, scope="module")
-def _release_memory():
-    yield
-    import gc
-    gc.collect()
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
-
-
-def _rel(a, b):
-    a, b = a.detach().double(), b.detach().double()
-    return float((a - b).abs().max() / max(float(b.abs().max()), 1e-30))
 
 
 # ------------------------------------------------------------------ 1. PFN train (csrc/pfn_train.hip)
@@ -169,7 +156,7 @@ def _pfn_case(cfg, seed, as_float=False, tail=0, gammas="mixed", dup=False, dev=
     z = F.linear(ref._decorate(vox.double(), num, coords), rl.linear.weight).detach()
     if tail:
         assert out.shape[0] == V + tail and bool((out[V:] == 0).all())
-    errs = {"out": _rel(out[:V], want)}
+    errs = {"out": rel(out[:V], want)}
     assert errs["out"] < 1e-5, errs
     mean64, var64 = z.mean(dim=(0, 1)), z.var(dim=(0, 1), unbiased=False)
     torch.testing.assert_close(mean.double(), mean64, rtol=1e-6, atol=1e-6 * float(mean64.abs().max()))
@@ -179,7 +166,7 @@ def _pfn_case(cfg, seed, as_float=False, tail=0, gammas="mixed", dup=False, dev=
     for name, a, b in (("d_weight", layer.linear.weight, rl.linear.weight), ("d_gamma", layer.norm.weight, rl.norm.weight),
                        ("d_beta", layer.norm.bias, rl.norm.bias)):
         assert a.grad is not None and bool(torch.isfinite(a.grad).all()), name
-        errs[name] = _rel(a.grad, b.grad)
+        errs[name] = rel(a.grad, b.grad)
     print(f"pfn {cfg} seed {seed}: " + "  ".join(f"{k} {v:.2e}" for k, v in errs.items()))
     assert all(errs[k] < 1e-4 for k in ("d_weight", "d_gamma", "d_beta")), errs
     with torch.no_grad():                                            # a second step: the running statistics after two calls
@@ -356,18 +343,18 @@ def _bn_check(segs, rows, seed, y_pad=(0, 0), g_pad=(0, 0), eps=1e-3, quantised=
         return None, ref
     y, dxs, dg, db, bstats = bn_run(xs, segs, gamma, beta, eps, y_ld, y_off, G, g_off)
     yk = y[:, y_off:y_off + ctot]
-    errs = dict(y=_rel(yk[:, keep], ref["y"][:, keep]), dg=_rel(dg[keep], ref["dg"][keep]), db=_rel(db[keep], ref["db"][keep]))
+    errs = dict(y=rel(yk[:, keep], ref["y"][:, keep]), dg=rel(dg[keep], ref["dg"][keep]), db=rel(db[keep], ref["db"][keep]))
     assert bool((y[:, :y_off] == SENTINEL).all()) and bool((y[:, y_off + ctot:] == SENTINEL).all())
     c0, dz_err = 0, 0.0
     for dx, want, (C_, ld, off) in zip(dxs, ref["dz"], segs):
         k = keep[c0:c0 + C_]
-        dz_err = max(dz_err, _rel(dx[:, off:off + C_][:, k], want[:, k]) if bool(k.any()) else 0.0)
+        dz_err = max(dz_err, rel(dx[:, off:off + C_][:, k], want[:, k]) if bool(k.any()) else 0.0)
         assert bool((dx[:, :off] == SENTINEL).all()) and bool((dx[:, off + C_:] == SENTINEL).all())
         c0 += C_
     errs["dz"] = dz_err
     n = float(rows)
     mean, var, uvar = bstats[:ctot], bstats[ctot:2 * ctot], bstats[2 * ctot:]
-    errs["mean"], errs["var"], errs["uvar"] = _rel(mean, ref["mean"]), _rel(var, ref["var"]), _rel(uvar, ref["var"] * n / (n - 1))
+    errs["mean"], errs["var"], errs["uvar"] = rel(mean, ref["mean"]), rel(var, ref["var"]), rel(uvar, ref["var"] * n / (n - 1))
     print(f"bn {segs} rows {rows}: " + "  ".join(f"{k} {v:.2e}" for k, v in errs.items()))
     assert all(errs[k] < 1e-5 for k in ("y", "dz", "dg", "db")), errs
     assert all(errs[k] < 1e-6 for k in ("mean", "var", "uvar")), errs
@@ -420,7 +407,7 @@ def test_bn_relu_constant_and_clamped_channels():
     # dz of the constant channel: gamma / sqrt(eps) (delta - mean delta), the z-hat term vanishing
     g5 = out["G"][:, out["g_off"] + 5].double()
     dz5 = 0.75 / eps ** 0.5 * (g5 - g5.mean())
-    assert _rel(out["dxs"][0][:, 4 + 5], dz5) < 1e-5
+    assert rel(out["dxs"][0][:, 4 + 5], dz5) < 1e-5
     for c, (seg, col) in ((9, (0, 4 + 9)), (14, (1, 2))):
         assert bool((out["yk"][:, c] == 0).all())
         assert float(out["dg"][c]) == 0.0 and float(out["db"][c]) == 0.0
@@ -472,7 +459,7 @@ def test_bn_relu_large_mean_channel_within_4x_of_stock_fp32():
     (ys * out["G"][:, 4:16]).sum().backward()
     pairs = dict(y=(out["yk"][:, ch], ys[:, ch], ref["y"][:, ch]), dz=(out["dxs"][0][:, 4 + ch], z.grad[:, ch], ref["dz"][0][:, ch]),
                  dg=(out["dg"][ch], gm.grad[ch], ref["dg"][ch]), db=(out["db"][ch], bt.grad[ch], ref["db"][ch]))
-    res = {k: (_rel(a, r), _rel(s, r)) for k, (a, s, r) in pairs.items()}
+    res = {k: (rel(a, r), rel(s, r)) for k, (a, s, r) in pairs.items()}
     print("bn large-mean channel, kernel / stock fp32: " + "  ".join(f"{k} {a:.2e} / {s:.2e}" for k, (a, s) in res.items()))
     bad = {k: v for k, v in res.items() if not v[0] <= (max(4 * v[1], 1e-5) if k == "y" else 1e-5)}
     assert not bad, bad
@@ -503,7 +490,7 @@ def test_wgrad_rectangular_widths_and_unequal_strides(cin, cout):
     x_ld, g_ld = cin + 44, cout + 12
     assert x_ld != g_ld
     dw, ref = _wgrad_raw(2, 13, 10, cin, cout, x_ld, g_ld, 4, 4, 700 + cin)
-    err = _rel(dw, ref)
+    err = rel(dw, ref)
     print(f"wgrad43 raw cin {cin} cout {cout} x_ld {x_ld} g_ld {g_ld}: {err:.3e}")
     assert err <= BAR
 
@@ -514,7 +501,7 @@ def test_wgrad_every_small_map():
     for H in range(1, 10):
         for W in range(1, 10):
             dw, ref = _wgrad_raw(2, H, W, 32, 64, 36, 72, 4, 8, 800 + 10 * H + W)
-            err = _rel(dw, ref)
+            err = rel(dw, ref)
             print(f"wgrad43 raw map {H}x{W}: {err:.3e}")
             worst = max(worst, err)
             assert err <= BAR, (H, W, err)
@@ -531,7 +518,7 @@ def test_wgrad_tile_counts_across_the_split(tiles, cin, cout):
     B, H, W = WGRAD_TILES[tiles]
     assert B * ((H + 3) // 4) * ((W + 3) // 4) == tiles
     dw, ref = _wgrad_raw(B, H, W, cin, cout, cin + 4, cout + 8, 4, 0, 900 + tiles)
-    err = _rel(dw, ref)
+    err = rel(dw, ref)
     print(f"wgrad43 raw {tiles} tiles (B, H, W) = {(B, H, W)} cin {cin} cout {cout}: {err:.3e}")
     assert err <= BAR
 
@@ -540,6 +527,6 @@ def test_wgrad_large_positive_mean_input():
     """post-ReLU x with mean / sigma = 8 against zero-mean g: the input transform's rows cancel the mean except one (row sums of
     B^T: 0, -6, 0, 0, 0, 0), whose position then carries 36 * mean into the fp32 accumulation"""
     dw, ref = _wgrad_raw(2, 30, 26, 64, 128, 64 + 8, 128 + 4, 4, 4, 950, shift=8.0)
-    err = _rel(dw, ref)
+    err = rel(dw, ref)
     print(f"wgrad43 raw large-mean x: {err:.3e}")
     assert err <= BAR

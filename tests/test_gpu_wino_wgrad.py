@@ -14,6 +14,7 @@ import pytest
 import torch
 import torch.nn as nn
 
+from _gpu_util import no_host_sync, pp_inputs, rel, release
 from lidardetection_amd import bev_train, wino, workspace
 from lidardetection_amd.pcdet.models.backbones_2d.base_bev_backbone import BaseBEVBackbone
 from lidardetection_amd.pointpillar import make_bev_backbone
@@ -36,16 +37,7 @@ FIXTURE_CFG = _Cfg(LAYER_NUMS=[1, 1], LAYER_STRIDES=[2, 2], NUM_FILTERS=[64, 32]
 @pytest.fixture(autouse=True, scope="module")
 def _release_memory():
     yield
-    import gc
-    gc.collect()
-    torch.cuda.synchronize()
-    workspace.drop("wino43_wgrad")
-    torch.cuda.empty_cache()
-
-
-def _rel(a, b):
-    a, b = a.detach().double(), b.detach().double()
-    return float((a - b).abs().max() / max(float(b.abs().max()), 1e-30))
+    release("wino43_wgrad")
 
 
 def _randn(shape, seed, scale=1.0, shift=0.0):
@@ -82,7 +74,7 @@ def test_kernel_matches_float64(shape, sliced):
         x, g = _map(shape, 1, True), _map(shape, 2, False)
     dw = wino.conv3x3_wgrad_f43(x, g)
     assert dw.shape == (C, C, 3, 3) and dw.is_contiguous() and dw.dtype == torch.float32
-    err = _rel(dw, _ref64(x, g))
+    err = rel(dw, _ref64(x, g))
     print(f"wgrad43 {shape} sliced={sliced}: {err:.3e}")
     assert err <= BAR
 
@@ -94,7 +86,7 @@ def test_production_shapes_match_float64(shape):
     dw = wino.conv3x3_wgrad_f43(x, g)
     w = torch.zeros((shape[1], shape[1], 3, 3), device=DEV).contiguous(memory_format=CL)
     lib = torch.ops.aten.convolution_backward(g, x, w, None, [1, 1], [1, 1], [1, 1], False, [0, 0], 1, [False, True, False])[1]
-    err, err_lib = _rel(dw, ref), _rel(lib, ref)
+    err, err_lib = rel(dw, ref), rel(lib, ref)
     print(f"wgrad43 {shape}: kernel {err:.3e}  library {err_lib:.3e}")
     assert err <= BAR
 
@@ -148,11 +140,11 @@ def test_autograd(cin, cout, hw):
     (torch.nn.functional.conv2d(x64, w64, None, 1, 1) * res["wino"][5].double()).sum().backward()
     assert torch.equal(res["wino"][0], res["library"][0])            # the forward is untouched
     assert torch.equal(res["wino"][1], res["library"][1])            # ... and so is the input gradient
-    assert _rel(res["wino"][2], w64.grad) <= BAR
+    assert rel(res["wino"][2], w64.grad) <= BAR
     # accumulation: a second backward into the same .grad gives twice the single one, to fp32 rounding
     _, _, single, x, w, G = res["wino"]
     (bev_train.conv3x3_train(x, w, wgrad="wino") * G).sum().backward()
-    assert _rel(w.grad, 2 * single) <= 2.0 ** -22
+    assert rel(w.grad, 2 * single) <= 2.0 ** -22
 
 
 def _fixture_model(z):
@@ -178,19 +170,19 @@ def test_backbone_matches_reference_fixture(golden_dir):
     assert tb.routes() == ([["conv", "wino"], ["conv", "wino"]], ["fused", "fused"])
     assert tb.wgrad_routes() == [[None, "wino"], [None, "wino"]]     # 64 -> 64 and 32 -> 32: both widths are supported
     y = ys[2]
-    assert _rel(y, torch.from_numpy(z["out64"]).to(DEV)) < 1e-5
+    assert rel(y, torch.from_numpy(z["out64"]).to(DEV)) < 1e-5
     if torch.equal(ys[0], ys[1]):                                    # the library-option forward is bitwise stable here: ours equals it
         assert torch.equal(y, ys[0])
     (y * G).sum().backward()
-    assert _rel(x.grad, torch.from_numpy(z["dx64"]).to(DEV)) < 1e-4
+    assert rel(x.grad, torch.from_numpy(z["dx64"]).to(DEV)) < 1e-4
     for name, mod in m.named_modules():
         if isinstance(mod, nn.BatchNorm2d):
-            assert _rel(mod.weight.grad, torch.from_numpy(z["d_gamma." + name]).to(DEV)) < 1e-4, name
-            assert _rel(mod.bias.grad, torch.from_numpy(z["d_beta." + name]).to(DEV)) < 1e-4, name
+            assert rel(mod.weight.grad, torch.from_numpy(z["d_gamma." + name]).to(DEV)) < 1e-4, name
+            assert rel(mod.bias.grad, torch.from_numpy(z["d_beta." + name]).to(DEV)) < 1e-4, name
         elif isinstance(mod, (nn.Conv2d, nn.ConvTranspose2d)):
             key = name + ".weight"
             ref = torch.from_numpy(z["dw16." + key].astype(np.float32)).to(DEV) * float(z["dw_scale." + key])
-            assert _rel(mod.weight.grad, ref) < 2e-3, name           # float16 storage
+            assert rel(mod.weight.grad, ref) < 2e-3, name           # float16 storage
 
 
 def _three(make, seed):
@@ -221,45 +213,25 @@ def test_pointpillar_widths_match_library_option():
     yl = bev_train.TrainBEVBackbone(lib[0], lib[1])(xs[1])
     noise = 1 + NOISE * _randn(shape, 42)
     yn = bev_train.TrainBEVBackbone(noisy[0], noisy[1])((xs[2] * noise).contiguous(memory_format=CL))
-    assert _rel(yw, yl) < 1e-4
+    assert rel(yw, yl) < 1e-4
     G = _randn(yw.shape, 43).contiguous(memory_format=CL)
     for y in (yw, yl, yn):
         (y * G).sum().backward()
-    assert _rel(xs[0].grad, xs[1].grad) < max(1e-4, 10 * _rel(xs[2].grad, xs[1].grad))
+    assert rel(xs[0].grad, xs[1].grad) < max(1e-4, 10 * rel(xs[2].grad, xs[1].grad))
     pw, pl, pn = dict(new.named_parameters()), dict(lib.named_parameters()), dict(noisy.named_parameters())
     bad = {}
     for k in pl:
         assert pw[k].grad is not None and bool(torch.isfinite(pw[k].grad).all()), k
-        err, fl = _rel(pw[k].grad, pl[k].grad), _rel(pn[k].grad, pl[k].grad)
+        err, fl = rel(pw[k].grad, pl[k].grad), rel(pn[k].grad, pl[k].grad)
         if not err < max(1e-4, 10 * fl):
             bad[k] = (err, fl)
     assert not bad, bad
 
 
-def _pp_inputs(B, seed):
-    from lidardetection_amd import synth
-    frames = [synth.cloud_ring(2300 + seed + i) for i in range(B)]
-    pts = torch.from_numpy(np.concatenate(frames)).to(DEV)
-    offs = torch.tensor(np.cumsum([0] + [len(f) for f in frames]), dtype=torch.int32, device=DEV)
-    r = np.random.default_rng(seed)
-    gt = np.zeros((B, 12, 8), np.float32)
-    for b in range(B):
-        n = 8
-        gt[b, :n, 0] = r.uniform(5, 60, n)
-        gt[b, :n, 1] = r.uniform(-30, 30, n)
-        gt[b, :n, 2] = r.uniform(-1.5, -0.5, n)
-        cls = r.integers(1, 4, n)
-        size = np.array([[3.9, 1.6, 1.56], [0.8, 0.6, 1.73], [1.76, 0.6, 1.73]], np.float32)[cls - 1]
-        gt[b, :n, 3:6] = size * r.uniform(0.9, 1.1, (n, 1))
-        gt[b, :n, 6] = r.uniform(-np.pi, np.pi, n)
-        gt[b, :n, 7] = cls
-    return pts, offs, torch.from_numpy(gt).to(DEV)
-
-
 def test_train_loss_wino_matches_library_option():
     from lidardetection_amd import pillar_ops
     from lidardetection_amd.pointpillar import PointPillarKITTI
-    pts, offs, gt = _pp_inputs(2, 5)
+    pts, offs, gt = pp_inputs(2, 5, 2300)
     models = []
     for _ in range(3):
         torch.manual_seed(6)
@@ -277,9 +249,9 @@ def test_train_loss_wino_matches_library_option():
     for losses in (lw, ll, ln):
         sum(losses).backward()
     pw, pl, pn = dict(new.named_parameters()), dict(lib.named_parameters()), dict(noisy.named_parameters())
-    errs = {k: _rel(p.grad, pl[k].grad) for k, p in pw.items() if p.grad is not None and bool(torch.isfinite(p.grad).all())}
+    errs = {k: rel(p.grad, pl[k].grad) for k, p in pw.items() if p.grad is not None and bool(torch.isfinite(p.grad).all())}
     assert len(errs) == len(pl)                                      # every parameter received a finite gradient
-    bad = {k: (v, _rel(pn[k].grad, pl[k].grad)) for k, v in errs.items() if not v < max(1e-4, 10 * _rel(pn[k].grad, pl[k].grad))}
+    bad = {k: (v, rel(pn[k].grad, pl[k].grad)) for k, v in errs.items() if not v < max(1e-4, 10 * rel(pn[k].grad, pl[k].grad))}
     assert not bad, bad
     routes = [r for blk in new.__dict__["_bev_train_wino"].wgrad_routes() for r in blk]
     assert routes.count("wino") == 13 and "library" not in routes
@@ -296,12 +268,8 @@ def test_sync_free():
         mods = copy.deepcopy(base)
         x = x0.clone().requires_grad_()
         tb = bev_train.TrainBEVBackbone(mods[0], mods[1], wgrad="wino")
-        if rep > 0:
-            torch.cuda.set_sync_debug_mode("error")
-        try:
+        with no_host_sync(rep > 0):
             (tb(x) * G).sum().backward()
-        finally:
-            torch.cuda.set_sync_debug_mode(0)
         assert x.grad is not None
         grads.append(mods)
     for p in grads[2].parameters():

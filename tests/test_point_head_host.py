@@ -9,11 +9,11 @@ import numpy as np
 import pytest
 import torch
 
+from _gpu_util import to_cfg
 import _point_head_np as ph
 from lidardetection_amd import _lib, point_head
 from lidardetection_amd.pcdet.models import dense_heads
 from lidardetection_amd.pcdet.utils.box_coder_utils import PointResidualCoder
-from lidardetection_amd.pcdet.utils.cfg import AttrDict
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
@@ -21,10 +21,6 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 @pytest.fixture(scope="module")
 def fx():
     return np.load(os.path.join(GOLDEN, "point_head_ref.npz"))
-
-
-def to_cfg(d):
-    return AttrDict({k: to_cfg(v) for k, v in d.items()}) if isinstance(d, dict) else d
 
 
 def close(a, b, tol=1e-9):

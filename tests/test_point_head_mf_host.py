@@ -8,10 +8,10 @@ import numpy as np
 import pytest
 import torch
 
+from _gpu_util import to_cfg
 import _point_head_mf_np as mf
 from lidardetection_amd import _lib, point_head_mf
 from lidardetection_amd.pcdet.models import dense_heads
-from lidardetection_amd.pcdet.utils.cfg import AttrDict
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
@@ -19,10 +19,6 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 @pytest.fixture(scope="module")
 def fx():
     return np.load(os.path.join(GOLDEN, "point_head_mf_ref.npz"))
-
-
-def to_cfg(d):
-    return AttrDict({k: to_cfg(v) for k, v in d.items()}) if isinstance(d, dict) else d
 
 
 def make_head(name, **kw):

@@ -13,7 +13,6 @@ import argparse
 import json
 import os
 import sys
-import time
 
 import numpy as np
 import torch
@@ -22,24 +21,12 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from lidardetection_amd import atss_assign  # noqa: E402
 from lidardetection_amd.pcdet.models.dense_heads.target_assigner.anchor_generator import AnchorGenerator  # noqa: E402
 
+from _measure import event_and_enqueue_ms  # noqa: E402
+
 HBM_PEAK = 8.0e12
 KITTI_SIZES = [([3.9, 1.6, 1.56], -1.78), ([0.8, 0.6, 1.73], -0.6), ([1.76, 0.6, 1.73], -0.6)]
 NUS_SIZES = [[4.63, 1.97, 1.74], [6.93, 2.51, 2.84], [6.37, 2.85, 3.19], [10.5, 2.94, 3.47], [12.29, 2.90, 3.87],
              [0.50, 2.53, 0.98], [2.11, 0.77, 1.47], [1.70, 0.60, 1.28], [0.73, 0.67, 1.77], [0.41, 0.41, 1.07]]
-
-
-def timed(fn, steps):
-    """-> (GPU ms per call, host enqueue ms per call)"""
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    start.record()
-    for _ in range(steps):
-        fn()
-    end.record()
-    host = time.perf_counter() - t0
-    torch.cuda.synchronize()
-    return start.elapsed_time(end) / steps, host * 1e3 / steps
 
 
 def shape(name, dev):
@@ -80,7 +67,7 @@ def main():
         fn = lambda: atss_assign.assign(flat, gt, 9, code, sincos=sincos)  # noqa: E731
         for _ in range(args.warmup):
             labels, _, _ = fn()
-        gpu_ms, host_ms = timed(fn, args.steps)
+        gpu_ms, host_ms = event_and_enqueue_ms(fn, args.steps)
         n = sum(a.shape[0] for a in flat)
         nbytes = gt.shape[0] * n * (4 + 4 * code + 4)
         out[name] = dict(batch=int(gt.shape[0]), sets=len(flat), anchors=n, max_gt=int(gt.shape[1]), topk=9,

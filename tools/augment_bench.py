@@ -20,6 +20,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import _augment_np as anp  # noqa: E402
 from lidardetection_amd import _lib, augment  # noqa: E402
+from _measure import event_total_ms, host_ms  # noqa: E402
 
 
 def make_batch(B, seed=0, G=3, S=15, n_db=600, M=24):
@@ -78,14 +79,7 @@ def main():
     offs = out["point_offsets"].cpu().numpy()
     rows_off = int(np.abs(offs - ref["point_offsets"]).max())
     # wrapper wall time
-    for _ in range(args.warmup):
-        aug(*dargs, inp["cand"], **kw)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(args.iters):
-        aug(*dargs, inp["cand"], **kw)
-    torch.cuda.synchronize()
-    wrapper_ms = (time.perf_counter() - t0) * 1e3 / args.iters
+    wrapper_ms = host_ms(lambda: aug(*dargs, inp["cand"], **kw), args.iters, warmup=args.warmup)
     # the raw call, device time from events
     L = _lib.lib()
     B, G, S = inp["cand"].shape
@@ -108,16 +102,7 @@ def main():
 
     for _ in range(args.warmup):
         assert call() == 0
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(5):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(args.iters):
-            call()
-        e1.record()
-        torch.cuda.synchronize()
-        times.append(e0.elapsed_time(e1) / args.iters)
+    times = [event_total_ms(call, args.iters, 0) for _ in range(5)]
     assert torch.equal(o["points"][:int(offs[-1])], out["points"][:int(offs[-1])])
     dev_ms = float(np.median(times))
     pasted = int(np.where(out["sample_valid"].cpu().numpy() > 0, np.diff(inp["db_offsets"])[inp["cand"]], 0).sum())

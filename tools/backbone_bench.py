@@ -1,9 +1,10 @@
 """Dense 2D backbone + head of PointPillar-KITTI (bs 16, fp32): stock modules vs the folded-BN fast path
 (lidardetection_amd/bev_backbone.py), plus a probe of torch's fused MIOpen conv+bias+relu op."""
-import os, sys, time
+import os, sys
 import torch, torch.nn.functional as F
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from lidardetection_amd.pointpillar import PointPillarKITTI
+from _measure import host_ms
 dev = torch.device("cuda:0")
 m = PointPillarKITTI(batch_size=16, device=dev).randomize_for_bench(0)
 x = torch.randn(16, 64, 496, 432, device=dev)
@@ -13,11 +14,7 @@ x = x.contiguous(memory_format=torch.channels_last)
 
 def run(fn, n=10):
     with torch.no_grad():
-        for _ in range(3): fn()
-        torch.cuda.synchronize(); t = time.perf_counter()
-        for _ in range(n): fn()
-        torch.cuda.synchronize()
-    return (time.perf_counter() - t) / n * 1e3
+        return host_ms(fn, n, warmup=3)
 
 
 print("stock modules (channels_last)  %.2f ms" % run(lambda: m.backbone_head_stock(x)), flush=True)

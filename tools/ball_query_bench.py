@@ -2,15 +2,11 @@ import os, sys, numpy as np, torch
 sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
 from lidardetection_amd import synth
 from lidardetection_amd.ext import pointnet2_stack_cuda as native
+from _measure import event_total_ms
 dev = torch.device("cuda:0")
 def ev(fn, n=20):
-    for _ in range(3): fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(n): fn()
-    b.record(); torch.cuda.synchronize()
-    return a.elapsed_time(b) / n * 1e3
+    return event_total_ms(fn, n, 3) * 1e3      # us per call
+
 B = 8
 frames = [synth.cloud_ring(2000 + f)[:, :3] for f in range(B)]
 xyz = torch.from_numpy(np.concatenate(frames, 0)).to(dev).contiguous()

@@ -7,7 +7,7 @@ process:
   step      PointPillarKITTI.train_loss(backbone=...) + backward (gradients of every parameter);
   backbone  backbone_head_stock / backbone_head_train + backward alone on a fixed channels-last canvas (no PFN, scatter or loss).
 
-Inputs: 16 synthetic KITTI-like clouds and boxes (tests/test_gpu_pfn_train.py's workload).  Device events, each iteration times
+Inputs: 16 synthetic KITTI-like clouds and boxes (tests/_pp_train_torch.py's workload).  Device events (_measure.alternate), each iteration times
 one call of each column back to back; medians after warm-up; peak memory from torch.cuda.max_memory_allocated above what was
 allocated before the call.  Prints one JSON line.
 
@@ -18,57 +18,25 @@ allocated before the call.  Prints one JSON line.
 statistics come from a run of their own.
 """
 import argparse
-import importlib.util
 import json
 import os
 import subprocess
 import sys
 
-import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))    # the workload builders and restatements the tests use
+
+import _pp_train_torch as T  # noqa: E402
+from _measure import alternate, peak_mb  # noqa: E402
 
 
 KINDS = ("stock", "fused", "fused_wino", "fused_wino_gemm")
 # column -> (backbone option, wgrad option, deblock option) of PointPillarKITTI.train_loss / backbone_head_train
 OPTIONS = {"stock": ("stock", "library", "library"), "fused": ("fused", "library", "library"), "fused_wino": ("fused", "wino", "library"),
            "fused_wino_gemm": ("fused", "wino", "gemm")}
-
-
-def load_test_module():
-    spec = importlib.util.spec_from_file_location("_pfn_train_tests", os.path.join(ROOT, "tests", "test_gpu_pfn_train.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-def peak_mb(fn):
-    torch.cuda.synchronize()
-    base = torch.cuda.memory_allocated()
-    torch.cuda.reset_peak_memory_stats()
-    fn()
-    torch.cuda.synchronize()
-    return round((torch.cuda.max_memory_allocated() - base) / 2 ** 20, 1)
-
-
-def alternate(fns, iters, warmup):
-    """{name: (median ms, min ms)}, the callables timed in turn within every iteration"""
-    for _ in range(warmup):
-        for fn in fns.values():
-            fn()
-    torch.cuda.synchronize()
-    ev = {k: (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for k in fns}
-    times = {k: [] for k in fns}
-    for _ in range(iters):
-        for k, fn in fns.items():
-            ev[k][0].record()
-            fn()
-            ev[k][1].record()
-            ev[k][1].synchronize()
-            times[k].append(ev[k][0].elapsed_time(ev[k][1]))
-    return {k: (float(np.median(v)), float(np.min(v))) for k, v in times.items()}
 
 
 def main():
@@ -80,9 +48,8 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("bev_train_bench: no GPU")
     from lidardetection_amd.pointpillar import PointPillarKITTI
-    T = load_test_module()
     dev, B = T.DEV, 16
-    pts, offs, gt = T._pp_inputs(B, 5)
+    pts, offs, gt = T.pp_inputs(B, 5)
     torch.manual_seed(4)
     pp = PointPillarKITTI(batch_size=B, device=dev).train()
     params = [p for p in pp.parameters() if p.requires_grad]

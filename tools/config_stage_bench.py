@@ -3,19 +3,14 @@ import os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from lidardetection_amd import synth
+from _measure import event_queued_ms
 
 dev = torch.device("cuda:0")
 
 
 def gpu_time(fn, n=7):
-    for _ in range(2):
-        r = fn()
-    torch.cuda.synchronize()
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)]
-    for a, b in evs:
-        a.record(); r = fn(); b.record()
-    torch.cuda.synchronize()
-    return float(np.median([a.elapsed_time(b) for a, b in evs])), r
+    times, r = event_queued_ms(fn, n, 2)
+    return float(np.median(times)), r
 
 
 def batch(frames):

@@ -2,8 +2,9 @@
 3x3 shapes of the PointPillar BEV backbone (bs 16, fp32) and names the kernels that ran (is there a
 non-atomic solver that is as fast as the split-K one, and does any fp32 Winograd solver exist on gfx950?).
 usage: python tools/conv_solver_probe.py LAYOUT(nhwc|nchw) DETERMINISTIC(0|1) [tag]    (env: MIOPEN_* as wanted)"""
-import sys, time
+import sys
 import torch, torch.nn.functional as F
+from _measure import host_ms
 layout, det = sys.argv[1], sys.argv[2] == "1"
 tag = sys.argv[3] if len(sys.argv) > 3 else ""
 dev = torch.device("cuda:0")
@@ -12,11 +13,7 @@ torch.backends.cudnn.deterministic = det
 
 
 def run(fn, n=10):
-    for _ in range(3): fn()
-    torch.cuda.synchronize(); t = time.perf_counter()
-    for _ in range(n): fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t) / n * 1e3
+    return host_ms(fn, n, warmup=3)
 
 
 out = []

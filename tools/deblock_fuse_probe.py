@@ -4,6 +4,7 @@ import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from lidardetection_amd.bev_backbone import bias_act_upsample_
+from _measure import event_total_ms
 dev = torch.device("cuda:0")
 B, H, W, K, N, CT = 16, 248, 216, 64, 128, 384
 torch.manual_seed(0)
@@ -16,12 +17,7 @@ A = x.permute(0, 2, 3, 1).reshape(B * H * W, K)
 
 
 def t(fn, n=20):
-    for _ in range(3): fn()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize(); e0.record()
-    for _ in range(n): fn()
-    e1.record(); torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n * 1e3
+    return event_total_ms(fn, n, 3) * 1e3      # us per call
 
 
 def cur():

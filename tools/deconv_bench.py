@@ -4,17 +4,12 @@ import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from lidardetection_amd.bev_backbone import deconv_pack, deconv_gemm_into_
+from _measure import event_total_ms
 dev = torch.device("cuda:0")
 
 
 def ev(fn, n=30, warm=5):
-    for _ in range(warm): fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(n): fn()
-    b.record(); torch.cuda.synchronize()
-    return a.elapsed_time(b) / n
+    return event_total_ms(fn, n, warm)
 
 
 for B, K, h, w, s, cup in [(16, 128, 124, 108, 2, 128), (16, 256, 62, 54, 4, 128), (16, 256, 100, 88, 2, 256)]:

@@ -1,13 +1,11 @@
-import os, sys, time
+import os, sys
 import torch, torch.nn.functional as F
+from _measure import host_ms
 dev = torch.device("cuda:0")
 torch.backends.cudnn.benchmark = True
 def run(fn, n=10):
-    for _ in range(3): fn()
-    torch.cuda.synchronize(); t = time.perf_counter()
-    for _ in range(n): fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t) / n * 1e3
+    return host_ms(fn, n, warmup=3)
+
 for C, H, W in ((64, 248, 216), (128, 124, 108), (256, 62, 54)):
     x = torch.randn(16, C, H, W, device=dev)
     w = torch.randn(C, C, 3, 3, device=dev) * 0.05

@@ -8,6 +8,7 @@ from lidardetection_amd.pcdet.models.backbones_3d import spconv_backbone, vfe
 from lidardetection_amd.pcdet.utils.cfg import AttrDict
 from lidardetection_amd.voxelizer import BatchVoxelizer
 from lidardetection_amd.spconv import ops
+from _measure import event_total_ms
 
 dev = torch.device("cuda:0")
 B = 16
@@ -19,12 +20,7 @@ m = spconv_backbone.VoxelBackBone8x(AttrDict(), 4, [1408, 1600, 40]).to(dev).eva
 
 
 def timeit(fn, n=10):
-    for _ in range(3): fn()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize(); e0.record()
-    for _ in range(n): fn()
-    e1.record(); torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n * 1e3
+    return event_total_ms(fn, n, 3) * 1e3      # us per call
 
 
 with torch.no_grad():

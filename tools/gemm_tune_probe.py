@@ -2,18 +2,14 @@
 vs. PyTorch TunableOp's pick (tuned in-process)."""
 import os, sys, time
 import torch
+from _measure import event_total_ms
 dev = torch.device("cuda:0")
 shapes = {"deblock1 (fused elsewhere)": (16 * 248 * 216, 64, 128), "deblock2": (16 * 124 * 108, 128, 512), "deblock3": (16 * 62 * 54, 256, 2048),
           "heads (addmm)": (16 * 248 * 216, 384, 72)}
 
 
 def t(fn, n=20):
-    for _ in range(3): fn()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize(); e0.record()
-    for _ in range(n): fn()
-    e1.record(); torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n * 1e3
+    return event_total_ms(fn, n, 3) * 1e3      # us per call
 
 
 ops = {}

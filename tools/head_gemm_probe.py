@@ -1,16 +1,12 @@
 """Head (384 -> 72, 1x1) as MIOpen conv vs a plain GEMM (torch.addmm -> hipBLASLt/rocBLAS) on the NHWC map."""
-import time
 import torch, torch.nn.functional as F
+from _measure import host_ms
 dev = torch.device("cuda:0")
 torch.backends.cudnn.benchmark = True
 
 
 def run(fn, n=10):
-    for _ in range(3): fn()
-    torch.cuda.synchronize(); t = time.perf_counter()
-    for _ in range(n): fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t) / n * 1e3
+    return host_ms(fn, n, warmup=3)
 
 
 B, C, H, W, N = 16, 384, 248, 216, 72

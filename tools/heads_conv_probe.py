@@ -1,13 +1,9 @@
 import torch, torch.nn.functional as F
+from _measure import event_total_ms
 dev = torch.device("cuda:0")
 def ev(fn, n=10):
-    for _ in range(3): fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(n): fn()
-    b.record(); torch.cuda.synchronize()
-    return a.elapsed_time(b) / n
+    return event_total_ms(fn, n, 3)
+
 cl = lambda t: t.contiguous(memory_format=torch.channels_last)
 x = cl(torch.randn(4, 64, 128, 128, device=dev))
 w1 = cl(torch.randn(2304, 64, 3, 3, device=dev) * 0.05)

@@ -1,8 +1,8 @@
 """Times the fused anchor-head loss (lidardetection_amd/anchor_loss.py) against the torch restatement of the reference's get_loss in
-tests/test_anchor_loss_host.py (fp32, autograd), forward alone and forward + backward, at PointPillar-KITTI bs 16 (321 408 anchors per
+tests/_anchor_loss_torch.py (fp32, autograd), forward alone and forward + backward, at PointPillar-KITTI bs 16 (321 408 anchors per
 frame, 3 classes, code 7, 2 direction bins) and SECOND-MultiHead-NuScenes bs 4 (6 heads, 327 680 anchors, code 10, WeightedL1Loss,
-no direction classifier).  Labels and targets come from the GPU assigner (the workloads of tests/test_gpu_anchor_loss.py).  Device
-events after warm-up; prints one JSON line.
+no direction classifier).  Labels and targets come from the GPU assigner (the workloads of the same module).  Device
+events per call after warm-up (_measure.event_ms); prints one JSON line.
 
   python tools/loss_bench.py [--iters 50] [--ref-iters 10] [--rocprof OUTDIR]
 
@@ -12,44 +12,23 @@ HBM floor, from shapes at 8 TB/s: forward reads cls + box + dir logits, targets 
 same and writes the three gradients.
 """
 import argparse
-import importlib.util
 import json
 import os
 import subprocess
 import sys
 
-import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))    # the workload builders and restatements the tests use
 
 from lidardetection_amd import anchor_loss  # noqa: E402
 
+import _anchor_loss_torch as T  # noqa: E402
+from _measure import event_ms  # noqa: E402
+
 HBM_BYTES_PER_S = 8.0e12
-
-
-def load_test_module():
-    """the workloads and (through it) the restatement live in the GPU test file; loading it by path keeps one copy"""
-    spec = importlib.util.spec_from_file_location("_loss_tests", os.path.join(ROOT, "tests", "test_gpu_anchor_loss.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-def time_ms(fn, iters, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    times = []
-    for _ in range(iters):
-        start.record()
-        fn()
-        end.record()
-        end.synchronize()
-        times.append(start.elapsed_time(end))
-    return float(np.median(times)), float(np.min(times))
 
 
 def main():
@@ -61,13 +40,12 @@ def main():
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("loss_bench: no GPU")
-    T = load_test_module()
     result = {"tool": "loss_bench", "device": torch.cuda.get_device_name(0), "workloads": {}}
     for name in ["pointpillar_kitti_bs16", "second_multihead_nuscenes_bs4"]:
         if name.startswith("pointpillar"):
-            _, head, t, cls, box, dirs, _ = T._pp_case(B=16, seed=0)
+            _, head, t, cls, box, dirs, _ = T.pp_case(B=16, seed=0)
         else:
-            _, head, t, cls, box, _ = T._nus_case(B=4, seed=1)
+            _, head, t, cls, box, _ = T.nus_case(B=4, seed=1)
             dirs = []
         spec, anchors = head.loss_spec, head.loss_anchors()
         labels, targets = t['box_cls_labels'], t['box_reg_targets']
@@ -83,8 +61,8 @@ def main():
                 torch.autograd.grad(list(losses), leaves)
 
         with torch.no_grad():
-            fwd_med, fwd_min = time_ms(lambda: fused(False), args.iters, 5)
-        fb_med, fb_min = time_ms(lambda: fused(True), args.iters, 5)
+            fwd_med, fwd_min, _ = event_ms(lambda: fused(False), args.iters, 5)
+        fb_med, fb_min, _ = event_ms(lambda: fused(True), args.iters, 5)
         code, bins = len(spec.code_weights), spec.num_dir_bins if dirs else 0
         cls_cols = sum(int(x.numel()) for x in cls) // (B * N)    # class logits per anchor (multihead: each head's own)
         read = B * N * 4 * (cls_cols + code + bins + code + 1)
@@ -99,9 +77,9 @@ def main():
                 rl = [x.detach().requires_grad_() for x in leaves]
                 widths = [x.shape[-1] if nh > 1 else spec.num_class for x in cls] + [code] * nh + [bins] * len(dirs)
                 views = [x.reshape(B, -1, c) for x, c in zip(rl, widths)]
-                losses = T.H.restated_loss(views[:nh], views[nh:2 * nh], views[2 * nh:], labels, targets, anchors, spec)
+                losses = T.restated_loss(views[:nh], views[nh:2 * nh], views[2 * nh:], labels, targets, anchors, spec)
                 torch.autograd.grad([x for x in losses if x.requires_grad], rl)
-            r_med, r_min = time_ms(restated, args.ref_iters, 2)
+            r_med, r_min, _ = event_ms(restated, args.ref_iters, 2)
             w.update({"restated_fwd_bwd_ms_median": round(r_med, 3), "restated_fwd_bwd_ms_min": round(r_min, 3),
                       "speedup": round(r_med / fb_med, 1)})
         result["workloads"][name] = w

@@ -3,6 +3,7 @@ import os, sys, numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from lidardetection_amd import synth
 from lidardetection_amd.ext import iou3d_nms_cuda
+from _measure import event_total_ms
 dev = torch.device("cuda:0")
 B = 16
 bt = []
@@ -11,12 +12,6 @@ for k in range(B):
     bt.append(torch.from_numpy(b[np.argsort(-s, kind="stable")]))
 boxes = torch.stack(bt).to(dev)
 for thr in (0.01, 0.7):
-    for _ in range(3):
-        keep, num = iou3d_nms_cuda.nms_batch(boxes, None, thr)
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(20):
-        keep, num = iou3d_nms_cuda.nms_batch(boxes, None, thr)
-    e1.record(); torch.cuda.synchronize()
-    print(f"thr {thr}: {e0.elapsed_time(e1)/20*1e3:.1f} us per batch of {B}x4096, kept/frame {num.float().mean().item():.0f}")
+    ms = event_total_ms(lambda: iou3d_nms_cuda.nms_batch(boxes, None, thr), 20, 3)
+    keep, num = iou3d_nms_cuda.nms_batch(boxes, None, thr)
+    print(f"thr {thr}: {ms*1e3:.1f} us per batch of {B}x4096, kept/frame {num.float().mean().item():.0f}")

@@ -16,7 +16,6 @@ import argparse
 import json
 import os
 import sys
-import time
 
 import torch
 from torch.nn.utils import clip_grad_norm_
@@ -25,22 +24,16 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from lidardetection_amd import optim  # noqa: E402
 from lidardetection_amd.pointpillar import PointPillarKITTI  # noqa: E402
 
+from _measure import event_and_enqueue_ms  # noqa: E402
+
 HBM_PEAK = 8.0e12
 WD, CLIP = 0.01, 10.0
 
 
 def timed(fn, steps):
     """-> (GPU ms per step, host enqueue ms per step) of `steps` calls of fn(i)"""
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    start.record()
-    for i in range(steps):
-        fn(i)
-    end.record()
-    host = time.perf_counter() - t0
-    torch.cuda.synchronize()
-    return start.elapsed_time(end) / steps, host * 1e3 / steps
+    it = iter(range(steps))
+    return event_and_enqueue_ms(lambda: fn(next(it)), steps)
 
 
 def main():

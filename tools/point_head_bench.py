@@ -23,7 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
-from roi_loss_bench import enqueue_ms, kernel_count, wall_ms  # noqa: E402
+from _measure import enqueue_ms, event_ms, kernel_count  # noqa: E402
 from lidardetection_amd import point_head  # noqa: E402
 from lidardetection_amd.pcdet.ops.roiaware_pool3d import roiaware_pool3d_utils  # noqa: E402
 from lidardetection_amd.pcdet.utils.box_coder_utils import PointResidualCoder  # noqa: E402
@@ -146,12 +146,12 @@ def main():
                   "gts_per_frame": 20, "positives": int((t["point_cls_labels"] > 0).sum()), "ignored": int((t["point_cls_labels"] < 0).sum())}
         for col, fn, iters in [("fused_targets_fwd_bwd", fused, args.iters), ("fused_targets", fused_targets, args.iters),
                                ("torch_port_targets_fwd_bwd", port, args.ref_iters)]:
-            med, lo = wall_ms(fn, iters, 10)
-            n_kernels, n_d2h, n_items, names = kernel_count(fn)
+            med, lo, _ = event_ms(fn, iters, 10)
+            k = kernel_count(fn)
             result[col] = {"wall_ms_median": round(med, 4), "wall_ms_min": round(lo, 4), "enqueue_ms": round(enqueue_ms(fn, iters), 4),
-                           "device_kernels": n_kernels, "device_to_host_copies": n_d2h, "item_calls": n_items}
+                           "device_kernels": k["kernels"], "device_to_host_copies": k["d2h_copies"], "item_calls": k["item_calls"]}
             if col != "torch_port_targets_fwd_bwd":
-                result[col]["kernel_names"] = names
+                result[col]["kernel_names"] = k["names"]
         result["speedup_wall"] = round(result["torch_port_targets_fwd_bwd"]["wall_ms_median"] / result["fused_targets_fwd_bwd"]["wall_ms_median"], 1)
         print(json.dumps(result), flush=True)
 

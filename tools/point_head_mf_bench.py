@@ -23,7 +23,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 from point_head_bench import scene  # noqa: E402
-from roi_loss_bench import enqueue_ms, kernel_count, wall_ms  # noqa: E402
+from _measure import enqueue_ms, event_ms, kernel_count  # noqa: E402
 from lidardetection_amd import point_head, point_head_mf  # noqa: E402
 from lidardetection_amd.pcdet.models.dense_heads import PointHeadSimpleMultiFrame  # noqa: E402
 from lidardetection_amd.pcdet.utils.cfg import AttrDict  # noqa: E402
@@ -79,12 +79,12 @@ def main():
     result = {"tool": "point_head_mf_bench", "device": torch.cuda.get_device_name(0), "batch": B, "points": n, "gt_rows": M,
               "stack_frame_size": S, "positives": int((lab > 0).sum()), "ignored": int((lab < 0).sum())}
     for col, fn in (("fused", fused), ("s_calls", s_calls)):
-        med, lo = wall_ms(fn, args.iters, 10)
-        n_kernels, n_d2h, _, names = kernel_count(fn)
+        med, lo, _ = event_ms(fn, args.iters, 10)
+        k = kernel_count(fn)
         result[col] = {"wall_ms_median": round(med, 4), "wall_ms_min": round(lo, 4), "enqueue_ms": round(enqueue_ms(fn, args.iters), 4),
-                       "device_kernels": n_kernels, "device_to_host_copies": n_d2h}
+                       "device_kernels": k["kernels"], "device_to_host_copies": k["d2h_copies"]}
         if col == "fused":
-            result[col]["kernel_names"] = names
+            result[col]["kernel_names"] = k["names"]
     result["speedup_wall"] = round(result["s_calls"]["wall_ms_median"] / result["fused"]["wall_ms_median"], 2)
     print(json.dumps(result), flush=True)
 

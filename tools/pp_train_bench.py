@@ -5,10 +5,10 @@ scatter), and reports the peak device memory of each:
   pfn_scatter  PFN + scatter forward + backward (gradients of the linear weight and the norm's weight / bias) on a fixed
                channels-last canvas gradient;
   full_step    PointPillarKITTI.train_loss + backward, against the same step on the torch PFN (float32) and scatter (the stock
-               step of tests/test_gpu_pfn_train.py).
+               step of tests/_pp_train_torch.py).
 
-Inputs: 16 synthetic KITTI-like clouds (8 uniform, 8 ring) through BatchVoxelizer at 16 000 voxels per frame.  Device events after
-warm-up, the median of --iters; peak memory from torch.cuda.max_memory_allocated above what was allocated before the call.
+Inputs: 16 synthetic KITTI-like clouds (8 uniform, 8 ring) through BatchVoxelizer at 16 000 voxels per frame.  Device events per call after
+warm-up (_measure.event_ms), the median of --iters; peak memory from torch.cuda.max_memory_allocated above what was allocated before the call.
 Prints one JSON line.
 
   python tools/pp_train_bench.py [--iters 20] [--rocprof OUTDIR]
@@ -17,51 +17,21 @@ Prints one JSON line.
 `rocprofv3 --kernel-trace --stats --output-format csv -d OUTDIR`, so the kernel statistics come from a run of their own.
 """
 import argparse
-import importlib.util
 import json
 import os
 import subprocess
 import sys
 
-import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))    # the workload builders and restatements the tests use
 
 from lidardetection_amd import pillar_ops, synth  # noqa: E402
 
-
-def load_test_module():
-    """the workloads and the stock step live in the GPU test file; loading it by path keeps one copy"""
-    spec = importlib.util.spec_from_file_location("_pfn_train_tests", os.path.join(ROOT, "tests", "test_gpu_pfn_train.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-def time_ms(fn, iters, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    times = []
-    for _ in range(iters):
-        start.record()
-        fn()
-        end.record()
-        end.synchronize()
-        times.append(start.elapsed_time(end))
-    return float(np.median(times)), float(np.min(times))
-
-
-def peak_mb(fn):
-    torch.cuda.synchronize()
-    base = torch.cuda.memory_allocated()
-    torch.cuda.reset_peak_memory_stats()
-    fn()
-    torch.cuda.synchronize()
-    return round((torch.cuda.max_memory_allocated() - base) / 2 ** 20, 1)
+import _pp_train_torch as T  # noqa: E402
+from _measure import event_ms, peak_mb  # noqa: E402
 
 
 def main():
@@ -72,12 +42,11 @@ def main():
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("pp_train_bench: no GPU")
-    T = load_test_module()
     dev = T.DEV
     B = 16
-    vox, nv = T._bs16_voxels(B=B)
+    vox, nv = T.bs16_voxels(B=B)
     total = vox["voxel_offsets"][B:B + 1]
-    m = T._vfe()
+    m = T.vfe()
     layer = m.pfn_layers[0]
     params = [layer.linear.weight, layer.norm.weight, layer.norm.bias]
     G = torch.randn(B, 64, 496, 432, device=dev).contiguous(memory_format=torch.channels_last)
@@ -101,25 +70,25 @@ def main():
 
     result = {"tool": "pp_train_bench", "device": torch.cuda.get_device_name(0), "batch": B, "pillars": nv,
               "padded_rows": int(vox["voxels"].shape[0])}
-    med, mn = time_ms(fused_pfn, args.iters, 3)
+    med, mn, _ = event_ms(fused_pfn, args.iters, 3)
     w = {"fused_ms_median": round(med, 4), "fused_ms_min": round(mn, 4), "fused_peak_mb": peak_mb(fused_pfn)}
     if not args.fused_only:
-        med_t, mn_t = time_ms(torch_pfn, args.iters, 3)
+        med_t, mn_t, _ = event_ms(torch_pfn, args.iters, 3)
         w.update({"torch_ms_median": round(med_t, 3), "torch_ms_min": round(mn_t, 3), "torch_peak_mb": peak_mb(torch_pfn),
                   "speedup": round(med_t / med, 1)})
     result["pfn_scatter"] = w
 
     from lidardetection_amd.pointpillar import PointPillarKITTI
-    pts, offs, gt = T._pp_inputs(B, 5)
+    pts, offs, gt = T.pp_inputs(B, 5)
     torch.manual_seed(4)
     pp = PointPillarKITTI(batch_size=B, device=dev).train()
     pparams = [p for p in pp.parameters() if p.requires_grad]
     fused_step = lambda: torch.autograd.grad(sum(pp.train_loss(pts, offs, gt)), pparams)                 # noqa: E731
-    stock_step = lambda: torch.autograd.grad(sum(T._stock_loss(pp, pts, offs, gt, torch.float32)), pparams)            # noqa: E731
-    med, mn = time_ms(fused_step, max(args.iters // 2, 3), 2)
+    stock_step = lambda: torch.autograd.grad(sum(T.stock_loss(pp, pts, offs, gt, torch.float32)), pparams)            # noqa: E731
+    med, mn, _ = event_ms(fused_step, max(args.iters // 2, 3), 2)
     w = {"fused_ms_median": round(med, 3), "fused_ms_min": round(mn, 3), "fused_peak_mb": peak_mb(fused_step)}
     if not args.fused_only:
-        med_t, mn_t = time_ms(stock_step, max(args.iters // 2, 3), 2)
+        med_t, mn_t, _ = event_ms(stock_step, max(args.iters // 2, 3), 2)
         w.update({"torch_ms_median": round(med_t, 3), "torch_ms_min": round(mn_t, 3), "torch_peak_mb": peak_mb(stock_step),
                   "speedup": round(med_t / med, 2)})
     result["full_step"] = w

@@ -14,7 +14,6 @@ import argparse
 import json
 import os
 import sys
-import time
 
 import numpy as np
 import torch
@@ -28,6 +27,8 @@ from lidardetection_amd.pcdet.ops.iou3d_nms import iou3d_nms_utils  # noqa: E402
 from lidardetection_amd.pcdet.utils import common_utils  # noqa: E402
 from lidardetection_amd.pcdet.utils.cfg import AttrDict  # noqa: E402
 from lidardetection_amd.pvrcnn import TARGET_CONFIG  # noqa: E402
+
+from _measure import enqueue_ms, event_ms, kernel_count  # noqa: E402
 
 
 def looped_assign(cfg, rois, roi_scores, roi_labels, gt_boxes):
@@ -98,45 +99,6 @@ def looped_assign(cfg, rois, roi_scores, roi_labels, gt_boxes):
             "roi_labels": o_labels, "reg_valid_mask": reg_valid, "rcnn_cls_labels": cls}
 
 
-def wall_ms(fn, iters, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    times = []
-    for _ in range(iters):
-        start.record()
-        fn()
-        end.record()
-        end.synchronize()
-        times.append(start.elapsed_time(end))
-    return float(np.median(times)), float(np.min(times))
-
-
-def enqueue_ms(fn, iters):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(iters):
-        fn()
-    t1 = time.perf_counter()
-    torch.cuda.synchronize()
-    return (t1 - t0) / iters * 1e3
-
-
-def kernel_count(fn):
-    from torch.profiler import ProfilerActivity, profile
-    fn()
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-        fn()
-        torch.cuda.synchronize()
-    names = [e.name for e in prof.events() if str(e.device_type).endswith("CUDA") and "memcpy" not in e.name.lower()
-             and "memset" not in e.name.lower()]
-    copies = [e.name for e in prof.events() if str(e.device_type).endswith("CUDA") and "memcpy" in e.name.lower()]
-    short = lambda n: n.split("<")[0].split("(")[0].strip()   # noqa: E731  templated torch kernels carry names of several KB
-    return len(names), len(copies), sorted({short(n) for n in names})
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=200)
@@ -156,12 +118,12 @@ def main():
     result = {"tool": "proposal_target_bench", "device": torch.cuda.get_device_name(0), "batch": 8, "rois": 512, "max_gt": 40,
               "roi_per_image": cfg.ROI_PER_IMAGE}
     for name, fn, iters in [("hip", hip, args.iters), ("hip_given_random_numbers", hip_fixed, args.iters), ("looped_port", port, args.ref_iters)]:
-        med, lo = wall_ms(fn, iters, 5)
-        n_kernels, n_copies, names = kernel_count(fn)
+        med, lo, _ = event_ms(fn, iters, 5)
+        k = kernel_count(fn)
         result[name] = {"wall_ms_median": round(med, 4), "wall_ms_min": round(lo, 4), "enqueue_ms": round(enqueue_ms(fn, iters), 4),
-                        "device_kernels": n_kernels, "device_copies": n_copies}
+                        "device_kernels": k["kernels"], "device_copies": k["copies"]}
         if name != "looped_port":
-            result[name]["kernel_names"] = names
+            result[name]["kernel_names"] = k["names"]
     result["speedup_wall"] = round(result["looped_port"]["wall_ms_median"] / result["hip"]["wall_ms_median"], 1)
     print(json.dumps(result), flush=True)
 

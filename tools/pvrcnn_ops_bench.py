@@ -9,18 +9,14 @@ from lidardetection_amd.pcdet.ops.pointnet2.pointnet2_stack import pointnet2_uti
 from lidardetection_amd.pcdet.ops.pointnet2.pointnet2_batch import pointnet2_utils as pn_batch
 from lidardetection_amd.pcdet.ops.roiaware_pool3d import roiaware_pool3d_utils as roiaware
 from lidardetection_amd.pcdet.ops.roipoint_pool3d import roipoint_pool3d_utils as roipoint
+from _measure import event_total_ms
 
 dev = torch.device("cuda:0")
 B, NKP, NROI = 8, 2048, 128
 
 
 def timeit(fn, n=10):
-    for _ in range(3): fn()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize(); e0.record()
-    for _ in range(n): fn()
-    e1.record(); torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n * 1e3
+    return event_total_ms(fn, n, 3) * 1e3      # us per call
 
 
 frames = [synth.cloud_ring(2000 + f)[:19968] for f in range(B)]

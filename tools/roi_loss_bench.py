@@ -13,7 +13,6 @@ import argparse
 import json
 import os
 import sys
-import time
 
 import numpy as np
 import torch
@@ -26,6 +25,8 @@ from lidardetection_amd import roi_loss  # noqa: E402
 from lidardetection_amd.pcdet.models.roi_heads.roi_head_template import RoIHeadTemplate, _corners, _smooth_l1  # noqa: E402
 from lidardetection_amd.pcdet.utils.cfg import AttrDict  # noqa: E402
 from lidardetection_amd.pvrcnn import LOSS_CONFIG, TARGET_CONFIG  # noqa: E402
+
+from _measure import enqueue_ms, event_ms, kernel_count  # noqa: E402
 
 
 def ported_get_loss(d, lw):
@@ -65,46 +66,6 @@ def ported_get_loss(d, lw):
     loss = cls + loss_reg
     tb["rcnn_loss"] = loss.item()
     return loss, tb
-
-
-def wall_ms(fn, iters, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    times = []
-    for _ in range(iters):
-        start.record()
-        fn()
-        end.record()
-        end.synchronize()
-        times.append(start.elapsed_time(end))
-    return float(np.median(times)), float(np.min(times))
-
-
-def enqueue_ms(fn, iters):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(iters):
-        fn()
-    t1 = time.perf_counter()
-    torch.cuda.synchronize()
-    return (t1 - t0) / iters * 1e3
-
-
-def kernel_count(fn):
-    from torch.profiler import ProfilerActivity, profile
-    fn()
-    torch.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-        fn()
-        torch.cuda.synchronize()
-    dev_events = [e.name for e in prof.events() if str(e.device_type).endswith("CUDA")]
-    names = [n for n in dev_events if "memcpy" not in n.lower() and "memset" not in n.lower()]
-    d2h = [n for n in dev_events if "memcpy" in n.lower() and "dtoh" in n.lower().replace(" ", "")]
-    items = sum(1 for e in prof.events() if e.name == "aten::item")       # scalar reads: each waits for the device
-    short = lambda n: n.split("<")[0].split("(")[0].strip()   # noqa: E731
-    return len(names), len(d2h), items, sorted({short(n) for n in names})
 
 
 def main():
@@ -154,12 +115,12 @@ def main():
               "fg_rows": int(d["reg_valid_mask"].sum())}
     for name, fn, iters in [("fused_fwd_bwd", fused, args.iters), ("fused_forward", fused_forward, args.iters),
                             ("mirror_get_loss", mirror_get_loss, args.iters), ("torch_port_fwd_bwd", port, args.ref_iters)]:
-        med, lo = wall_ms(fn, iters, 10)
-        n_kernels, n_d2h, n_items, names = kernel_count(fn)
+        med, lo, _ = event_ms(fn, iters, 10)
+        k = kernel_count(fn)
         result[name] = {"wall_ms_median": round(med, 4), "wall_ms_min": round(lo, 4), "enqueue_ms": round(enqueue_ms(fn, iters), 4),
-                        "device_kernels": n_kernels, "device_to_host_copies": n_d2h, "item_calls": n_items}
+                        "device_kernels": k["kernels"], "device_to_host_copies": k["d2h_copies"], "item_calls": k["item_calls"]}
         if name != "torch_port_fwd_bwd":
-            result[name]["kernel_names"] = names
+            result[name]["kernel_names"] = k["names"]
     result["speedup_wall"] = round(result["torch_port_fwd_bwd"]["wall_ms_median"] / result["fused_fwd_bwd"]["wall_ms_median"], 1)
     print(json.dumps(result), flush=True)
 

@@ -1,9 +1,10 @@
 """SECOND-KITTI (BASELINE.json configs[2]) forward + NMS, bs 16 on one MI355X: frames/s and per-stage GPU time."""
-import os, sys, time
+import os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from lidardetection_amd import synth
 from lidardetection_amd.second import SECONDKitti
+from _measure import event_total_ms, host_ms
 
 dev = torch.device("cuda:0")
 torch.backends.cudnn.benchmark = True
@@ -16,20 +17,12 @@ m = SECONDKitti(batch_size=B, n_max=max(sizes), device=dev).randomize_for_bench(
 
 
 def gpu_time(fn, n=10):
-    for _ in range(2): r = fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(n): r = fn()
-    b.record(); torch.cuda.synchronize()
-    return a.elapsed_time(b) / n, r
+    return event_total_ms(fn, n, 2), fn()
 
 
 with torch.no_grad():
-    for _ in range(4): out = m(pts, offs)
-    torch.cuda.synchronize(); t0 = time.perf_counter()
-    for _ in range(10): out = m(pts, offs)
-    torch.cuda.synchronize(); dt = (time.perf_counter() - t0) / 10
+    dt = host_ms(lambda: m(pts, offs), 10, warmup=4) / 1e3
+    out = m(pts, offs)
     print(f"SECOND-KITTI bs {B}: {B / dt:.1f} frames/s ({dt * 1e3:.2f} ms/step), kept/frame {out[3].float().mean().item():.1f}")
     t1, (feats, coords) = gpu_time(lambda: m.voxelize_vfe(pts, offs))
     t2, canvas = gpu_time(lambda: m.sparse_backbone(feats, coords))

@@ -18,7 +18,6 @@ import argparse
 import json
 import os
 import sys
-import time
 
 import numpy as np
 import torch
@@ -26,6 +25,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from lidardetection_amd import optim, spconv, synth  # noqa: E402
 from lidardetection_amd.second import SECONDKitti  # noqa: E402
+
+from _measure import host_ms  # noqa: E402
 
 CONFIGS = [("stock", "stock"), ("fused", "stock"), ("stock", "fused"), ("fused", "fused")]      # (sparse, backbone)
 SIZES = np.array([[3.9, 1.6, 1.56], [0.8, 0.6, 1.73], [1.76, 0.6, 1.73]], np.float32)
@@ -47,16 +48,6 @@ def inputs(B, dev, seed=0):
     return pts, offs, torch.from_numpy(gt).to(dev), [int(v) for v in lens]
 
 
-def timed(fn, steps):
-    """ms per call of `steps` calls of fn(), host clock, the queue drained before and after"""
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(steps):
-        fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3 / steps
-
-
 def bench_steps(B, dev, args):
     torch.manual_seed(0)
     model = SECONDKitti(batch_size=B, device=dev).train()
@@ -68,11 +59,11 @@ def bench_steps(B, dev, args):
         fns[f"sparse={sparse},backbone={backbone}"] = (
             lambda s=sparse, b=backbone: model.train_step(pts, offs, gt, opt, host_offsets=host_offs, sparse=s, backbone=b))
     for fn in fns.values():
-        timed(fn, args.warmup)
+        host_ms(fn, args.warmup)
     rows = {k: [] for k in fns}
     for _ in range(args.rounds):                     # alternate, so that a drift of the machine hits every configuration
         for k, fn in fns.items():
-            rows[k].append(timed(fn, args.steps))
+            rows[k].append(host_ms(fn, args.steps))
     with torch.no_grad():
         vox = model.voxelizer(pts, offs, model.n_max, compact=True, host_offsets=host_offs)
         voxels = int(vox["voxel_offsets"][B])
@@ -103,11 +94,11 @@ def bench_dense_bev(B, dev, args, C=128, D=2, H=200, W=176, rows_per_frame=12000
     assert torch.equal(run(True), run(False))
     fns = {"fallback": lambda: run(False), "kernels": lambda: run(True)}
     for fn in fns.values():
-        timed(fn, args.warmup)
+        host_ms(fn, args.warmup)
     rows = {k: [] for k in fns}
     for _ in range(args.rounds):
         for k, fn in fns.items():
-            rows[k].append(timed(fn, 4 * args.steps))
+            rows[k].append(host_ms(fn, 4 * args.steps))
     return {"rows": int(idx.shape[0]), "map": [B, C * D, H, W], "ms_fwd_bwd_best": {k: min(v) for k, v in rows.items()},
             "ms_fwd_bwd_all_rounds": rows}
 

@@ -1,6 +1,6 @@
 """SECOND-KITTI sparse-conv stack micro-benchmark (BASELINE.json configs[2] shapes): rulebook + implicit-GEMM time per layer,
 achieved fp32 TFLOP/s = 2 * sum_k n_k * Cin * Cout / time, vs the 157.3 TFLOP/s fp32 MFMA peak."""
-import os, sys, time
+import os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from lidardetection_amd import synth, spconv
@@ -8,6 +8,7 @@ from lidardetection_amd.pcdet.models.backbones_3d import spconv_backbone, vfe
 from lidardetection_amd.pcdet.utils.cfg import AttrDict
 from lidardetection_amd.voxelizer import BatchVoxelizer
 from lidardetection_amd.spconv import ops
+from _measure import event_total_ms, host_ms
 
 dev = torch.device("cuda:0")
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 16
@@ -19,13 +20,8 @@ bd = vfe.MeanVFE(AttrDict(), 4)(bd)
 m = spconv_backbone.VoxelBackBone8x(AttrDict(), 4, [1408, 1600, 40]).to(dev).eval()
 print(f"B={B} input voxels {bd['voxel_features'].shape[0]}")
 with torch.no_grad():
-    for _ in range(2):
-        out = m(dict(bd))
-    torch.cuda.synchronize(); t = time.perf_counter()
-    for _ in range(5):
-        out = m(dict(bd))
-    torch.cuda.synchronize()
-    print(f"VoxelBackBone8x forward (rulebooks rebuilt each call): {(time.perf_counter()-t)/5*1e3:.2f} ms per batch of {B}")
+    fwd_ms = host_ms(lambda: m(dict(bd)), 5, warmup=2)
+    print(f"VoxelBackBone8x forward (rulebooks rebuilt each call): {fwd_ms:.2f} ms per batch of {B}")
     # per-layer implicit GEMM flops
     x = spconv.SparseConvTensor(bd["voxel_features"], bd["voxel_coords"].int(), m.sparse_shape, B)
     tot_flops, tot_t = 0.0, 0.0
@@ -42,12 +38,7 @@ with torch.no_grad():
                 fl = 2.0 * nk * c.in_channels * c.out_channels
                 w = c.weight.reshape(-1, c.in_channels, c.out_channels).contiguous()
                 f = x.features.contiguous()
-                for _ in range(3): ops._implicit_gemm(f, nbr, w, None, nbr.shape[0])
-                torch.cuda.synchronize(); e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for _ in range(10): ops._implicit_gemm(f, nbr, w, None, nbr.shape[0])
-                e1.record(); torch.cuda.synchronize()
-                ms = e0.elapsed_time(e1) / 10
+                ms = event_total_ms(lambda: ops._implicit_gemm(f, nbr, w, None, nbr.shape[0]), 10, 3)
                 tot_flops += fl; tot_t += ms
                 def eff(T):   # useful fraction of MFMA rows if valid rows were packed per (T-row tile, offset)
                     n = nbr.shape[0]; pad = (-n) % T

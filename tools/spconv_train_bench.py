@@ -1,11 +1,12 @@
 """SECOND sparse backbone, training step shape: forward + backward (dgrad + wgrad) per 16 frames (ring clouds)."""
-import os, sys, time
+import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from lidardetection_amd import synth
 from lidardetection_amd.pcdet.models.backbones_3d import spconv_backbone, vfe
 from lidardetection_amd.pcdet.utils.cfg import AttrDict
 from lidardetection_amd.voxelizer import BatchVoxelizer
+from _measure import host_ms
 dev = torch.device("cuda:0"); B = 16
 frames = [synth.cloud_ring(2000 + f) for f in range(B)]
 o = BatchVoxelizer(synth.SEC_VOXEL, synth.SEC_RANGE, 5, 16000).voxelize_frames(frames, device=dev)
@@ -21,13 +22,6 @@ def step():
     loss.backward()
 
 
-for _ in range(3): step()
-torch.cuda.synchronize(); t0 = time.perf_counter()
-for _ in range(5): step()
-torch.cuda.synchronize()
-print(f"VoxelBackBone8x train-mode forward+backward: {(time.perf_counter() - t0) / 5 * 1e3:.2f} ms per 16 frames")
+print(f"VoxelBackBone8x train-mode forward+backward: {host_ms(step, 5, warmup=3):.2f} ms per 16 frames")
 with torch.no_grad():
-    torch.cuda.synchronize(); t0 = time.perf_counter()
-    for _ in range(5): m(dict(bd))
-    torch.cuda.synchronize()
-    print(f"  forward only (train-mode BN, module sequence): {(time.perf_counter() - t0) / 5 * 1e3:.2f} ms")
+    print(f"  forward only (train-mode BN, module sequence): {host_ms(lambda: m(dict(bd)), 5):.2f} ms")

@@ -7,6 +7,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 torch.backends.cudnn.benchmark = True
 from lidardetection_amd.pointpillar import PointPillarKITTI
 from lidardetection_amd.bev_backbone import FoldedBEVBackbone
+from _measure import event_total_ms
 dev = torch.device("cuda:0")
 B = 16
 m = PointPillarKITTI(batch_size=B, max_voxels=16000, n_max=20000, device=dev).randomize_for_bench(0)
@@ -34,12 +35,7 @@ def halves():
 
 def t(fn, n=10):
     with torch.no_grad():
-        for _ in range(3): fn()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize(); e0.record()
-        for _ in range(n): fn()
-        e1.record(); torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n
+        return event_total_ms(fn, n, 3)
 
 
 with torch.no_grad():

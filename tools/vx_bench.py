@@ -10,6 +10,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from lidardetection_amd import synth  # noqa: E402
 from lidardetection_amd.voxelizer import BatchVoxelizer  # noqa: E402
+from _measure import event_total_ms  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--cloud", default="uniform")
@@ -29,16 +30,7 @@ offs = torch.tensor(np.concatenate([[0], np.cumsum(sizes)]), dtype=torch.int32, 
 for algo in [int(x) for x in a.algos.split(",")]:
     vz = BatchVoxelizer(synth.PP_VOXEL, synth.PP_RANGE, 32, 16000, algo=algo)
     out = vz.alloc_outputs(a.batch, dev)
-    for _ in range(5):
-        vz(pts, offs, max(sizes), out=out, resident=a.resident)
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(a.iters):
-        vz(pts, offs, max(sizes), out=out, resident=a.resident)
-    e1.record()
-    torch.cuda.synchronize()
-    ms = e0.elapsed_time(e1) / a.iters
+    ms = event_total_ms(lambda: vz(pts, offs, max(sizes), out=out, resident=a.resident), a.iters, 5)
     if a.flush:
         junk = torch.empty(256 * 1024 * 1024, dtype=torch.float32, device=dev)
         evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.iters)]

@@ -5,6 +5,7 @@ import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from lidardetection_amd import synth
 from lidardetection_amd.voxelizer import BatchVoxelizer
+from _measure import event_total_ms
 dev = torch.device("cuda:0")
 
 
@@ -14,13 +15,7 @@ def run(name, frames, voxel, rng, P, maxv, C):
     offs = torch.tensor(np.concatenate([[0], np.cumsum(sizes)]), dtype=torch.int32, device=dev)
     vz = BatchVoxelizer(voxel, rng, P, maxv, C)
     out = vz.alloc_outputs(len(frames), dev)
-    for _ in range(5): vz(pts, offs, max(sizes), out=out)
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(50): vz(pts, offs, max(sizes), out=out)
-    e1.record(); torch.cuda.synchronize()
-    ms = e0.elapsed_time(e1) / 50
+    ms = event_total_ms(lambda: vz(pts, offs, max(sizes), out=out), 50, 5)
     rows = int(out["voxel_offsets"][-1])
     alg = 4 * C * sum(sizes) + rows * (P * C * 4 + 20)
     print(f"{name}: {ms * 1e3:.1f} us/launch, {len(frames)} frames, rows {rows}, err flag {vz.error_flag(len(frames), max(sizes), dev)}, "

@@ -2,23 +2,18 @@
 layer shapes of the BEV backbones (PointPillar bs 16: 64 @ 248x216, 128 @ 124x108, 256 @ 62x54; SECOND bs 16: 128 @ 200x176,
 256 @ 100x88).  Prints per shape: ms, direct-convolution-equivalent TFLOP/s (2 * 9 * Cin * Cout * pixels), MFMA-issued TFLOP/s
 (the 16 / 36 of it that Winograd really multiplies) as a fraction of the 157.3 TFLOP/s fp32 peak, max error vs MIOpen."""
-import os, sys, time
+import os, sys
 import torch, torch.nn.functional as F
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from lidardetection_amd import wino
 from lidardetection_amd.bev_backbone import bias_act_
+from _measure import event_total_ms
 dev = torch.device("cuda:0")
 torch.backends.cudnn.benchmark = True
 
 
 def ev(fn, n=20, warm=3):
-    for _ in range(warm): fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(n): fn()
-    b.record(); torch.cuda.synchronize()
-    return a.elapsed_time(b) / n
+    return event_total_ms(fn, n, warm)
 
 
 shapes = [(16, 64, 248, 216), (16, 128, 124, 108), (16, 256, 62, 54), (16, 128, 200, 176), (16, 256, 100, 88)]
